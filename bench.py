@@ -204,6 +204,19 @@ def gradient_error(m, model, x, y):
     return flat, worst, "%d points of the benchmark batch, the engine's weights after the timed steps, %d tensors; fp64 NumPy oracle" % (len(x), len(g_ref))
 
 
+def dump_outputs(e, directory):
+    """--dump-outputs DIR: what the timed path handed back after its LAST timed step, one DIR/<name>.npy per array (at most P
+    values each: 0.6 MB in all for the benchmark model): the step's loss and gradient (after the all-reduce when N > 1), the updated
+    parameters and Adam moments.  Read after the timed region's fence and before any other leg steps the engine; the inputs are
+    seeded, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(directory, exist_ok=True)
+    loss, grad = e.grad_read()
+    m, v, _ = e.get_opt_state()
+    arrays = {"loss": np.asarray([loss], dtype=grad.dtype), "grad": grad, "params": e.get_flat(), "adam_m": m, "adam_v": v}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside any launcher: start N ranks of this script (one process per GPU), hand them
     the torchrun-style environment, watch them.  Rank 0 inherits stdout and prints the JSON line; every rank's stderr is
@@ -287,7 +300,12 @@ def main():
     ap.add_argument("--config-steps", type=int, default=8)
     ap.add_argument("--given-w-points", type=int, default=1 << 17)
     ap.add_argument("--force-dist", action="store_true", help="build the RCCL communicator and all-reduce even at world size 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss, gradient, updated parameters and Adam moments "
+                         "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -389,6 +407,8 @@ def main():
         dt_max = dt = comm.all_reduce_float(e, dt, op="max")
         comm_build_s = comm.all_reduce_float(e, comm_build_s, op="max")
     loss = e.last_loss()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(e, args.dump_outputs)
     dist_info = {"rccl_ranks_seen": ranks_seen, "world": world, "comm_build_s": comm_build_s,
                  "ms_per_step_rank_min": dt_min / args.steps * 1e3, "ms_per_step_rank_max": dt_max / args.steps * 1e3,
                  "numa_node_rank0": numa_node,

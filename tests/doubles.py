@@ -143,6 +143,16 @@ class OracleEngine(object):
     def last_loss(self):
         return float(self.grad_buf[-1])
 
+    # ---- what `bench.py --dump-outputs` reads back ----------------------------------------------------
+    def grad_read(self):
+        return float(self.grad_buf[-1]), self.grad_buf[:-1].copy()
+
+    def get_flat(self):
+        return self.theta.copy()
+
+    def get_opt_state(self):
+        return self.m.copy(), self.v.copy(), self.t
+
 
 class GlooComm(object):
     """RcclComm's interface on a gloo process group (CPU)."""

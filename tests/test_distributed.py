@@ -262,6 +262,42 @@ def test_bench_self_launch_two_ranks_prints_one_json_line():
     assert d["value"] > 0 and abs(d["value"] - 96 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
 
 
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` on the engine double: the loss, gradient, parameters and Adam moments of the LAST timed step,
+    the same in two runs with the same arguments, and equal to an oracle replay of exactly W + K steps on the benchmark's seeded
+    inputs (so --steps is the number of steps that ran and nothing stepped the engine between the timed region and the dump)"""
+    import json
+    import nif_amd
+    warmup, steps, points = 1, 3, 48
+    args = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--points", str(points), "--no-cpu-baseline",
+            "--ramp-steps", "0"]
+    runs = []
+    for name in ("a", "b"):
+        r = _run_bench({}, args + ["--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        runs.append({p.stem: np.load(str(p)) for p in (tmp_path / name).glob("*.npy")})
+    a, b = runs
+    assert sorted(a) == ["adam_m", "adam_v", "grad", "loss", "params"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    import bench
+    spec = O.Spec("NIFMultiScale", bench.CFG_SHAPE, bench.CFG_PARAM)
+    th = O.flatten(O.init_weights(spec, np.random.default_rng(1)))
+    m, v = np.zeros_like(th), np.zeros_like(th)
+    x, y = nif_amd.data.synthetic_wave_batch(points, seed=100)
+    x, y = x.astype(np.float32).astype(np.float64), y.astype(np.float32).astype(np.float64)
+    adam = nif_amd.Adam(1e-3).as_struct()
+    for t in range(1, warmup + steps + 1):
+        loss, g = O.loss_and_grad(spec, O.unflatten(spec, th), x, y, None, batch_global=points)
+        g = O.flatten(g)
+        th, m, v = O.adam_step(th, g, m, v, t, lr=adam.lr, b1=adam.beta1, b2=adam.beta2, eps=adam.eps)
+    for k, want in (("loss", [loss]), ("grad", g), ("params", th), ("adam_m", m), ("adam_v", v)):
+        np.testing.assert_allclose(a[k], want, rtol=1e-12, atol=0, err_msg=k)
+
+
 def test_bench_self_launch_eight_ranks_self_check_fields():
     """world 8 -- the size of the driver's scaling run -- on the engine double: the all-reduce self-check (rank + 1 through the step's
     own collective: 36 on every rank) runs before the warm-up and the line carries what lets the driver see that N ranks took part"""
