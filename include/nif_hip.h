@@ -235,6 +235,43 @@ typedef enum { NIF_LOSS_MSE_ = 0, NIF_LOSS_MAE_ = 1, NIF_LOSS_HUBER_ = 2, NIF_LO
 int nif_set_loss(nif_ctx* ctx, int32_t kind /* nif_loss */);
 /* optimizer.apply_gradients with Adam on the (already all-reduced) nif_grad_dev() buffer */
 int nif_adam_step_dev(nif_ctx* ctx, const nif_adam* opt);
+/* The reference's other optimizers (nif/optimizers/__init__.py:1-20), applied on the same buffers and at the same point of the step as
+ * Adam: after the all-reduce, with the weight-regulariser term added first.  t = the context's iteration count after the increment
+ * (Keras' iterations + 1); lr_d = lr / (1 + decay (t - 1)) is Keras' legacy time-inverse decay (_decayed_lr).
+ *   NIF_OPT_LION       nif/optimizers/external_optimizers.py:631-735 (dense apply :682-703), slot m:
+ *                      theta -= lr_d (sign(b1 m + (1-b1) g) + weight_decay theta);  m = b2 m + (1-b2) g  (from the old m)
+ *   NIF_OPT_ADABELIEF  external_optimizers.py:322-628 (dense apply :456-530), slots m, v and (amsgrad) vhat: optional warm-up /
+ *                      linear decay of lr_d over total_steps, rectification behind sma_threshold (RAdam), v += eps
+ *   NIF_OPT_ADAM       nif_adam_step_dev / nif_graph_launch, bit for bit (decay and the AdaBelief fields must be zero)
+ * The per-step scalars (learning rate, both bias corrections, r_t, the branch) are formed once per step in fp64: on the host for an
+ * eager step, per block from device memory inside a captured graph. */
+typedef enum { NIF_OPT_ADAM = 0, NIF_OPT_LION = 1, NIF_OPT_ADABELIEF = 2 } nif_opt_kind;
+#define NIF_OPT_RECTIFY 1      /* AdaBelief rectify=True (the reference's default) */
+#define NIF_OPT_AMSGRAD 2      /* AdaBelief amsgrad=True: the third slot vhat, allocated on first use */
+typedef struct {               /* 72 bytes; reserved fields must be zero */
+  int32_t kind, flags;         /* nif_opt_kind, NIF_OPT_* bits */
+  float lr, beta1, beta2, eps; /* Lion: eps unused */
+  float weight_decay;          /* Lion `wd`, AdaBelief `weight_decay` */
+  float decay;                 /* Keras legacy `decay` keyword */
+  float sma_threshold, warmup_proportion, min_lr;
+  int32_t reserved0;
+  int64_t total_steps;         /* AdaBelief warm-up / decay horizon; 0 = off */
+  int32_t reserved[4];
+} nif_opt;
+/* optimizer.apply_gradients with any kind on nif_grad_dev() (the fused-tail form under the same conditions as nif_adam_step_dev).
+ * nif_train_step and nif_train_step_multi stay Adam-only. */
+int nif_opt_step_dev(nif_ctx* ctx, const nif_opt* opt);
+/* nif_graph_launch for a graph whose steps were recorded by nif_opt_step_dev: NIF_ERR_INVALID when opt's kind or amsgrad flag is not
+ * the recorded one.  A capture that mixes kinds fails at the step that mixes them (NIF_ERR_STATE); nif_graph_launch refuses a graph
+ * recorded with non-Adam steps (NIF_ERR_STATE). */
+int nif_graph_launch_opt(nif_ctx* ctx, int32_t graph_id, const nif_opt* opt);
+/* optimizer slots for checkpoints: slot 0 m, 1 v, 2 vhat (reads zeros before vhat exists; a write allocates it) */
+int nif_get_opt_slot(nif_ctx* ctx, int32_t slot, float* host, int64_t n);
+int nif_set_opt_slot(nif_ctx* ctx, int32_t slot, const float* host, int64_t n);
+/* the per-step scalars of iteration t (>= 1) as the kernels receive them, in fp64 (host-only, no context):
+ * out[0] learning rate, out[1] 1 - b1^t, out[2] 1 - b2^t, out[3] r_t, out[4] 1 when the update divides by (v_hat + eps), else 0
+ * (AdaBelief's momentum branch); Lion fills out[0] only */
+int nif_opt_scalars(const nif_opt* opt, int64_t t, double* out5);
 /* zero [grad | loss]: what a rank contributes to the step's all-reduce when its shard has no rows left (uneven shards of
  * Model.fit under data parallelism); the weight-regulariser term is still added by the following nif_adam_step_dev */
 int nif_zero_grad(nif_ctx* ctx);
@@ -245,7 +282,7 @@ int nif_reserve(nif_ctx* ctx, int64_t B_max, int32_t n_tangents);
 int nif_loss_and_grad(nif_ctx* ctx, const float* xin_host, const float* y_host, const float* sw_host_or_null,
                       int64_t B, float* loss_out, float* grad_host);        /* lbfgs.py:66-74 */
 int nif_train_step(nif_ctx* ctx, const float* xin_host, const float* y_host, const float* sw_host_or_null,
-                   int64_t B, const nif_adam* opt, float* loss_out);        /* Model.fit's train_step */
+                   int64_t B, const nif_adam* opt, float* loss_out);        /* Model.fit's train_step (Adam only) */
 /* Weight regularisers of cfg_parameter_net["l1_reg"/"l2_reg"] (nif/model.py:109-117: L2(l2) or else L1(l1) on
  * every ParameterNet kernel and bias): loss += l2*sum(w^2) + l1*sum(|w|) over theta[lo, hi); the gradient
  * term is added once, after the cross-rank all-reduce, inside nif_adam_step_dev / nif_loss_and_grad. */
@@ -310,7 +347,7 @@ int nif_comm_allreduce(nif_ctx* ctx, void* dev_buf, int64_t count, int32_t dtype
 /* every rank reached this call and ctx's stream has drained (one-word all-reduce + stream synchronise) */
 int nif_comm_barrier(nif_ctx* ctx);
 /* Model.fit's train_step on n GPUs from ONE process: rows split contiguously and evenly over the
- * contexts, per-shard loss/gradient, one grouped all-reduce, identical Adam update everywhere.  Host pointers. */
+ * contexts, per-shard loss/gradient, one grouped all-reduce, identical Adam update everywhere.  Host pointers.  Adam only. */
 int nif_train_step_multi(nif_ctx** ctxs, int32_t n, const float* xin_host, const float* y_host,
                          const float* sw_host_or_null, int64_t B, const nif_adam* opt, float* loss_out);
 

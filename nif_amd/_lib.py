@@ -53,6 +53,19 @@ class nif_adam(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
 
 
+OPT_ADAM, OPT_LION, OPT_ADABELIEF = 0, 1, 2
+OPT_RECTIFY, OPT_AMSGRAD = 1, 2
+
+
+class nif_opt(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("flags", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+        ("eps", C.c_float), ("weight_decay", C.c_float), ("decay", C.c_float), ("sma_threshold", C.c_float),
+        ("warmup_proportion", C.c_float), ("min_lr", C.c_float), ("reserved0", C.c_int32), ("total_steps", C.c_int64),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 _CTX = C.c_void_p
@@ -109,6 +122,11 @@ SIGNATURES = {
     "nif_set_loss": (C.c_int, [_CTX, C.c_int32]),
     "nif_sobolev_forward_dev": (C.c_int, [_CTX, _VP, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _VP, _VP]),
     "nif_adam_step_dev": (C.c_int, [_CTX, C.POINTER(nif_adam)]),
+    "nif_opt_step_dev": (C.c_int, [_CTX, C.POINTER(nif_opt)]),
+    "nif_graph_launch_opt": (C.c_int, [_CTX, C.c_int32, C.POINTER(nif_opt)]),
+    "nif_get_opt_slot": (C.c_int, [_CTX, C.c_int32, _VP, C.c_int64]),
+    "nif_set_opt_slot": (C.c_int, [_CTX, C.c_int32, _VP, C.c_int64]),
+    "nif_opt_scalars": (C.c_int, [C.POINTER(nif_opt), C.c_int64, C.POINTER(C.c_double)]),
     "nif_zero_grad": (C.c_int, [_CTX]),
     "nif_reserve": (C.c_int, [_CTX, C.c_int64, C.c_int32]),
     "nif_device_pci_bus_id": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32]),

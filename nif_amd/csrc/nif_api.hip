@@ -206,7 +206,8 @@ extern "C" int nif_destroy(nif_ctx* c) {
   for (hipEvent_t e : c->ev_chunk) hipEventDestroy(e);
   for (hipGraphExec_t ex : c->graphs) if (ex) (void)hipGraphExecDestroy(ex);
   if (c->adam_host) (void)hipHostFree(c->adam_host);
-  void* ptrs[] = {c->adam_dev, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
+  if (c->opt_host) (void)hipHostFree(c->opt_host);
+  void* ptrs[] = {c->adam_dev, c->opt_dev, c->vhat, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
                   c->DU, c->ZL, c->partial, c->loss_partial, c->dring, c->metric, c->tl, c->lWF, c->lWB, c->sWF4, c->sWB4, c->sWF4x, c->sWB4x, c->sWscale, c->sWF4h, c->sWB4h, c->ll_slots, c->ll_wpf, c->ll_wpb, c->stash_l, c->PHI, c->DPHI, c->DA, c->DZL, c->d_a, c->d_b, c->d_c, c->d_d};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->st) hipStreamDestroy(c->st);
@@ -1992,6 +1993,8 @@ extern "C" int nif_metric_read(nif_ctx* c, double* sum, double* cnt, int reset) 
 extern "C" int nif_adam_step_dev(nif_ctx* c, const nif_adam* opt) {
   if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
+  if (c->capturing && c->cap_kind > OPT_ADAM)
+    return fail(NIF_ERR_STATE, "nif_adam_step_dev: this capture already holds Lion / AdaBelief steps (one optimizer kind per graph)");
   HIPCHK(hipSetDevice(c->dev));
   if (c->tail_pending && !c->capturing && tail_can_defer(c)) {      // the step's row reduction and the update in ONE launch
     c->tail_pending = false;
@@ -2010,7 +2013,7 @@ extern "C" int nif_adam_step_dev(nif_ctx* c, const nif_adam* opt) {
   if (c->capturing) {      // inside nif_graph_begin / _end: hyper-parameters and iteration count come from device memory at replay time
     launch_adam_dev(c->theta, c->grad, c->m, c->v, c->P, c->adam_dev, c->st);
     HIPCHK(hipGetLastError());
-    c->step += 1; c->cap_steps += 1;
+    c->step += 1; c->cap_steps += 1; c->cap_kind = OPT_ADAM;
     c->packed = false; c->packed32 = false; c->packed_p32 = false;
     c->reg_applied = false;
     return NIF_OK;
@@ -2052,12 +2055,14 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
   if (!c->metric) { HIPCHK(hipMalloc(&c->metric, 2 * sizeof(double))); HIPCHK(hipMemsetAsync(c->metric, 0, 2 * sizeof(double), c->st)); }
   if (!c->adam_dev) HIPCHK(hipMalloc(&c->adam_dev, sizeof(AdamDev)));
   if (!c->adam_host) HIPCHK(hipHostMalloc(&c->adam_host, sizeof(AdamDev)));
+  if (!c->opt_dev) HIPCHK(hipMalloc(&c->opt_dev, sizeof(OptDev)));
+  if (!c->opt_host) HIPCHK(hipHostMalloc(&c->opt_host, sizeof(OptDev)));
   HIPCHK(hipStreamSynchronize(c->st));
   // (ensure_packed above did every first-use initialisation eagerly; the RECORDED sequence must start with the packing of whatever
   // weights the previous replay left behind)
   c->packed = false; c->packed32 = false; c->packed_p32 = false;
   HIPCHK(hipStreamBeginCapture(c->st, hipStreamCaptureModeRelaxed));
-  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step;
+  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step; c->cap_kind = -1; c->cap_ams = false;
   return NIF_OK;
 }
 extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
@@ -2074,12 +2079,15 @@ extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) { (void)hipGetLastError(); return fail(NIF_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
   c->graphs.push_back(ex); c->graph_steps.push_back(c->cap_steps);
+  c->graph_kind.push_back(c->cap_kind); c->graph_ams.push_back(c->cap_ams ? 1 : 0);
   *graph_id = (int32_t)c->graphs.size() - 1;
   return NIF_OK;
 }
 extern "C" int nif_graph_launch(nif_ctx* c, int32_t graph_id, const nif_adam* opt) {
   if (!c || !opt || graph_id < 0 || graph_id >= (int32_t)c->graphs.size() || !c->graphs[graph_id]) return fail(NIF_ERR_INVALID, "bad argument");
   if (c->capturing) return fail(NIF_ERR_STATE, "nif_graph_launch while capturing");
+  if (c->graph_kind[graph_id] > OPT_ADAM)
+    return fail(NIF_ERR_STATE, "nif_graph_launch: the graph holds Lion / AdaBelief steps (nif_graph_launch_opt with that optimizer)");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
@@ -2094,6 +2102,124 @@ extern "C" int nif_graph_launch(nif_ctx* c, int32_t graph_id, const nif_adam* op
 extern "C" int nif_graph_destroy(nif_ctx* c, int32_t graph_id) {
   if (!c || graph_id < 0 || graph_id >= (int32_t)c->graphs.size()) return fail(NIF_ERR_INVALID, "bad argument");
   if (c->graphs[graph_id]) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipGraphExecDestroy(c->graphs[graph_id]); c->graphs[graph_id] = nullptr; }
+  return NIF_OK;
+}
+
+// ---- Lion / AdaBelief (include/nif_hip.h nif_opt_step_dev; reference nif/optimizers/external_optimizers.py:322-735) -----------------
+static int opt_check(const nif_opt* o) {
+  if (o->kind < NIF_OPT_ADAM || o->kind > NIF_OPT_ADABELIEF) return fail(NIF_ERR_INVALID, "nif_opt: kind must be NIF_OPT_ADAM, _LION or _ADABELIEF");
+  if (o->reserved0 || o->reserved[0] || o->reserved[1] || o->reserved[2] || o->reserved[3]) return fail(NIF_ERR_INVALID, "nif_opt: reserved fields must be zero");
+  if (o->flags & ~(NIF_OPT_RECTIFY | NIF_OPT_AMSGRAD)) return fail(NIF_ERR_INVALID, "nif_opt: unknown flag bits");
+  if (o->kind != NIF_OPT_ADABELIEF && (o->flags || o->total_steps || o->sma_threshold != 0.f || o->warmup_proportion != 0.f || o->min_lr != 0.f))
+    return fail(NIF_ERR_INVALID, "nif_opt: flags, sma_threshold, total_steps, warmup_proportion and min_lr are AdaBelief's");
+  if (o->kind == NIF_OPT_ADAM && (o->decay != 0.f || o->weight_decay != 0.f))
+    return fail(NIF_ERR_INVALID, "nif_opt: Adam has no decay / weight_decay on this path (nif_adam)");
+  if (o->total_steps < 0) return fail(NIF_ERR_INVALID, "nif_opt: total_steps < 0");
+  return NIF_OK;
+}
+static OptDev opt_dev_of(const nif_opt* o, long step) {
+  OptDev d;
+  d.kind = o->kind; d.flags = o->flags; d.lr = o->lr; d.beta1 = o->beta1; d.beta2 = o->beta2; d.eps = o->eps; d.wd = o->weight_decay;
+  d.decay = o->decay; d.sma_threshold = o->sma_threshold; d.warmup_proportion = o->warmup_proportion; d.min_lr = o->min_lr;
+  d.total_steps = (long)o->total_steps; d.step = step;
+  return d;
+}
+static bool opt_ams(const nif_opt* o) { return o->kind == NIF_OPT_ADABELIEF && (o->flags & NIF_OPT_AMSGRAD); }
+static int ensure_vhat(nif_ctx* c) {
+  if (c->vhat) return NIF_OK;
+  if (c->capturing) return fail(NIF_ERR_STATE, "AMSGrad's vhat slot does not exist yet: run one eager step or nif_set_opt_slot(2, ...) before the capture");
+  HIPCHK(hipMalloc(&c->vhat, sizeof(float) * (size_t)c->P));
+  HIPCHK(hipMemsetAsync(c->vhat, 0, sizeof(float) * (size_t)c->P, c->st));
+  return NIF_OK;
+}
+extern "C" int nif_opt_scalars(const nif_opt* o, int64_t t, double* out) {
+  if (!o || !out || t < 1) return fail(NIF_ERR_INVALID, "bad argument");
+  const int rc = opt_check(o); if (rc) return rc;
+  const OptScalars s = opt_scalars(opt_dev_of(o, 0), (long)t);
+  out[0] = s.lr; out[1] = s.bc1; out[2] = s.bc2; out[3] = s.r; out[4] = (double)s.div;
+  return NIF_OK;
+}
+// The same place in the step as nif_adam_step_dev and the same three forms: fused with the deferred row reduction (tail_can_defer),
+// inside a capture from device memory, else after the flushed reduction and the regulariser term
+extern "C" int nif_opt_step_dev(nif_ctx* c, const nif_opt* opt) {
+  if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
+  int rc = opt_check(opt); if (rc) return rc;
+  if (opt->kind == NIF_OPT_ADAM) { const nif_adam a = {opt->lr, opt->beta1, opt->beta2, opt->eps}; return nif_adam_step_dev(c, &a); }
+  if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
+  const bool ams = opt_ams(opt);
+  if (c->capturing && c->cap_kind >= 0 && (c->cap_kind != opt->kind || c->cap_ams != ams))
+    return fail(NIF_ERR_STATE, "nif_opt_step_dev: this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
+  HIPCHK(hipSetDevice(c->dev));
+  if (ams) { rc = ensure_vhat(c); if (rc) return rc; }
+  if (c->tail_pending && !c->capturing && tail_can_defer(c)) {      // the step's row reduction and the update in ONE launch
+    c->tail_pending = false;
+    c->step += 1;
+    const OptDev d = opt_dev_of(opt, c->step - 1);
+    launch_reduce_opt(opt->kind, ams, c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m,
+                      c->v, c->vhat, opt_args(d, opt_scalars(d, c->step)), c->st);
+    HIPCHK(hipGetLastError());
+    c->packed = false; c->packed32 = false; c->packed_p32 = false;
+    c->reg_applied = false;
+    return NIF_OK;
+  }
+  TAIL_FLUSH(c)
+  apply_reg(c);
+  if (c->capturing) {      // the scalars from c->opt_dev at replay time (nif_graph_launch_opt refreshes it)
+    launch_opt_dev(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, c->opt_dev, c->st);
+    HIPCHK(hipGetLastError());
+    c->step += 1; c->cap_steps += 1; c->cap_kind = opt->kind; c->cap_ams = ams;
+    c->packed = false; c->packed32 = false; c->packed_p32 = false;
+    c->reg_applied = false;
+    return NIF_OK;
+  }
+  c->step += 1;
+  const OptDev d = opt_dev_of(opt, c->step - 1);
+  { ProfScope p_(c, NIF_PROF_ADAM);
+    launch_opt(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, opt_args(d, opt_scalars(d, c->step)), c->st); }
+  HIPCHK(hipGetLastError());
+  c->packed = false; c->packed32 = false; c->packed_p32 = false;
+  c->reg_applied = false;
+  return NIF_OK;
+}
+extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt* opt) {
+  if (!c || !opt || graph_id < 0 || graph_id >= (int32_t)c->graphs.size() || !c->graphs[graph_id]) return fail(NIF_ERR_INVALID, "bad argument");
+  int rc = opt_check(opt); if (rc) return rc;
+  const int rk = c->graph_kind[graph_id];
+  if (rk >= 0 && (rk != opt->kind || (c->graph_ams[graph_id] != 0) != opt_ams(opt)))
+    return fail(NIF_ERR_INVALID, "nif_graph_launch_opt: the graph was recorded with another optimizer kind / amsgrad flag");
+  if (opt->kind == NIF_OPT_ADAM) { const nif_adam a = {opt->lr, opt->beta1, opt->beta2, opt->eps}; return nif_graph_launch(c, graph_id, &a); }
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_graph_launch_opt while capturing");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
+  *c->opt_host = opt_dev_of(opt, c->step);
+  HIPCHK(hipMemcpyAsync(c->opt_dev, c->opt_host, sizeof(OptDev), hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipGraphLaunch(c->graphs[graph_id], c->st));
+  c->step += c->graph_steps[graph_id];
+  c->packed = false; c->packed32 = false; c->packed_p32 = false; c->reg_applied = false;
+  return NIF_OK;
+}
+extern "C" int nif_get_opt_slot(nif_ctx* c, int32_t slot, float* host, int64_t n) {
+  if (!c || !host || slot < 0 || slot > 2) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat)");
+  if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  float* src = slot == 0 ? c->m : slot == 1 ? c->v : c->vhat;
+  if (!src) { memset(host, 0, sizeof(float) * (size_t)n); return NIF_OK; }
+  HIPCHK(hipMemcpyAsync(host, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+extern "C" int nif_set_opt_slot(nif_ctx* c, int32_t slot, const float* host, int64_t n) {
+  if (!c || !host || slot < 0 || slot > 2) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat)");
+  if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_set_opt_slot while capturing");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  if (slot == 2) { const int rc = ensure_vhat(c); if (rc) return rc; }
+  float* dst = slot == 0 ? c->m : slot == 1 ? c->v : c->vhat;
+  HIPCHK(hipMemcpyAsync(dst, host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
 

@@ -65,6 +65,11 @@ struct nif_ctx {
   // captured training steps (nif_graph_*): hipGraph executables, the steps each one carries, the device-side Adam state
   std::vector<hipGraphExec_t> graphs; std::vector<int> graph_steps; bool capturing = false; int cap_steps = 0; long cap_step0 = 0;
   AdamDev* adam_dev = nullptr; AdamDev* adam_host = nullptr;
+  // Lion / AdaBelief (nif_opt_step_dev): AdaBelief's amsgrad slot (allocated on first use), the device-side state of captured steps, and
+  // the optimizer kind / amsgrad flag each capture recorded (-1: no update step) -- a graph is replayed only with the kind it holds
+  float* vhat = nullptr;
+  OptDev* opt_dev = nullptr; OptDev* opt_host = nullptr;
+  int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
   bool ll_mlp_packed = false;        // last-layer class: the f32 planes of the 32-point MLP kernels are current
   int loss_kind = 0;                 // NIF_LOSS_* (nif_set_loss)
   float* sob_acc = nullptr;          // [grad | loss] summed over the column groups of a Sobolev step with more than three x_index columns

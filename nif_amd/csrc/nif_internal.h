@@ -266,6 +266,56 @@ struct AdamDev { float lr, beta1, beta2, eps; long step; };      // device-resid
 void launch_adam_dev(float* theta, const float* g, float* m, float* v, long P, AdamDev* ad, hipStream_t st);
 void launch_adam(float* theta, const float* g, float* m, float* v, long P, float lr_t, float b1, float b2,
                  float eps, hipStream_t st);
+// Lion / AdaBelief (k_opt.hip, include/nif_hip.h nif_opt_step_dev).  OptDev: the hyper-parameters of a nif_opt and the iteration count,
+// in device memory for a captured graph of steps (as AdamDev); the host forms the same scalars from the same struct for eager steps.
+enum { OPT_ADAM = 0, OPT_LION = 1, OPT_ADABELIEF = 2 };
+enum { OPT_RECTIFY = 1, OPT_AMSGRAD = 2 };
+struct OptDev { int kind, flags; float lr, beta1, beta2, eps, wd, decay, sma_threshold, warmup_proportion, min_lr; long total_steps; long step; };
+struct OptScalars { double lr, bc1, bc2, r; int div; };
+// the per-step scalars of iteration t (Keras' iterations + 1) in fp64: lr_d = lr / (1 + decay (t - 1)) (Keras' _decayed_lr); for AdaBelief
+// the warm-up ramp / linear decay to min_lr over total_steps, the bias corrections 1 - b^t, the rectification factor r_t and whether
+// this step divides by (v_hat + eps) (div = 0: the plain momentum step below sma_threshold)
+__host__ __device__ inline OptScalars opt_scalars(const OptDev& o, long t_) {
+  OptScalars s;
+  const double t = (double)t_;
+  double lr = (double)o.lr;
+  if (o.decay != 0.f) lr = lr / (1.0 + (double)o.decay * (t - 1.0));
+  const double b2 = (double)o.beta2, b2t = pow(b2, t);
+  s.bc1 = 1.0 - pow((double)o.beta1, t);
+  s.bc2 = 1.0 - b2t;
+  s.r = 1.0; s.div = 1;
+  if (o.kind == OPT_ADABELIEF) {
+    if (o.total_steps > 0) {
+      const double ts = (double)o.total_steps, w = ts * (double)o.warmup_proportion;
+      const double ds = fmax(ts - w, 1.0), rate = ((double)o.min_lr - lr) / ds;
+      lr = t <= w ? lr * (t / w) : lr + rate * fmin(t - w, ds);
+    }
+    if (o.flags & OPT_RECTIFY) {
+      const double sma_inf = 2.0 / (1.0 - b2) - 1.0;
+      const double sma_t = sma_inf - 2.0 * t * b2t / (1.0 - b2t);
+      if (sma_t >= (double)o.sma_threshold)
+        s.r = sqrt((sma_t - 4.0) / (sma_inf - 4.0) * (sma_t - 2.0) / (sma_inf - 2.0) * sma_inf / sma_t);
+      else
+        s.div = 0;
+    }
+  }
+  s.lr = lr;
+  return s;
+}
+// what one update kernel receives (floats; the fp64 scalars rounded once)
+struct OptArgs { float lr, b1, b2, eps, wd, bc1, bc2, r; int div; };
+__host__ __device__ inline OptArgs opt_args(const OptDev& o, const OptScalars& s) {
+  OptArgs a;
+  a.lr = (float)s.lr; a.b1 = o.beta1; a.b2 = o.beta2; a.eps = o.eps; a.wd = o.wd;
+  a.bc1 = (float)s.bc1; a.bc2 = (float)s.bc2; a.r = (float)s.r; a.div = s.div;
+  return a;
+}
+void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, const OptArgs& a,
+                hipStream_t st);
+void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g,
+                       long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st);
+void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
+                    hipStream_t st);
 void launch_latent_to_w(const float* theta, long off_Wh, long off_bh, int r, long po, const float* lr, long B,
                         float* w, hipStream_t st);
 void launch_given_w(const float* x, const float* w, float* u, long B, int si, int so, int n, int nh, long po,

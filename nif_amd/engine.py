@@ -359,6 +359,23 @@ class Engine(object):
     def adam_step_dev(self, adam):
         check(self.lib.nif_adam_step_dev(self.ctx, C.byref(adam)))
 
+    # Lion / AdaBelief (include/nif_hip.h nif_opt_*): `opt` is a _lib.nif_opt (optimizers.Lion / AdaBeliefOptimizer .as_opt())
+    def opt_step_dev(self, opt):
+        check(self.lib.nif_opt_step_dev(self.ctx, C.byref(opt)))
+
+    def graph_launch_opt(self, gid, opt):
+        check(self.lib.nif_graph_launch_opt(self.ctx, int(gid), C.byref(opt)))
+
+    def get_opt_slot(self, slot):
+        """slot 0 m, 1 v, 2 vhat (zeros before AMSGrad first used it)"""
+        out = np.empty((self.n_params,), dtype=np.float32)
+        check(self.lib.nif_get_opt_slot(self.ctx, int(slot), ptr(out), out.size))
+        return out
+
+    def set_opt_slot(self, slot, values):
+        values = _f32(values)
+        check(self.lib.nif_set_opt_slot(self.ctx, int(slot), ptr(values), values.size))
+
     # captured training steps (include/nif_hip.h nif_graph_*)
     def graph_begin(self):
         check(self.lib.nif_graph_begin(self.ctx))

@@ -6,6 +6,7 @@ import contextlib
 import json
 import os
 import time
+import warnings
 
 import numpy as np
 
@@ -135,22 +136,52 @@ class Model(object):
 
     def save_weights(self, filepath):
         """Flat parameters in Keras variable order + Adam slots, as .npz (the reference's TF-checkpoint
-        format, README.md:179-195, is a TensorFlow artefact and out of scope)."""
+        format, README.md:179-195, is a TensorFlow artefact and out of scope).  Compiled with Lion / AdaBelief: the
+        weights + opt_kind, opt_step and that optimizer's slots (opt_m; opt_v; opt_vhat with amsgrad) instead."""
         ws = self.get_weights()
-        m, v, step = self._engine.get_opt_state()
         arrs = {"w%03d" % i: w for i, w in enumerate(ws)}
-        np.savez(filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz",
-                 names=np.array([nm for nm, _ in self._engine.shapes]), adam_m=m, adam_v=v,
-                 adam_step=np.int64(step), **arrs)
+        path = filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz"
+        names = np.array([nm for nm, _ in self._engine.shapes])
+        opt = self.optimizer
+        if opt is not None and not isinstance(opt, Adam):
+            e = self._engine
+            m, v, step = e.get_opt_state()
+            slots = {"opt_m": m}
+            if opt.kind == _lib.OPT_ADABELIEF:
+                slots["opt_v"] = v
+                if opt.amsgrad:
+                    slots["opt_vhat"] = e.get_opt_slot(2)
+            np.savez(path, names=names, opt_kind=np.int32(opt.kind), opt_step=np.int64(step), **slots, **arrs)
+            return
+        m, v, step = self._engine.get_opt_state()
+        np.savez(path, names=names, adam_m=m, adam_v=v, adam_step=np.int64(step), **arrs)
 
     def load_weights(self, filepath):
         f = filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz"
         d = np.load(f)
         n = len(self._engine.shapes)
         self.set_weights([d["w%03d" % i] for i in range(n)])
+        opt = self.optimizer
         if "adam_m" in d:
-            self._engine.set_opt_state(d["adam_m"], d["adam_v"], int(d["adam_step"]))
-            self._fresh_slots = False
+            if opt is None or isinstance(opt, Adam):
+                self._engine.set_opt_state(d["adam_m"], d["adam_v"], int(d["adam_step"]))
+                self._fresh_slots = False
+            else:
+                warnings.warn("load_weights: the file holds Adam slots, the model is compiled with %s: weights loaded, "
+                              "optimizer state not restored" % type(opt).__name__)
+        elif "opt_kind" in d:
+            kind, ams = int(d["opt_kind"]), "opt_vhat" in d
+            if opt is not None and not isinstance(opt, Adam) and opt.kind == kind and bool(opt.amsgrad) == ams:
+                e = self._engine
+                m = d["opt_m"]
+                e.set_opt_state(m, d["opt_v"] if "opt_v" in d else np.zeros_like(m), int(d["opt_step"]))
+                if ams:
+                    e.set_opt_slot(2, d["opt_vhat"])
+                self._fresh_slots = False
+            else:
+                warnings.warn("load_weights: the file holds the slots of another optimizer (kind %d%s) than the compiled one (%s): "
+                              "weights loaded, optimizer state not restored"
+                              % (kind, ", amsgrad" if ams else "", type(opt).__name__ if opt is not None else "none"))
 
     # ---- inference -------------------------------------------------------------------------------
     def _run(self, x):
@@ -346,9 +377,12 @@ class Model(object):
             raise NotImplementedError("compile(metrics=...): in-memory arrays on one GPU")
         self._push_losses(e, 1)                   # (raises here, not at first engine access, when the shape has no kernel for it)
         self.stop_training = False
+        is_adam = isinstance(self.optimizer, Adam)
         if getattr(self, "_fresh_slots", False):
             z = np.zeros((e.n_params,), dtype=np.float32)
             e.set_opt_state(z, z, 0)
+            if not is_adam and self.optimizer.amsgrad:
+                e.set_opt_slot(2, z)
             self._fresh_slots = False
         ncol = s.pi_dim + s.si_dim
         shard = x if isinstance(x, ShardBatches) else None
@@ -468,7 +502,8 @@ class Model(object):
                             dt.upload(t[perm])
                         if has_sw:
                             src_sw.upload(sw[perm])
-                adam = self.optimizer.as_struct()
+                adam = self.optimizer.as_struct() if is_adam else self.optimizer.as_opt()    # (Lion / AdaBelief: a nif_opt)
+                step_dev = e.adam_step_dev if is_adam else e.opt_step_dev
                 self._push_losses(e, 1)           # (a callback of the previous epoch may have evaluated another model on the shared engine)
                 e.metric_read(reset=True)
 
@@ -490,7 +525,7 @@ class Model(object):
                             e.zero_grad()
                         if world > 1:
                             comm.all_reduce_grad(e)
-                        e.adam_step_dev(adam)
+                        step_dev(adam)
                         e.metric_accumulate(bg)     # Keras' loss metric: sample-weighted mean over the batches,
                 if steps_per_epoch is not None:
                     # Keras with array inputs and steps_per_epoch (TensorLikeDataAdapter: ONE iterator over `epochs` successive passes,
@@ -538,7 +573,10 @@ class Model(object):
                 if steps_per_epoch is not None:
                     pass
                 elif use_graph and graph_id is not None:
-                    e.graph_launch(graph_id, adam)
+                    if is_adam:
+                        e.graph_launch(graph_id, adam)
+                    else:
+                        e.graph_launch_opt(graph_id, adam)
                 else:
                     run_batches()
                 tot, cnt = e.metric_read(reset=True)   # accumulated on the device: one host sync per epoch

@@ -1,5 +1,10 @@
 """Optimizers accepted by Model.compile.  The hot path uses stock Keras-2.11 Adam (README.md:33;
-SURVEY a-11); the update itself is the k_adam HIP kernel."""
+SURVEY a-11); the update itself is the k_adam HIP kernel.  The reference's Lion and AdaBeliefOptimizer
+(nif/optimizers/__init__.py) run on the k_opt.hip kernels."""
+import numbers
+
+import numpy as np
+
 from . import _lib
 
 
@@ -23,8 +28,111 @@ class Adam(object):
         return _lib.nif_adam(self.learning_rate, self.beta_1, self.beta_2, self.epsilon)
 
 
+def _number(cls, what, v):
+    """a plain number (learning-rate / weight-decay schedule objects are not built)"""
+    if isinstance(v, bool) or not isinstance(v, (numbers.Real, np.floating, np.integer)):
+        raise NotImplementedError("%s(%s=%r): only numbers are built (no schedule objects)" % (cls, what, v))
+    return float(v)
+
+
+def _legacy_kwargs(cls, kwargs, learning_rate):
+    """the keyword arguments of Keras' legacy optimizer base both reference classes accept: `lr` (wins over learning_rate, as in
+    the reference's kwargs.get("lr", learning_rate)) and `decay`; clipping and anything else is not built"""
+    kwargs = dict(kwargs)
+    learning_rate = kwargs.pop("lr", learning_rate)
+    decay = _number(cls, "decay", kwargs.pop("decay", 0.0))
+    if decay < 0.0:
+        raise ValueError("decay cannot be less than 0. Received: decay=%r." % (decay,))
+    if kwargs:
+        raise NotImplementedError("%s(%s): not built (clipping and the other keyword arguments of Keras' optimizer base are "
+                                  "out of scope)" % (cls, ", ".join(sorted(kwargs))))
+    return _number(cls, "learning_rate", learning_rate), decay
+
+
+class _LrProperty(object):
+    # Keras exposes optimizer.lr / optimizer.learning_rate; LearningRateScheduler sets it
+    @property
+    def lr(self):
+        return self.learning_rate
+
+    @lr.setter
+    def lr(self, v):
+        self.learning_rate = float(v)
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+class Lion(_LrProperty):
+    """nif.optimizers.Lion (reference nif/optimizers/external_optimizers.py:631-735), updated by the k_lion kernels:
+    theta -= lr_d (sign(b1 m + (1-b1) g) + wd theta), then m = b2 m + (1-b2) g; lr_d = lr / (1 + decay (t - 1))."""
+    kind = _lib.OPT_LION
+    amsgrad = False
+
+    def __init__(self, learning_rate=1e-4, beta_1=0.9, beta_2=0.99, wd=0, name="lion", print_change_log=True, **kwargs):
+        self.learning_rate, self.decay = _legacy_kwargs("Lion", kwargs, learning_rate)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.wd = _number("Lion", "wd", wd)
+        self.name = name
+
+    def get_config(self):
+        return {"name": self.name, "learning_rate": self.learning_rate, "decay": self.decay, "beta_1": self.beta_1,
+                "beta_2": self.beta_2, "wd": self.wd}
+
+    def as_opt(self):
+        o = _lib.nif_opt()
+        o.kind = self.kind
+        o.lr, o.beta1, o.beta2, o.weight_decay, o.decay = self.learning_rate, self.beta_1, self.beta_2, self.wd, self.decay
+        return o
+
+
+class AdaBeliefOptimizer(_LrProperty):
+    """nif.optimizers.AdaBeliefOptimizer (reference nif/optimizers/external_optimizers.py:322-628), updated by the k_adabelief kernels:
+    Adam on the belief (g - m)^2, optional rectification (RAdam) behind sma_threshold, AMSGrad, weight_decay * theta added to the
+    step, and a warm-up / linear decay of the learning rate over total_steps.  epsilon 0 becomes Keras' 1e-7."""
+    kind = _lib.OPT_ADABELIEF
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-14, weight_decay=0.0, rectify=True, amsgrad=False,
+                 sma_threshold=5.0, total_steps=0, warmup_proportion=0.1, min_lr=0.0, name="AdaBeliefOptimizer",
+                 print_change_log=True, **kwargs):
+        self.learning_rate, self.decay = _legacy_kwargs("AdaBeliefOptimizer", kwargs, learning_rate)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon = float(epsilon or 1e-7)
+        self.weight_decay = _number("AdaBeliefOptimizer", "weight_decay", weight_decay)
+        self.rectify, self.amsgrad = bool(rectify), bool(amsgrad)
+        self.sma_threshold = float(sma_threshold)
+        self.total_steps = int(total_steps)
+        self.warmup_proportion, self.min_lr = float(warmup_proportion), float(min_lr)
+        self.name = name
+
+    def get_config(self):
+        return {"name": self.name, "learning_rate": self.learning_rate, "beta_1": self.beta_1, "beta_2": self.beta_2,
+                "decay": self.decay, "weight_decay": self.weight_decay, "sma_threshold": self.sma_threshold,
+                "epsilon": self.epsilon, "amsgrad": self.amsgrad, "rectify": self.rectify, "total_steps": self.total_steps,
+                "warmup_proportion": self.warmup_proportion, "min_lr": self.min_lr}
+
+    def as_opt(self):
+        o = _lib.nif_opt()
+        o.kind = self.kind
+        o.flags = (_lib.OPT_RECTIFY if self.rectify else 0) | (_lib.OPT_AMSGRAD if self.amsgrad else 0)
+        o.lr, o.beta1, o.beta2, o.eps = self.learning_rate, self.beta_1, self.beta_2, self.epsilon
+        o.weight_decay, o.decay, o.sma_threshold = self.weight_decay, self.decay, self.sma_threshold
+        o.warmup_proportion, o.min_lr, o.total_steps = self.warmup_proportion, self.min_lr, self.total_steps
+        return o
+
+
+class L4Adam(object):
+    """nif.optimizers.L4Adam: not built -- the reference's own class cannot run (its apply step starts from new_var = None,
+    external_optimizers.py:148)."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("L4Adam: the reference's implementation does not run (external_optimizers.py:148 new_var=None); "
+                                  "use Adam, Lion or AdaBeliefOptimizer")
+
+
 def get(opt):
-    if isinstance(opt, Adam):
+    if isinstance(opt, (Adam, Lion, AdaBeliefOptimizer)):
         return opt
     if isinstance(opt, str):
         if opt.lower() == "adam":
