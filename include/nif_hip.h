@@ -272,6 +272,21 @@ int nif_set_opt_slot(nif_ctx* ctx, int32_t slot, const float* host, int64_t n);
  * out[0] learning rate, out[1] 1 - b1^t, out[2] 1 - b2^t, out[3] r_t, out[4] 1 when the update divides by (v_hat + eps), else 0
  * (AdaBelief's momentum branch); Lion fills out[0] only */
 int nif_opt_scalars(const nif_opt* opt, int64_t t, double* out5);
+/* Low-magnitude pruning (tfmot.sparsity.keras 0.7.3 as nif_amd/sparsity.py restates it).  A segment is one pruned tensor: `size` floats
+ * of the flat parameter vector from float `offset`; segments are given in increasing, non-overlapping order.
+ *   nif_prune_config   registers n segments (n = 0: pruning off, its buffers freed); masks start at all ones, thresholds at 0
+ *   nif_prune_update   per segment the exact k[s]-th largest |w| (1 <= k[s] <= size) of the current weights becomes its threshold, and
+ *                      mask = (|w| >= threshold): ties keep more than k entries.  On the device (k_prune.hip, radix select over the
+ *                      magnitude bits with integer counts): deterministic, only the k values travel
+ *   nif_prune_apply    w = w * mask on every segment
+ *   nif_get/set_prune_state  the masks as float32 0 / 1, segment after segment (n_mask = the sum of the sizes), and the thresholds
+ * Every call runs the deferred row reduction / loss-metric accumulation first, as its neighbours do, and is refused inside a graph
+ * capture (NIF_ERR_STATE). */
+int nif_prune_config(nif_ctx* ctx, int32_t n, const int64_t* offsets, const int64_t* sizes);
+int nif_prune_update(nif_ctx* ctx, const int64_t* k_per_segment);
+int nif_prune_apply(nif_ctx* ctx);
+int nif_get_prune_state(nif_ctx* ctx, float* masks, int64_t n_mask, float* thresholds, int32_t n_seg);
+int nif_set_prune_state(nif_ctx* ctx, const float* masks, int64_t n_mask, const float* thresholds, int32_t n_seg);
 /* zero [grad | loss]: what a rank contributes to the step's all-reduce when its shard has no rows left (uneven shards of
  * Model.fit under data parallelism); the weight-regulariser term is still added by the following nif_adam_step_dev */
 int nif_zero_grad(nif_ctx* ctx);

@@ -127,6 +127,11 @@ SIGNATURES = {
     "nif_get_opt_slot": (C.c_int, [_CTX, C.c_int32, _VP, C.c_int64]),
     "nif_set_opt_slot": (C.c_int, [_CTX, C.c_int32, _VP, C.c_int64]),
     "nif_opt_scalars": (C.c_int, [C.POINTER(nif_opt), C.c_int64, C.POINTER(C.c_double)]),
+    "nif_prune_config": (C.c_int, [_CTX, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "nif_prune_update": (C.c_int, [_CTX, C.POINTER(C.c_int64)]),
+    "nif_prune_apply": (C.c_int, [_CTX]),
+    "nif_get_prune_state": (C.c_int, [_CTX, _VP, C.c_int64, _VP, C.c_int32]),
+    "nif_set_prune_state": (C.c_int, [_CTX, _VP, C.c_int64, _VP, C.c_int32]),
     "nif_zero_grad": (C.c_int, [_CTX]),
     "nif_reserve": (C.c_int, [_CTX, C.c_int64, C.c_int32]),
     "nif_device_pci_bus_id": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32]),

@@ -207,7 +207,7 @@ extern "C" int nif_destroy(nif_ctx* c) {
   for (hipGraphExec_t ex : c->graphs) if (ex) (void)hipGraphExecDestroy(ex);
   if (c->adam_host) (void)hipHostFree(c->adam_host);
   if (c->opt_host) (void)hipHostFree(c->opt_host);
-  void* ptrs[] = {c->adam_dev, c->opt_dev, c->vhat, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
+  void* ptrs[] = {c->adam_dev, c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
                   c->DU, c->ZL, c->partial, c->loss_partial, c->dring, c->metric, c->tl, c->lWF, c->lWB, c->sWF4, c->sWB4, c->sWF4x, c->sWB4x, c->sWscale, c->sWF4h, c->sWB4h, c->ll_slots, c->ll_wpf, c->ll_wpb, c->stash_l, c->PHI, c->DPHI, c->DA, c->DZL, c->d_a, c->d_b, c->d_c, c->d_d};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->st) hipStreamDestroy(c->st);
@@ -2219,6 +2219,108 @@ extern "C" int nif_set_opt_slot(nif_ctx* c, int32_t slot, const float* host, int
   if (slot == 2) { const int rc = ensure_vhat(c); if (rc) return rc; }
   float* dst = slot == 0 ? c->m : slot == 1 ? c->v : c->vhat;
   HIPCHK(hipMemcpyAsync(dst, host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+
+// ---- low-magnitude pruning (include/nif_hip.h nif_prune_*; k_prune.hip) -----------------------------------------------------------
+static void prune_free(nif_ctx* c) {
+  void* ptrs[] = {c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  c->prune_segs_dev = nullptr; c->prune_mask = nullptr; c->prune_thr = nullptr; c->prune_hist = nullptr; c->prune_sel = nullptr;
+  c->prune_segs.clear(); c->prune_nblk = 0; c->prune_lo = 0; c->prune_hi = 0;
+}
+// what every nif_prune_* call does first: no capture, the deferred row reduction and loss-metric accumulation run now
+static int prune_enter(nif_ctx* c, bool need_config) {
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_prune_*: not inside a graph capture");
+  if (need_config && c->prune_segs.empty()) return fail(NIF_ERR_STATE, "pruning is not configured (nif_prune_config)");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  return metric_flush(c);
+}
+extern "C" int nif_prune_config(nif_ctx* c, int32_t n, const int64_t* offsets, const int64_t* sizes) {
+  if (!c || n < 0 || (n > 0 && (!offsets || !sizes))) return fail(NIF_ERR_INVALID, "bad argument");
+  std::vector<PruneSeg> segs((size_t)n);
+  long nblk = 0, end = 0;
+  for (int i = 0; i < n; ++i) {
+    const long off = (long)offsets[i], sz = (long)sizes[i];
+    if (off < end || sz < 1 || sz > 0x7fffffffL || off + sz > c->P)
+      return fail(NIF_ERR_INVALID, "nif_prune_config: segments must be non-empty, below 2^31 floats, inside theta, increasing and disjoint");
+    segs[i].off = off; segs[i].size = sz; segs[i].k = sz; segs[i].blk0 = nblk;
+    nblk += (sz + PRUNE_CHUNK - 1) / PRUNE_CHUNK;
+    end = off + sz;
+  }
+  int rc = prune_enter(c, false); if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(c->st));      // (queued work may still read the buffers freed here)
+  prune_free(c);
+  if (n == 0) return NIF_OK;
+  HIPCHK(hipMalloc(&c->prune_segs_dev, sizeof(PruneSeg) * (size_t)n));
+  HIPCHK(hipMalloc(&c->prune_mask, (size_t)c->P + 16));
+  HIPCHK(hipMalloc(&c->prune_thr, sizeof(float) * (size_t)n));
+  HIPCHK(hipMalloc(&c->prune_hist, sizeof(unsigned) * PRUNE_BINS * (size_t)n));
+  HIPCHK(hipMalloc(&c->prune_sel, sizeof(PruneSel) * (size_t)n));
+  HIPCHK(hipMemcpy(c->prune_segs_dev, segs.data(), sizeof(PruneSeg) * (size_t)n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(c->prune_mask, 1, (size_t)c->P + 16, c->st));
+  HIPCHK(hipMemsetAsync(c->prune_thr, 0, sizeof(float) * (size_t)n, c->st));
+  HIPCHK(hipMemsetAsync(c->prune_hist, 0, sizeof(unsigned) * PRUNE_BINS * (size_t)n, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->prune_segs = segs; c->prune_nblk = nblk; c->prune_lo = segs.front().off; c->prune_hi = end;
+  return NIF_OK;
+}
+extern "C" int nif_prune_update(nif_ctx* c, const int64_t* k) {
+  if (!c || !k) return fail(NIF_ERR_INVALID, "null");
+  if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
+  int rc = prune_enter(c, true); if (rc) return rc;
+  const int n = (int)c->prune_segs.size();
+  for (int i = 0; i < n; ++i)
+    if (k[i] < 1 || k[i] > c->prune_segs[i].size) return fail(NIF_ERR_INVALID, "nif_prune_update: 1 <= k <= the segment's size");
+  HIPCHK(hipStreamSynchronize(c->st));      // (the previous update's copy of the host table is through before the table changes)
+  for (int i = 0; i < n; ++i) c->prune_segs[i].k = (long)k[i];
+  HIPCHK(hipMemcpyAsync(c->prune_segs_dev, c->prune_segs.data(), sizeof(PruneSeg) * (size_t)n, hipMemcpyHostToDevice, c->st));
+  launch_prune_update(c->theta, c->prune_segs_dev, n, c->prune_nblk, c->prune_hist, c->prune_sel, c->prune_thr, c->prune_mask, c->st);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_prune_apply(nif_ctx* c) {
+  if (!c) return fail(NIF_ERR_INVALID, "null");
+  if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
+  int rc = prune_enter(c, true); if (rc) return rc;
+  launch_prune_apply(c->theta, c->prune_mask, c->prune_lo, c->prune_hi, c->P, c->st);
+  HIPCHK(hipGetLastError());
+  c->packed = false; c->packed32 = false; c->packed_p32 = false;      // (theta changed: no stale ShapeNet / ParameterNet planes)
+  return NIF_OK;
+}
+static long prune_total(const nif_ctx* c) {
+  long t = 0;
+  for (const PruneSeg& s : c->prune_segs) t += s.size;
+  return t;
+}
+extern "C" int nif_get_prune_state(nif_ctx* c, float* masks, int64_t n_mask, float* thr, int32_t n_seg) {
+  if (!c || !masks || !thr) return fail(NIF_ERR_INVALID, "null");
+  int rc = prune_enter(c, true); if (rc) return rc;
+  if (n_mask != prune_total(c) || n_seg != (int32_t)c->prune_segs.size()) return fail(NIF_ERR_INVALID, "nif_get_prune_state: size mismatch");
+  std::vector<unsigned char> h((size_t)c->P);
+  HIPCHK(hipMemcpyAsync(h.data(), c->prune_mask, (size_t)c->P, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(thr, c->prune_thr, sizeof(float) * (size_t)n_seg, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  long o = 0;
+  for (const PruneSeg& s : c->prune_segs)
+    for (long i = 0; i < s.size; ++i) masks[o++] = h[(size_t)(s.off + i)] ? 1.f : 0.f;
+  return NIF_OK;
+}
+extern "C" int nif_set_prune_state(nif_ctx* c, const float* masks, int64_t n_mask, const float* thr, int32_t n_seg) {
+  if (!c || !masks || !thr) return fail(NIF_ERR_INVALID, "null");
+  int rc = prune_enter(c, true); if (rc) return rc;
+  if (n_mask != prune_total(c) || n_seg != (int32_t)c->prune_segs.size()) return fail(NIF_ERR_INVALID, "nif_set_prune_state: size mismatch");
+  std::vector<unsigned char> h((size_t)c->P + 16, 1);
+  long o = 0;
+  for (const PruneSeg& s : c->prune_segs)
+    for (long i = 0; i < s.size; ++i, ++o) {
+      if (masks[o] != 0.f && masks[o] != 1.f) return fail(NIF_ERR_INVALID, "nif_set_prune_state: mask values are 0 or 1");
+      h[(size_t)(s.off + i)] = masks[o] != 0.f ? 1 : 0;
+    }
+  HIPCHK(hipMemcpyAsync(c->prune_mask, h.data(), h.size(), hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(c->prune_thr, thr, sizeof(float) * (size_t)n_seg, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }

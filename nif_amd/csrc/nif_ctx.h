@@ -70,6 +70,11 @@ struct nif_ctx {
   float* vhat = nullptr;
   OptDev* opt_dev = nullptr; OptDev* opt_host = nullptr;
   int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
+  // magnitude pruning (nif_prune_*): the segment table (host copy: the k of the last update), its span [prune_lo, prune_hi), a byte mask
+  // over the whole of theta (1 outside the segments), the thresholds and the select's histograms / per-segment state
+  std::vector<PruneSeg> prune_segs; long prune_nblk = 0, prune_lo = 0, prune_hi = 0;
+  PruneSeg* prune_segs_dev = nullptr; unsigned char* prune_mask = nullptr; float* prune_thr = nullptr;
+  unsigned* prune_hist = nullptr; PruneSel* prune_sel = nullptr;
   bool ll_mlp_packed = false;        // last-layer class: the f32 planes of the 32-point MLP kernels are current
   int loss_kind = 0;                 // NIF_LOSS_* (nif_set_loss)
   float* sob_acc = nullptr;          // [grad | loss] summed over the column groups of a Sobolev step with more than three x_index columns

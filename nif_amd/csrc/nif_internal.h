@@ -316,6 +316,18 @@ void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, i
                        long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st);
 void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
                     hipStream_t st);
+// magnitude pruning (k_prune.hip, nif_prune_*): one segment = one pruned tensor, `size` floats of theta from `off`; its histogram /
+// mask-build blocks are [blk0, blk0 + ceil(size / PRUNE_CHUNK)) of a flattened grid.  k: keep the k largest |w| (1 <= k <= size)
+#define PRUNE_CHUNK 4096         // entries per histogram / mask block (256 threads x 16)
+#define PRUNE_BINS 2048          // histogram bins per segment (the widest digit: 11 bits)
+struct PruneSeg { long off, size, k, blk0; };
+struct PruneSel { unsigned prefix, krem; };     // the key prefix selected so far and the rank still to find below it
+// exact k-th largest |w| of every segment into thr[seg] (three digit passes, 11/10/10 bits of the 31-bit magnitude key), then
+// mask[off + i] = |w[off + i]| >= thr[seg] over every segment.  hist: nseg * PRUNE_BINS zeros on entry, zeros again on return
+void launch_prune_update(const float* theta, const PruneSeg* segs, int nseg, long nblk, unsigned* hist, PruneSel* sel, float* thr,
+                         unsigned char* mask, hipStream_t st);
+// theta[i] = mask[i] ? theta[i] : theta[i] * 0 over [lo, hi) (mask is 1 outside the segments)
+void launch_prune_apply(float* theta, const unsigned char* mask, long lo, long hi, long P, hipStream_t st);
 void launch_latent_to_w(const float* theta, long off_Wh, long off_bh, int r, long po, const float* lr, long B,
                         float* w, hipStream_t st);
 void launch_given_w(const float* x, const float* w, float* u, long B, int si, int so, int n, int nh, long po,

@@ -376,6 +376,39 @@ class Engine(object):
         values = _f32(values)
         check(self.lib.nif_set_opt_slot(self.ctx, int(slot), ptr(values), values.size))
 
+    # low-magnitude pruning (include/nif_hip.h nif_prune_*; nif_amd.sparsity drives these)
+    def prune_config(self, offsets, sizes):
+        """register the pruned tensors as segments of theta (float offsets, sizes); empty lists: pruning off"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        sz = np.ascontiguousarray(sizes, dtype=np.int64)
+        assert off.shape == sz.shape
+        i64 = C.POINTER(C.c_int64)
+        check(self.lib.nif_prune_config(self.ctx, int(off.size), off.ctypes.data_as(i64), sz.ctypes.data_as(i64)))
+        self._prune_sizes = [int(v) for v in sz]
+
+    def prune_update(self, ks):
+        """masks of the current weights: per segment keep the k largest |w| (ties keep more)"""
+        k = np.ascontiguousarray(ks, dtype=np.int64)
+        if k.size != len(getattr(self, "_prune_sizes", [])):
+            raise ValueError("prune_update: one k per configured segment")
+        check(self.lib.nif_prune_update(self.ctx, k.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    def prune_apply(self):
+        check(self.lib.nif_prune_apply(self.ctx))
+
+    def get_prune_state(self):
+        """(list of float32 0 / 1 masks, one per segment, float32 thresholds)"""
+        sizes = getattr(self, "_prune_sizes", [])
+        masks = np.empty((sum(sizes),), dtype=np.float32)
+        thr = np.empty((len(sizes),), dtype=np.float32)
+        check(self.lib.nif_get_prune_state(self.ctx, ptr(masks), masks.size, ptr(thr), thr.size))
+        return np.split(masks, np.cumsum(sizes)[:-1]), thr
+
+    def set_prune_state(self, masks, thresholds):
+        flat = np.concatenate([_f32(mk).ravel() for mk in masks]) if len(masks) else np.zeros((0,), dtype=np.float32)
+        thr = _f32(thresholds)
+        check(self.lib.nif_set_prune_state(self.ctx, ptr(flat), flat.size, ptr(thr), thr.size))
+
     # captured training steps (include/nif_hip.h nif_graph_*)
     def graph_begin(self):
         check(self.lib.nif_graph_begin(self.ctx))

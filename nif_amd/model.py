@@ -151,10 +151,17 @@ class Model(object):
                 slots["opt_v"] = v
                 if opt.amsgrad:
                     slots["opt_vhat"] = e.get_opt_slot(2)
-            np.savez(path, names=names, opt_kind=np.int32(opt.kind), opt_step=np.int64(step), **slots, **arrs)
+            np.savez(path, names=names, opt_kind=np.int32(opt.kind), opt_step=np.int64(step), **slots, **arrs, **self._extra_arrays())
             return
         m, v, step = self._engine.get_opt_state()
-        np.savez(path, names=names, adam_m=m, adam_v=v, adam_step=np.int64(step), **arrs)
+        np.savez(path, names=names, adam_m=m, adam_v=v, adam_step=np.int64(step), **arrs, **self._extra_arrays())
+
+    def _extra_arrays(self):
+        """hook: arrays a wrapper adds to save_weights' file (sparsity.PrunedModel: masks, thresholds, step)"""
+        return {}
+
+    def _load_extra(self, d):
+        """hook: what load_weights restores beyond the weights and the optimizer slots"""
 
     def load_weights(self, filepath):
         f = filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz"
@@ -182,6 +189,7 @@ class Model(object):
                 warnings.warn("load_weights: the file holds the slots of another optimizer (kind %d%s) than the compiled one (%s): "
                               "weights loaded, optimizer state not restored"
                               % (kind, ", amsgrad" if ams else "", type(opt).__name__ if opt is not None else "none"))
+        self._load_extra(d)
 
     # ---- inference -------------------------------------------------------------------------------
     def _run(self, x):
@@ -337,6 +345,11 @@ class Model(object):
         """sample weights as the engine sees them (hook of the two-output model: an overall loss weight rides on them)"""
         return sw
 
+    def _batch_hook(self, e, callbacks):
+        """hook: None, or what fit() runs at the start of every batch, before anything else the batch does (sparsity.PrunedModel:
+        the pruning step, the mask update on a pruning turn, the masks applied); called once per fit after on_train_begin"""
+        return None
+
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, shuffle=True,
             sample_weight=None, initial_epoch=0, validation_data=None, validation_split=0.0, steps_per_epoch=None, **kwargs):
         """Keras Model.fit semantics for in-memory arrays (or one file of a shard dataset, nif_amd.data): per epoch
@@ -461,9 +474,11 @@ class Model(object):
             # shard is a batch shorter (or empty) join the collectives of the steps they lack with a zero gradient
             sizes, gsizes = dist.plan_steps(N, bs, comm, e)
             e.reserve(max(1, max(sizes, default=0)), self._n_tangents())
-            use_graph = (self._graph_epochs and world == 1 and shard is None and not self._po_l1 and not kinds and len(sizes) >= 4
-                         and max(sizes) <= self._GRAPH_MAX_BATCH and hasattr(e, "graph_begin") and epochs - initial_epoch >= 2)
             graph_id = None
+            batch_hook = self._batch_hook(e, callbacks)
+            use_graph = (self._graph_epochs and world == 1 and shard is None and not self._po_l1 and not kinds and len(sizes) >= 4
+                         and batch_hook is None
+                         and max(sizes) <= self._GRAPH_MAX_BATCH and hasattr(e, "graph_begin") and epochs - initial_epoch >= 2)
             stream = [-1, 0]          # steps_per_epoch: (pass, next batch of the pass) of the one iterator over `epochs` passes
             cur_perm = [None]         # the permutation of the pass the resident table holds (a pass may span epochs under steps_per_epoch:
                                       # the metric forward of a batch reads the host rows through it -- ADVICE r4)
@@ -511,6 +526,8 @@ class Model(object):
                     for ib in range(lo, len(sizes) if hi is None else hi):
                         b, bg = sizes[ib], gsizes[ib]
                         b0 = ib * bs
+                        if batch_hook is not None:
+                            batch_hook()
                         if self._po_l1:
                             self._push_losses(e, bg)
                         if kinds and b > 0:      # compile(metrics=...): the batch's predictions with the weights its loss sees

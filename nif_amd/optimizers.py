@@ -323,6 +323,8 @@ class TFPLBFGS(object):
     def __init__(self, model, loss_fun, inps, outs, display_epoch=1, sample_weight=None):
         import numpy as np
         self._np = np
+        if getattr(model, "_is_pruned", False):
+            raise NotImplementedError("TFPLBFGS / LBFGSOptimizer on a pruned model (nif_amd.sparsity): strip_pruning(model) first")
         name = loss_fun if isinstance(loss_fun, str) else getattr(loss_fun, "name", None) or getattr(loss_fun, "__name__", None)
         if not isinstance(loss_fun, str) and loss_fun is not None:      # loss OBJECTS: only their defaults are built (as Model.compile)
             if float(getattr(loss_fun, "delta", 1.0)) != 1.0:
@@ -406,6 +408,8 @@ class LBFGSOptimizer(object):
         if not isinstance(loss_closure, MSEClosure):
             raise TypeError("LBFGSOptimizer(loss_closure=nif_amd.optimizers.MSEClosure(model, x, y), ...): a Python loss function "
                             "cannot be differentiated here -- the closure names the model and its table, the HIP kernels do the rest")
+        if getattr(loss_closure.model, "_is_pruned", False):
+            raise NotImplementedError("TFPLBFGS / LBFGSOptimizer on a pruned model (nif_amd.sparsity): strip_pruning(model) first")
         self._c = loss_closure
         self.steps = int(steps)
         self._it = 0
