@@ -36,9 +36,6 @@ __device__ __forceinline__ FuseDep fuse_dep_addr(int p, int g) {
 // deposit one operand (NBL = 4: two K-steps of 8 features) of this lane into the plane image at `img` (LDS byte pointer)
 __device__ __forceinline__ void fuse_deposit4(char* img, const FuseDep& d, const bf16x8 (&s)[2]) {
   typedef unsigned long long u64;
-#ifdef NIF_S6_NODEP      // measurement builds (results are wrong)
-  return;
-#endif
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     const u64 lo = __builtin_bit_cast(u64, __builtin_shufflevector(s[ks], s[ks], 0, 1, 2, 3));

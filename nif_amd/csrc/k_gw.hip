@@ -17,9 +17,6 @@
 // (nif/layers/mlp.py:219, nif/model.py:253-300 StridedSliceGrad + AddN; SURVEY a-10).
 #include "nif_internal.h"
 
-#ifndef NIF_GW_BF16
-#define NIF_GW_BF16 1
-#endif
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -122,12 +119,11 @@ __global__ __launch_bounds__(64 * WV) void k_gw_mfma(GwArgs A, int NBO) {
       for (int q = 0; q < 4; ++q) zq[kk][q] = ld4(zrow + 4 * q);   // k >= r: replaced by ones at use (compute_tile)
     }
   };
-#if NIF_GW_BF16
   // the K = batch GEMM on the bf16 matrix cores: both operands split into bf16 hi + lo, three products
   // (hi*hi + hi*lo + lo*hi, 1.9e-6 rms of sum|a b| -- well inside the fp32 re-association noise of a sum over
   // 10^6 points); v_mfma_f32_32x32x16_bf16 takes 8 consecutive points per lane: the two halves of a lane's 16
   auto compute_tile = [&](long t, const f32x4 (&af)[NBI][4], const f32x4 (&bf)[OBC][4], const f32x4 (&zq)[KC][4]) {
-    const bool wbias = t < A.bias_ntiles;
+    const bool wbias = t < A.bias_ntiles;   // tangent pseudo-tiles (Sobolev) carry no bias gradient
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
       bf16x8 bh[OBC], bl[OBC];
@@ -168,30 +164,6 @@ __global__ __launch_bounds__(64 * WV) void k_gw_mfma(GwArgs A, int NBO) {
       }
     }
   };
-#else
-  auto compute_tile = [&](long t, const f32x4 (&af)[NBI][4], const f32x4 (&bf)[OBC][4], const f32x4 (&zq)[KC][4]) {
-    const bool wbias = t < A.bias_ntiles;   // tangent pseudo-tiles (Sobolev) carry no bias gradient
-#pragma unroll
-    for (int kk = 0; kk < KC; ++kk) {
-      if (k0 + kk > A.r) break;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float zt = k0 + kk < A.r ? zq[kk][q][c] : 1.0f;
-#pragma unroll
-          for (int ib = 0; ib < NBI; ++ib) {
-            const float a = af[ib][q][c] * zt;
-#pragma unroll
-            for (int ob = 0; ob < OBC; ++ob)
-              acc[kk][ib][ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bf[ob][q][c], acc[kk][ib][ob], 0, 0, 0);
-          }
-#pragma unroll
-          for (int ob = 0; ob < OBC; ++ob) bacc[kk][ob] = fmaf(wbias ? zt : 0.f, bf[ob][q][c], bacc[kk][ob]);
-        }
-    }
-  };
-#endif
   if (!DBUF) {
     // one register set (wide variants whose accumulators already fill the file)
     f32x4 af0[NBI][4], bf0[OBC][4], zq0[KC][4];
@@ -485,12 +457,6 @@ static GwArgs gw_fix(const GwArgs& in) {
   return a;
 }
 
-#ifndef NIF_GW_WIDE_DBUF
-#define NIF_GW_WIDE_DBUF false
-#endif
-#ifndef NIF_GW_WIDE_KC2
-#define NIF_GW_WIDE_KC2 1
-#endif
 #ifndef NIF_GW_WAVES
 #define NIF_GW_WAVES 4   // 8 = two waves per SIMD, single-buffered: spills at 256 registers, slower
 #endif
@@ -543,15 +509,10 @@ int launch_gw_mfma(const GwArgs& a_, int NBI, int NBO, int rows, hipStream_t st)
     dim3 grid(rows, (a.r + 1 + 1) / 2, 1);
     hipLaunchKernelGGL((k_gw_mfma<2, 2, 2, WV, true>), grid, block, 0, st, a, NBO);
   } else if (NBI == 4 && NBO == 4) {
-#if NIF_GW_WIDE_KC2
     // 128-wide: both planes of a pair in one workgroup (256 accumulator registers, single-buffered): the layer-input
     // stash is read 2x and dL/da 1x instead of 4x and 2x
     dim3 grid(rows, (a.r + 1 + 1) / 2, 2);
-    hipLaunchKernelGGL((k_gw_mfma<4, 2, 2, WV, NIF_GW_WIDE_DBUF>), grid, block, 0, st, a, NBO);
-#else
-    dim3 grid(rows, a.r + 1, 2);
-    hipLaunchKernelGGL((k_gw_mfma<4, 2, 1, WV, true>), grid, block, 0, st, a, NBO);
-#endif
+    hipLaunchKernelGGL((k_gw_mfma<4, 2, 2, WV, false>), grid, block, 0, st, a, NBO);
   }
   return 0;
 }
@@ -765,9 +726,6 @@ __global__ __launch_bounds__(64 * WV) void k_gw_out_mfma(GwArgs A) {
   }
 }
 
-#ifndef NIF_GW_EDGE_MFMA
-#define NIF_GW_EDGE_MFMA 1
-#endif
 #ifndef NIF_GW_EDGE_WAVES
 #define NIF_GW_EDGE_WAVES 16
 #endif
@@ -907,7 +865,7 @@ __global__ __launch_bounds__(64 * WV) void k_gw_first_lds(GwArgs A) {
 void launch_gw_first(const GwArgs& a_, int NBO, int rows, hipStream_t st) {
   const GwArgs a = gw_fix(a_);
   static const bool use_lds = [] { const char* e = getenv("NIF_GW_LDS"); return !(e && e[0] == '0'); }();
-  if (use_lds && NIF_GW_EDGE_MFMA && (a.r + 1) * (a.nd + 1) <= 32 && (NBO <= 2 || NBO == 4) && a.ncol <= 16) {
+  if (use_lds && (a.r + 1) * (a.nd + 1) <= 32 && (NBO <= 2 || NBO == 4) && a.ncol <= 16) {
     const int buf = NBO * 1024 + ((a.r * 32 + 63) & ~63) + ((a.ncol * 32 + 63) & ~63);
     constexpr int WVL = 4;   // one wave per SIMD (two: 0.089 instead of 0.080 ms)
     size_t shl = sizeof(float) * (size_t)(WVL * 2 * buf);
@@ -925,7 +883,7 @@ void launch_gw_first(const GwArgs& a_, int NBO, int rows, hipStream_t st) {
     }
     return;
   }
-  if (NIF_GW_EDGE_MFMA && (a.r + 1) * (a.nd + 1) <= 32) {
+  if ((a.r + 1) * (a.nd + 1) <= 32) {
     constexpr int WV = NIF_GW_EDGE_WAVES;   // one workgroup per partial row: many waves hide the single-buffered loads
     dim3 grid(rows);
     const size_t shx = (size_t)WV * (a.nd > 0 ? a.nd : 1) * 32 * sizeof(float);
@@ -1147,7 +1105,7 @@ void launch_gw_out(const GwArgs& a_, int NBI, int rows, hipStream_t st) {
   const GwArgs a = gw_fix(a_);
   if (a.W.nin == 0 && a.r == 0 && a.has_bias) { hipLaunchKernelGGL(k_gw_bias, dim3(rows), dim3(256), 0, st, a); return; }
   // few columns (e.g. so = 1, r = 1): the VALU kernel below is as fast; from 8 columns on the MFMA form wins big
-  if (NIF_GW_EDGE_MFMA && (a.r + 1) * a.nc <= 32 && (a.r + 1) * a.nc >= 8) {
+  if ((a.r + 1) * a.nc <= 32 && (a.r + 1) * a.nc >= 8) {
     dim3 grid(rows), block(256);
     if (NBI == 1) hipLaunchKernelGGL((k_gw_out_mfma<1, 4>), grid, block, 0, st, a);
     else if (NBI == 2) hipLaunchKernelGGL((k_gw_out_mfma<2, 4>), grid, block, 0, st, a);

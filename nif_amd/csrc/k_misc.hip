@@ -270,9 +270,6 @@ __global__ __launch_bounds__(NIF_L2W_T) void k_latent_to_w(const float* __restri
 // are staged in LDS too: gfx9 counts loads and stores in ONE in-order vmcnt, so a per-unit global load of lr made every iteration
 // wait for the previous unit's STORE to be acknowledged -- 16 waves x 1 KB in flight per CU over ~2 k cycles of store latency is
 // exactly the 8 B / clk / CU (4.9 TB/s) r5 measured; now nothing in the loop waits for vector memory.
-#ifndef NIF_L2W_NT
-#define NIF_L2W_NT 0      // 1: non-temporal stores of the output stream (measured r6: see DESIGN 5.6)
-#endif
 #ifndef NIF_L2W_NB
 #define NIF_L2W_NB 4096   // workgroups = contiguous spans of the output
 #endif
@@ -332,11 +329,7 @@ __global__ __launch_bounds__(NIF_L2W_T) void k_latent_to_w_flat(const float* __r
           for (int c = 0; c < 4; ++c) q[c] = fmaf(zk, l2w_sm[k * PS + idx[c]], q[c]);
         }
       }
-#if NIF_L2W_NT
-      __builtin_nontemporal_store(q, reinterpret_cast<f32x4*>(w + e));
-#else
-      *reinterpret_cast<f32x4*>(w + e) = q;
-#endif
+      *reinterpret_cast<f32x4*>(w + e) = q;      // (plain stores: non-temporal ones were 5 % slower in the write-stream probe)
     } else {
       // a unit that straddles a row boundary (or an end of the buffer): element by element
       int ar = a, scc = sc;

@@ -14,10 +14,6 @@
 #include "nif_internal.h"
 #include "k_pnet_bf16.h"
 
-#ifndef NIF_PBW_DENSE_BF16
-#define NIF_PBW_DENSE_BF16 1   // 0: f32-input MFMAs for the dense products (A/B builds)
-#endif
-
 struct PbwArgs {
   PNetArgs p;
   float* partial; long pstride;   // partial[row * pstride + theta index], row = blockIdx.x
@@ -45,9 +41,6 @@ __device__ __forceinline__ void tile_store(float* __restrict__ t, const f32x16& 
 // C[in][out] += sum_p IN[p][in] * DA[p][out] over the 32 points of the tile; IN, DA are LDS tiles [feature][32].
 // Gradient path: bf16 hi/lo splits, three v_mfma_f32_32x32x16_bf16 per 16 points (k_gw.hip) instead of 8 f32-input MFMAs
 typedef __bf16 pbw_bf16x8 __attribute__((ext_vector_type(8)));
-#ifndef NIF_PBW_BF16
-#define NIF_PBW_BF16 1
-#endif
 // in_rows < 32: IN holds only that many feature rows (the X^T tile of the first layer): the others count as zero
 __device__ __forceinline__ void grad_mfma(const float* IN, const float* DA, f32x16& C, int i, int hf, int in_rows = 32) {
   f32x4 a[4], b[4];
@@ -57,7 +50,6 @@ __device__ __forceinline__ void grad_mfma(const float* IN, const float* DA, f32x
     if (i >= in_rows) { a[q][0] = 0.f; a[q][1] = 0.f; a[q][2] = 0.f; a[q][3] = 0.f; }
     b[q] = lds4(DA + pswz4(i, 4 * hf + q));
   }
-#if NIF_PBW_BF16
 #pragma unroll
   for (int hh = 0; hh < 2; ++hh) {
     pbw_bf16x8 ah, al, bh, bl;
@@ -72,12 +64,6 @@ __device__ __forceinline__ void grad_mfma(const float* IN, const float* DA, f32x
     C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, C, 0, 0, 0);
     C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, C, 0, 0, 0);
   }
-#else
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) C = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][c], b[q][c], C, 0, 0, 0);
-#endif
 }
 // column sums of a DA tile: lane (i, hf) -> sum over its 16 points of feature i (other half via shfl)
 __device__ __forceinline__ float col_sum(const float* DA, int i, int hf) {
@@ -111,7 +97,6 @@ __global__ __launch_bounds__(64 * NIF_PBW_WAVES) void k_pnet_bwg(PbwArgs G) {
   float* hs = lds + (long)wid * WLDS;              // NM+1 layer-input tiles, then the dL/da tile and the X tile
   float* gaT = hs + (NM + 1) * 1024;
   float* xT = gaT + 1024;                          // [8 rows: the pi <= 6 inputs, then ones, rest zero][32]
-  const long plane = 256;                           // f32x4 per packed 32x32 matrix
 
   f32x16 C[NM], C1, Cb, CB1;   // SMALL: C1 = per-lane sum x da0, CB1 = per-lane sum da0, Cb = per-lane sum dz h
   float gbh[NM], gb0 = 0.f, gbb = 0.f;
@@ -125,11 +110,10 @@ __global__ __launch_bounds__(64 * NIF_PBW_WAVES) void k_pnet_bwg(PbwArgs G) {
   }
   for (int q = lane; q < 256; q += 64) xT[q] = 0.f;
   const PSmall S = psmall_stage<1>(A, lds + (long)WV * WLDS, threadIdx.x, 64 * WV);
-  // the 2 NM packed 32x32 weight planes (forward, then adjoint) live in LDS for the whole kernel: the per-tile
-  // dense products read their A operands with ds_read_b128 instead of waiting on global loads four times a tile
+  // the NM matrices' weight planes (forward, then adjoint) live in LDS for the whole kernel: the per-tile dense products read
+  // their A operands with ds_read_b128 instead of waiting on global loads four times a tile.  bf16 split planes built here from
+  // theta (k_pnet_bf16.h): per matrix 6 KB forward + 4 KB adjoint
   f32x4* wpl = reinterpret_cast<f32x4*>(lds + (long)WV * WLDS + ((psmall_floats(A, 1) + 3) & ~3));
-#if NIF_PBW_DENSE_BF16
-  // bf16 split planes built here from theta (k_pnet_bf16.h): per matrix 6 KB forward + 4 KB adjoint
   pbf16x8* bpl = reinterpret_cast<pbf16x8*>(wpl);
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
@@ -139,13 +123,6 @@ __global__ __launch_bounds__(64 * NIF_PBW_WAVES) void k_pnet_bwg(PbwArgs G) {
   }
   auto dense_f = [&](int m, const f32x16 (&x)[1], f32x16 (&y)[1]) { pbf_dense_fwd(bpl + m * (PBF_FWD_U4 + PBF_BWD_U4), x[0], y[0], lane); };
   auto dense_b = [&](int m, const f32x16 (&x)[1], f32x16 (&y)[1]) { pbf_dense_bwd(bpl + m * (PBF_FWD_U4 + PBF_BWD_U4) + PBF_FWD_U4, x[0], y[0], lane); };
-#else
-  for (int e = threadIdx.x; e < NM * 256; e += 64 * WV) { wpl[e] = A.WF[e]; wpl[NM * 256 + e] = A.WB[e]; }
-  const f32x4* WFl = wpl;
-  const f32x4* WBl = wpl + NM * 256;
-  auto dense_f = [&](int m, const f32x16 (&x)[1], f32x16 (&y)[1]) { dense_mfma_lds<1, 1, false>(WFl + (long)m * plane, x, y, lane); };
-  auto dense_b = [&](int m, const f32x16 (&x)[1], f32x16 (&y)[1]) { dense_mfma_lds<1, 1, false>(WBl + (long)m * plane, x, y, lane); };
-#endif
   __syncthreads();
 
   for (long tile = (long)blockIdx.x * WV + wid; tile < ntiles; tile += (long)gridDim.x * WV) {
@@ -394,7 +371,7 @@ void launch_pnet_bwg(const PNetArgs& a, float* partial, long pstride, int rows, 
   const int nm = a.lst * (a.res ? 2 : 1);
   dim3 grid(rows), block(64 * NIF_PBW_WAVES);
   const size_t shm = ((size_t)NIF_PBW_WAVES * ((nm + 2) * 1024 + 256) + (size_t)((psmall_floats(a, 1) + 3) & ~3) +
-                      (size_t)nm * (NIF_PBW_DENSE_BF16 ? 2560 : 2048)) * sizeof(float);
+                      (size_t)nm * 2560) * sizeof(float);
 #define PBW1(NM_, RES_, ACT_, SM_)                                                                                  \
   {                                                                                                                 \
     (void)hipFuncSetAttribute((const void*)k_pnet_bwg<NM_, RES_, ACT_, SM_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \

@@ -23,15 +23,6 @@
 // Keras 'mse' (README.md:33), adjoint per SURVEY a-10.
 #include "k_snet3_dev.h"
 
-// Ablation switches for timing experiments (NEVER set in a product build: results become wrong).
-//   NIF_ABL_NOSTORE  skip the stash / ring stores      NIF_ABL_NOACT   cheap stand-in for the activation
-//   NIF_ABL_NOBAR    skip the per-plane barrier         NIF_ABL_NOMFMA  skip the MFMAs
-#ifndef NIF_S3_PREFETCH_ADJ
-#define NIF_S3_PREFETCH_ADJ 0   // fetch act'(a) and h_in one layer ahead in the adjoint
-#endif
-#ifndef NIF_S3_LDSDMA
-#define NIF_S3_LDSDMA 1          // stage weight planes with global_load_lds instead of through registers
-#endif
 #ifndef NIF_S3_OCC4
 #define NIF_S3_OCC4 3   // waves/SIMD requested for the 64-wide (NBL = 4) instantiation
 #endif
@@ -124,11 +115,6 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
     }
   }
   __syncthreads();
-#ifdef NIF_S3_STAGGER
-  // de-phase the workgroups that share a CU (the second wave of residents starts NIF_S3_STAGGER*64 cycles
-  // late), so that one wave's VALU epilogue overlaps its SIMD partner's MFMA plane instead of colliding
-  if (blockIdx.x >= gridDim.x / 2) __builtin_amdgcn_s_sleep(NIF_S3_STAGGER);
-#endif
   int gpar = 0;
   int tlc = 0; (void)tlc;
   float loss_lane = 0.f;
@@ -141,22 +127,11 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
 #else
 #define NIF_TL(id) do { } while (0)
 #endif
-#ifdef NIF_ABL_NOPREFETCH
-#define NIF_HAS_NEXT false
-#else
-#define NIF_HAS_NEXT ((pl + 1 < nplanes) || !last_group)
-#endif
-#ifdef NIF_ABL_NOBAR
-#define NIF_BAR() __builtin_amdgcn_wave_barrier()
-#else
-#define NIF_BAR() __syncthreads()
-#endif
-#if NIF_S3_LDSDMA
 // the next plane goes L2 -> LDS by DMA (global_load_lds_dwordx4: wave-uniform LDS base + lane*16, our plane
 // image is lane-linear), no staging registers; hipcc drains it (vmcnt(0)) in front of the barrier
 #define NIF_PLANE(...)                                                                        \
   {                                                                                           \
-    if (NIF_HAS_NEXT) {                                                                       \
+    if ((pl + 1 < nplanes) || !last_group) {                                                  \
       const f32x4* src = plane_src(pl + 1 < nplanes ? pl + 1 : 0);                            \
       f32x4* dst = planes + ((gpar + 1) & 1) * (PLANE / 4);                                   \
       _Pragma("unroll") for (int q = 0; q < PF4; ++q)                                         \
@@ -167,31 +142,9 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
     }                                                                                         \
     const f32x4* cur = planes + (gpar & 1) * (PLANE / 4);                                     \
     __VA_ARGS__                                                                               \
-    NIF_BAR();                                                                                \
+    __syncthreads();                                                                          \
     ++gpar; ++pl;                                                                             \
   }
-#else
-#define NIF_PLANE(...)                                                                        \
-  {                                                                                           \
-    const bool has_next = NIF_HAS_NEXT;                                                       \
-    f32x4 pre[PF4];                                                                           \
-    if (has_next) {                                                                           \
-      const f32x4* src = plane_src(pl + 1 < nplanes ? pl + 1 : 0);                            \
-      _Pragma("unroll") for (int q = 0; q < PF4; ++q)                                         \
-        if (PEXACT || tid + NT * q < PLANE / 4) pre[q] = src[tid + NT * q];                   \
-    }                                                                                         \
-    const f32x4* cur = planes + (gpar & 1) * (PLANE / 4);                                     \
-    __VA_ARGS__                                                                               \
-    if (has_next) {                                                                           \
-      f32x4* dst = planes + ((gpar + 1) & 1) * (PLANE / 4);                                   \
-      _Pragma("unroll") for (int q = 0; q < PF4; ++q)                                         \
-        if (PEXACT || tid + NT * q < PLANE / 4) dst[tid + NT * q] = pre[q];                   \
-    }                                                                                         \
-    NIF_BAR();                                                                                \
-    ++gpar; ++pl;                                                                             \
-  }
-
-#endif
 
   for (long tg = blockIdx.x; tg < ngroups; tg += gridDim.x) {
     const bool last_group = tg + gridDim.x >= ngroups;
@@ -342,21 +295,12 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
       NIF_TL(4);
 
       // ---- adjoint through the hidden hyper-matrices --------------------------------------------
-      // act'(a_j) and h_{j-1} are fetched one layer ahead so that their L2/HBM latency hides behind the
-      // previous layer's MFMA planes
       f32x4 skip[MODE == 0 ? 1 : NBL];
       f32x4 dnext[NBL], hin[NBL];
-#if NIF_S3_PREFETCH_ADJ
-#pragma unroll
-      for (int b = 0; b < NBL; ++b) dnext[b] = reinterpret_cast<const f32x4*>(dring)[(nh * NBL + b) * 64 + lane];
-      if (nh > 0 && r > 0) st_load16<NBL>(IN0 + (long)(nh - 1) * A.slot_stride, row0, hin, g);
-#endif
       for (int j = nh - 1; j >= 0; --j) {
         f32x4 ga[NBL];
-#if !NIF_S3_PREFETCH_ADJ
 #pragma unroll
         for (int b = 0; b < NBL; ++b) dnext[b] = reinterpret_cast<const f32x4*>(dring)[((j + 1) * NBL + b) * 64 + lane];
-#endif
         if (MODE == 1 && (j & 1)) {
 #pragma unroll
           for (int b = 0; b < NBL; ++b) { skip[b] = 0.5f * gh[b]; ga[b] = dnext[b] * skip[b]; }
@@ -368,11 +312,6 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
             for (int b = 0; b < NBL; ++b) skip[b] = gh[b];
           }
         }
-#if NIF_S3_PREFETCH_ADJ
-        // next layer's act'(a) (layer j-1, or the first layer's when j == 0)
-#pragma unroll
-        for (int b = 0; b < NBL; ++b) dnext[b] = reinterpret_cast<const f32x4*>(dring)[(j * NBL + b) * 64 + lane];
-#endif
         if (active) st_store16<NBL>(DA0 + (long)(j + 1) * A.slot_stride, row0, ga, g);
         NIF_TL(50 + j);
 #pragma unroll
@@ -384,9 +323,7 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
               f32x4 U[NBL];
               mfma16<NBL, false>(cur, ga, U, lane);
               _Pragma("unroll") for (int b = 0; b < NBL; ++b) gh[b] += zt * U[b];
-#if !NIF_S3_PREFETCH_ADJ
               st_load16<NBL>(IN0 + (long)j * A.slot_stride, row0, hin, g);
-#endif
               const float* sb = sm + k * nsm + o_bh + j * NP + 4 * g;
               float s = 0.f, sbv = 0.f;
               _Pragma("unroll") for (int b = 0; b < NBL; ++b) {
@@ -397,9 +334,6 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
                 }
               }
               dzs[k * 64 + lane] += fmaf(A.omega, s, sbv);
-#if NIF_S3_PREFETCH_ADJ
-              if (k == r - 1 && j > 0) st_load16<NBL>(IN0 + (long)(j - 1) * A.slot_stride, row0, hin, g);
-#endif
             } else {
               mfma16<NBL, true>(cur, ga, gh, lane);
             }
@@ -416,10 +350,8 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
       // ---- first layer ---------------------------------------------------------------------------
       {
         f32x4 ga[NBL];
-#if !NIF_S3_PREFETCH_ADJ
 #pragma unroll
         for (int b = 0; b < NBL; ++b) dnext[b] = reinterpret_cast<const f32x4*>(dring)[b * 64 + lane];
-#endif
 #pragma unroll
         for (int b = 0; b < NBL; ++b) ga[b] = dnext[b] * gh[b];
         if (active) st_store16<NBL>(DA0, row0, ga, g);

@@ -2,10 +2,6 @@
 #pragma once
 #include "nif_internal.h"
 
-#ifndef NIF_S3_SETPRIO
-#define NIF_S3_SETPRIO 1
-#endif
-
 __device__ __forceinline__ float hyp3(const SNetArgs& A, int k, long slot) {
   return k < A.r ? A.theta[A.off_Wh + (long)k * A.po + slot] : A.theta[A.off_bh + slot];
 }
@@ -15,9 +11,7 @@ __device__ __forceinline__ float hyp3(const SNetArgs& A, int k, long slot) {
 // consecutive MFMAs hit independent accumulators
 template <int NBL, bool ACCUM>
 __device__ __forceinline__ void mfma16(const f32x4* plane, const f32x4 (&hin)[NBL], f32x4 (&T)[NBL], int lane) {
-#if NIF_S3_SETPRIO
   __builtin_amdgcn_s_setprio(1);   // MFMA cluster wins VALU-issue arbitration against co-resident waves (+8 %)
-#endif
   if (!ACCUM) {
 #pragma unroll
     for (int ob = 0; ob < NBL; ++ob) { T[ob][0] = 0.f; T[ob][1] = 0.f; T[ob][2] = 0.f; T[ob][3] = 0.f; }
@@ -31,23 +25,14 @@ __device__ __forceinline__ void mfma16(const f32x4* plane, const f32x4 (&hin)[NB
     for (int v = 0; v < 4; ++v)
 #pragma unroll
       for (int ob = 0; ob < NBL; ++ob)
-#ifdef NIF_ABL_NOMFMA
-        T[ob][v] += a[ob][v] * hin[ib][v];
-#else
         T[ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ob][v], hin[ib][v], T[ob], 0, 0, 0);
-#endif
   }
-#if NIF_S3_SETPRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // stash [tile32][feature][32]: this wave's 16-point tile is half `hx` of tile32
 template <int NBL>
 __device__ __forceinline__ void st_store16(float* __restrict__ slot, long row0, const f32x4 (&h)[NBL], int g) {
-#ifdef NIF_ABL_NOSTORE
-  if (h[0][0] != 12345.678f) return;
-#endif
   // row0 = (tile32 * FP) * 32 + 16*half + p   (floats); feature f lives at row0 + f*32.  One base address per PAIR of
   // blocks: the 8 accesses of a pair then sit within the 12-bit immediate offset (r2: hipcc kept 8 extra 64-bit per-feature
   // offsets in 16 VGPRs and spent a v_lshl_add_u64 per access on the second half of the tile)
@@ -63,9 +48,6 @@ __device__ __forceinline__ void st_store16(float* __restrict__ slot, long row0, 
 // the same tile as bf16 rows [tile32][feature][32 points] of 64 B (dL/da under mixed_bfloat16): same element index, half the bytes
 template <int NBL>
 __device__ __forceinline__ void st_store16_bf(float* __restrict__ slot, long row0, const f32x4 (&h)[NBL], int g) {
-#ifdef NIF_ABL_NOSTORE
-  if (h[0][0] != 12345.678f) return;
-#endif
 #pragma unroll
   for (int b = 0; b < NBL; b += 2) {
     __bf16* q = reinterpret_cast<__bf16*>(slot) + (row0 + (long)(16 * b + 4 * g) * 32);
@@ -77,13 +59,6 @@ __device__ __forceinline__ void st_store16_bf(float* __restrict__ slot, long row
 }
 template <int NBL>
 __device__ __forceinline__ void st_load16(const float* __restrict__ slot, long row0, f32x4 (&h)[NBL], int g) {
-#ifdef NIF_ABL_NOLOAD      // measurement builds: how much of the kernel is the stash round trip (results are wrong)
-  if (row0 != -12345) {
-#pragma unroll
-    for (int b = 0; b < NBL; ++b) { h[b][0] = 0.5f; h[b][1] = 0.25f; h[b][2] = 0.125f; h[b][3] = 0.75f; }
-    return;
-  }
-#endif
 #pragma unroll
   for (int b = 0; b < NBL; b += 2) {
     const float* q = slot + (row0 + (long)(16 * b + 4 * g) * 32);
@@ -301,9 +276,6 @@ __device__ __forceinline__ void sine16_tag_ph(const f32x4 (&a)[NBL], f32x4 (&h)[
 // the tile's phases as int16 rows [tile32][feature][32 points] of 64 B (element index as st_store16)
 template <int NBL>
 __device__ __forceinline__ void st_store16_ph(float* __restrict__ slot, long row0, const unsigned (&ph)[2 * NBL], int g) {
-#ifdef NIF_ABL_NOSTORE
-  if (ph[0] != 0x12345678u) return;
-#endif
 #pragma unroll
   for (int b = 0; b < NBL; b += 2) {
     unsigned short* q = reinterpret_cast<unsigned short*>(slot) + (row0 + (long)(16 * b + 4 * g) * 32);
@@ -316,13 +288,6 @@ __device__ __forceinline__ void st_store16_ph(float* __restrict__ slot, long row
 // ... read back as phases in REVOLUTIONS (f = q / 65536): ph_sin / ph_cos rebuild sin(a) / cos(a)
 template <int NBL>
 __device__ __forceinline__ void st_load16_ph(const float* __restrict__ slot, long row0, f32x4 (&f)[NBL], int g) {
-#ifdef NIF_ABL_NOLOAD
-  if (row0 != -12345) {
-#pragma unroll
-    for (int b = 0; b < NBL; ++b) { f[b][0] = 0.05f; f[b][1] = 0.25f; f[b][2] = 0.125f; f[b][3] = -0.075f; }
-    return;
-  }
-#endif
 #pragma unroll
   for (int b = 0; b < NBL; b += 2) {
     const short* q = reinterpret_cast<const short*>(slot) + (row0 + (long)(16 * b + 4 * g) * 32);
@@ -353,10 +318,6 @@ __device__ __forceinline__ void tag_cos(const f32x4 (&sn)[NBL], f32x4 (&d)[NBL])
 }
 template <int NBL, int ACT>
 __device__ __forceinline__ void act16(int act, const f32x4 (&a)[NBL], f32x4 (&h)[NBL], f32x4 (&d)[NBL], int n, int g) {
-#ifdef NIF_ABL_NOACT
-  _Pragma("unroll") for (int b = 0; b < NBL; ++b) { f32x4 t = a[b]; h[b] = t * 0.5f; d[b] = t + 1.0f; }
-  return;
-#endif
   if (ACT == ACT_SINE) { sine16<NBL>(a, h, d); return; }
   switch (act) {
     case ACT_SINE: sine16<NBL>(a, h, d); break;
@@ -395,11 +356,9 @@ __device__ __forceinline__ float act_d2(int act, float a) {
 }
 
 
-// s_setprio around the MFMA clusters of mfma_x6 / mfma_x3 (a translation unit that manages the priority itself defines the two away)
-#ifndef NIF_MFMA_PRIO_ON
+// s_setprio around the MFMA clusters of mfma_x6 / mfma_x3
 #define NIF_MFMA_PRIO_ON __builtin_amdgcn_s_setprio(1);
 #define NIF_MFMA_PRIO_OFF __builtin_amdgcn_s_setprio(0);
-#endif
 // ---- fp32 products as exact bf16 splits (k_snet4.hip has the derivation and the measured accuracy) ---------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -517,9 +476,6 @@ __device__ __forceinline__ void mfma_x6(const bf16x8* cur, const bf16x8 b0, cons
   NIF_MFMA_PRIO_OFF
 }
 // one K-step chunk of an adjoint plane, 3-product form, two blocks' chains interleaved
-#ifndef NIF_X16_LOLO
-#define NIF_X16_LOLO 0
-#endif
 template <int NBL, int PR = 0, bool ZI = false, int NT = NBL, int OB0 = 0, bool CP = false>
 __device__ __forceinline__ void mfma_x3(const bf16x8* cur, const bf16x8 b0, const bf16x8 b1, f32x4 (&T_)[NT], int lane) {
   NIF_MFMA_PRIO_ON
@@ -542,15 +498,8 @@ __device__ __forceinline__ void mfma_x3(const bf16x8* cur, const bf16x8 b0, cons
     const bf16x8 a0 = cur[(ib * 2 + 0) * 64 + lane], a1 = cur[(ib * 2 + 1) * 64 + lane];
     const bf16x8 c0 = cur[(ib * 2 + 2) * 64 + lane], c1 = cur[(ib * 2 + 3) * 64 + lane];
     if (PR == 3) {      // exact-product half planes (hi, lo) x half operand pair (b0 = hi, b1 = lo): three products, small terms first
-#if NIF_X16_LOLO      // measurement builds (r6): the lo.lo term as a fourth product (2^-24 of the product; DESIGN 7: what it buys the gradient)
-      T[ib] = mfma_f16(a1, b1, ZI ? z4 : T[ib]);
-      T[ib + 1] = mfma_f16(c1, b1, ZI ? z4 : T[ib + 1]);
-      T[ib] = mfma_f16(a0, b1, T[ib]);
-      T[ib + 1] = mfma_f16(c0, b1, T[ib + 1]);
-#else
       T[ib] = mfma_f16(a0, b1, ZI ? z4 : T[ib]);
       T[ib + 1] = mfma_f16(c0, b1, ZI ? z4 : T[ib + 1]);
-#endif
       T[ib] = mfma_f16(a1, b0, T[ib]);
       T[ib + 1] = mfma_f16(c1, b0, T[ib + 1]);
       T[ib] = mfma_f16(a0, b0, T[ib]);
@@ -564,102 +513,6 @@ __device__ __forceinline__ void mfma_x3(const bf16x8* cur, const bf16x8 b0, cons
     T[ib] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, T[ib], 0, 0, 0);
     T[ib + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c0, b0, T[ib + 1], 0, 0, 0);
   }
-  NIF_MFMA_PRIO_OFF
-}
-
-// the PR = 3 form with the first block pair's A operands already in registers (k_snet6, r6: read in front of the step's DMA issue)
-template <int NBL, bool ZI>
-__device__ __forceinline__ void mfma_x3_pre(const bf16x8* cur, const bf16x8 (&pa)[4], const bf16x8 b0, const bf16x8 b1, f32x4 (&T)[NBL], int lane) {
-  NIF_MFMA_PRIO_ON
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ib = 0; ib < NBL; ib += 2) {
-    const bf16x8 a0 = ib == 0 ? pa[0] : cur[(ib * 2 + 0) * 64 + lane], a1 = ib == 0 ? pa[1] : cur[(ib * 2 + 1) * 64 + lane];
-    const bf16x8 c0 = ib == 0 ? pa[2] : cur[(ib * 2 + 2) * 64 + lane], c1 = ib == 0 ? pa[3] : cur[(ib * 2 + 3) * 64 + lane];
-    T[ib] = mfma_f16(a0, b1, ZI ? z4 : T[ib]);
-    T[ib + 1] = mfma_f16(c0, b1, ZI ? z4 : T[ib + 1]);
-    T[ib] = mfma_f16(a1, b0, T[ib]);
-    T[ib + 1] = mfma_f16(c1, b0, T[ib + 1]);
-    T[ib] = mfma_f16(a0, b0, T[ib]);
-    T[ib + 1] = mfma_f16(c0, b0, T[ib + 1]);
-  }
-  NIF_MFMA_PRIO_OFF
-}
-
-// ... and the software-pipelined form (k_snet6, NIF_S6_PF): the first block pair's operands of THIS chunk come from registers when the
-// previous step prefetched them (USEPF), and the first pair of the NEXT chunk (already landed: three chunk buffers, DMA two steps
-// ahead) is read behind this chunk's first six products (MAKEPF) -- the LDS latency of a step's first reads leaves the critical path
-template <int NBL, bool ZI, bool USEPF, bool MAKEPF>
-__device__ __forceinline__ void mfma_x3_pf(const bf16x8* cur, const bf16x8* nxt, bf16x8 (&pf)[4], const bf16x8 b0, const bf16x8 b1,
-                                           f32x4 (&T)[NBL], int lane) {
-  static_assert(NBL == 4, "two block pairs per chunk");
-  NIF_MFMA_PRIO_ON
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  const bf16x8 a0 = USEPF ? pf[0] : cur[0 * 64 + lane], a1 = USEPF ? pf[1] : cur[1 * 64 + lane];
-  const bf16x8 c0 = USEPF ? pf[2] : cur[2 * 64 + lane], c1 = USEPF ? pf[3] : cur[3 * 64 + lane];
-  const bf16x8 d0 = cur[4 * 64 + lane], d1 = cur[5 * 64 + lane], e0 = cur[6 * 64 + lane], e1 = cur[7 * 64 + lane];
-  T[0] = mfma_f16(a0, b1, ZI ? z4 : T[0]);
-  T[1] = mfma_f16(c0, b1, ZI ? z4 : T[1]);
-  T[0] = mfma_f16(a1, b0, T[0]);
-  T[1] = mfma_f16(c1, b0, T[1]);
-  T[0] = mfma_f16(a0, b0, T[0]);
-  T[1] = mfma_f16(c0, b0, T[1]);
-  if (MAKEPF) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pf[i] = nxt[i * 64 + lane];
-  }
-  T[2] = mfma_f16(d0, b1, ZI ? z4 : T[2]);
-  T[3] = mfma_f16(e0, b1, ZI ? z4 : T[3]);
-  T[2] = mfma_f16(d1, b0, T[2]);
-  T[3] = mfma_f16(e1, b0, T[3]);
-  T[2] = mfma_f16(d0, b0, T[2]);
-  T[3] = mfma_f16(e0, b0, T[3]);
-  NIF_MFMA_PRIO_OFF
-}
-
-// ... and a whole PLANE of the exact-product form in one step (k_snet6, NIF_S6_BIGCHUNK: the 16 KB chunk = K-step halves at cur and cur + CFU
-// units): four operand groups (K step, block pair); the reads of group g + 2 are issued BEHIND the products of group g, so that the
-// step exposes ONE LDS round trip instead of one per group (r6 timeline: ~1 200 ticks of `mfma` phase for 384 matrix cycles)
-template <int NBL, bool ZI, int CFU>
-__device__ __forceinline__ void mfma_x3_plane(const bf16x8* cur, const bf16x8 (&b0)[2], const bf16x8 (&b1)[2], f32x4 (&T)[NBL], int lane) {
-  static_assert(NBL == 4, "two block pairs per K step");
-  NIF_MFMA_PRIO_ON
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  const bf16x8* c0_ = cur + lane;
-  bf16x8 p0 = c0_[0 * 64], p1 = c0_[1 * 64], p2 = c0_[2 * 64], p3 = c0_[3 * 64];                   // (K step 0, blocks 0 1)
-  bf16x8 q0 = c0_[4 * 64], q1 = c0_[5 * 64], q2 = c0_[6 * 64], q3 = c0_[7 * 64];                   // (K step 0, blocks 2 3)
-  __builtin_amdgcn_sched_barrier(0);
-  T[0] = mfma_f16(p0, b1[0], ZI ? z4 : T[0]);
-  T[1] = mfma_f16(p2, b1[0], ZI ? z4 : T[1]);
-  T[0] = mfma_f16(p1, b0[0], T[0]);
-  T[1] = mfma_f16(p3, b0[0], T[1]);
-  T[0] = mfma_f16(p0, b0[0], T[0]);
-  T[1] = mfma_f16(p2, b0[0], T[1]);
-  __builtin_amdgcn_sched_barrier(0);
-  const bf16x8* c1_ = cur + CFU + lane;
-  p0 = c1_[0 * 64]; p1 = c1_[1 * 64]; p2 = c1_[2 * 64]; p3 = c1_[3 * 64];                          // (K step 1, blocks 0 1)
-  __builtin_amdgcn_sched_barrier(0);
-  T[2] = mfma_f16(q0, b1[0], ZI ? z4 : T[2]);
-  T[3] = mfma_f16(q2, b1[0], ZI ? z4 : T[3]);
-  T[2] = mfma_f16(q1, b0[0], T[2]);
-  T[3] = mfma_f16(q3, b0[0], T[3]);
-  T[2] = mfma_f16(q0, b0[0], T[2]);
-  T[3] = mfma_f16(q2, b0[0], T[3]);
-  __builtin_amdgcn_sched_barrier(0);
-  q0 = c1_[4 * 64]; q1 = c1_[5 * 64]; q2 = c1_[6 * 64]; q3 = c1_[7 * 64];                          // (K step 1, blocks 2 3)
-  __builtin_amdgcn_sched_barrier(0);
-  T[0] = mfma_f16(p0, b1[1], T[0]);
-  T[1] = mfma_f16(p2, b1[1], T[1]);
-  T[0] = mfma_f16(p1, b0[1], T[0]);
-  T[1] = mfma_f16(p3, b0[1], T[1]);
-  T[0] = mfma_f16(p0, b0[1], T[0]);
-  T[1] = mfma_f16(p2, b0[1], T[1]);
-  T[2] = mfma_f16(q0, b1[1], T[2]);
-  T[3] = mfma_f16(q2, b1[1], T[3]);
-  T[2] = mfma_f16(q1, b0[1], T[2]);
-  T[3] = mfma_f16(q3, b0[1], T[3]);
-  T[2] = mfma_f16(q0, b0[1], T[2]);
-  T[3] = mfma_f16(q2, b0[1], T[3]);
   NIF_MFMA_PRIO_OFF
 }
 

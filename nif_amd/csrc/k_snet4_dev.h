@@ -233,11 +233,7 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && T
 #endif
   float loss_lane = 0.f;
   float* dring = (TRAIN && !SGN) ? A.dring + ((long)blockIdx.x * WAVES + wid) * (long)(nh + 1) * (NBL * 256) : nullptr;
-#ifdef NIF_ABL_INTERLEAVE     // measurement builds: the ten slots of a tile next to each other (the consumers then read garbage)
-  const long sstride = (long)FP * 32, tstride = (long)(2 * (nh + 1)) * FP * 32;
-#else
   const long sstride = A.slot_stride, tstride = (long)FP * 32;
-#endif
   float* IN0 = A.stash;
   float* DA0 = A.stash + (long)(nh + 1) * sstride;
 
@@ -296,11 +292,7 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && T
     const float* ys = zs + CZ * 16 + p;                 // y_o = ys[o*16]
     const float* wsp = zs + (CZ + CY) * 16 + p;
     const float* zt_base = zs + p;
-#ifdef NIF_ABL_STASHMASK      // measurement builds: the stash traffic folded onto a cache-resident window (results are wrong)
-    const long row0 = (tile32 & NIF_ABL_STASHMASK) * (long)FP * 32 + poff;
-#else
     const long row0 = tile32 * tstride + poff;
-#endif
     if (TRAIN)
       for (int k = 0; k < r; ++k) dzs[k * 64 + lane] = 0.f;
 

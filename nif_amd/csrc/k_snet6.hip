@@ -26,69 +26,22 @@
 
 #define ZERO_T6(x) _Pragma("unroll") for (int b_ = 0; b_ < NBL; ++b_) { (x)[b_][0] = 0.f; (x)[b_][1] = 0.f; (x)[b_][2] = 0.f; (x)[b_][3] = 0.f; }
 
-#ifndef NIF_S6_RING
-#define NIF_S6_RING 1       // 1: the h_j rows of a wave's tile in a private ring [matrix j][feature][16 points] that stays cache resident; 0: the [tile32][feature][32] stash
-#endif
-// private ring of a wave, point-major: the 4 features of (block b, lane group g) of point p are ONE 16-byte piece at
-// p * NP + 16 b + 4 g -- 4 store / load instructions per layer instead of 16 (NIF_S6_RING_V4 = 0: feature-major rows f * 16 + p)
-#ifndef NIF_S6_RING_NT
-#define NIF_S6_RING_NT 0      // bit 0: non-temporal ring stores, bit 1: non-temporal ring loads (measured: see DESIGN)
-#endif
-#ifndef NIF_S6_RING_V4
-#define NIF_S6_RING_V4 0
-#endif
-#ifndef NIF_S6_VMRING
-#define NIF_S6_VMRING 0       // 1: ring stores / loads behind the chunk DMA, counted out of the chunk wait (S6_CHUNK_RING) -- measured r4: 1.327 / 1.331 vs 1.332 / 1.330 ms per step, no gain: nothing waits for the ring
-#endif
+// private ring of a wave (the h_j rows of its tile, [matrix j][feature][16 points]: stays cache resident), feature-major rows f * 16 + p
 template <int NBL>
 __device__ __forceinline__ void ring_store16(float* __restrict__ slot, const f32x4 (&h)[NBL], int g, int p) {
-#ifdef NIF_ABL_NOSTORE
-  if (h[0][0] != 12345.678f) return;
-#endif
-#if NIF_S6_RING_V4
-  f32x4* q = reinterpret_cast<f32x4*>(slot + p * (16 * NBL) + 4 * g);
-#pragma unroll
-  for (int b = 0; b < NBL; ++b) q[4 * b] = h[b];
-#else
   float* q = slot + 4 * g * 16 + p;
 #pragma unroll
   for (int b = 0; b < NBL; ++b)
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-#if NIF_S6_RING_NT & 1
-      __builtin_nontemporal_store(h[b][v], q + (16 * b + v) * 16);
-#else
-      q[(16 * b + v) * 16] = h[b][v];
-#endif
-    }
-#endif
+    for (int v = 0; v < 4; ++v) q[(16 * b + v) * 16] = h[b][v];
 }
 template <int NBL>
 __device__ __forceinline__ void ring_load16(const float* __restrict__ slot, f32x4 (&h)[NBL], int g, int p) {
-#ifdef NIF_ABL_NOLOAD
-  if (p != -12345) {
-#pragma unroll
-    for (int b = 0; b < NBL; ++b) { h[b][0] = 0.5f; h[b][1] = 0.25f; h[b][2] = 0.125f; h[b][3] = 0.75f; }
-    return;
-  }
-#endif
-#if NIF_S6_RING_V4
-  const f32x4* q = reinterpret_cast<const f32x4*>(slot + p * (16 * NBL) + 4 * g);
-#pragma unroll
-  for (int b = 0; b < NBL; ++b) h[b] = q[4 * b];
-#else
   const float* q = slot + 4 * g * 16 + p;
 #pragma unroll
   for (int b = 0; b < NBL; ++b)
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-#if NIF_S6_RING_NT & 2
-      h[b][v] = __builtin_nontemporal_load(q + (16 * b + v) * 16);
-#else
-      h[b][v] = q[(16 * b + v) * 16];
-#endif
-    }
-#endif
+    for (int v = 0; v < 4; ++v) h[b][v] = q[(16 * b + v) * 16];
 }
 
 #ifdef NIF_TIMELINE      // measurement builds: s_memtime stamps of producer wave 0 and consumer wave 8 of block 0, third round -- kept in LDS
@@ -105,45 +58,16 @@ struct S6Args {
   float* partial; long pstride;     // partial-gradient rows [gridDim.x][pstride] (the ShapeNet = hypernetwork columns of them)
 };
 
-#ifndef NIF_S6_RECOMP0
-#define NIF_S6_RECOMP0 1     // the first layer's output (input of hidden matrix 0) is recomputed in the adjoint from the tile's inputs
-                             // (si FMAs + a sine per element) instead of going through the ring: a quarter of the ring traffic less
-#endif
-#ifndef NIF_S6_EARLYDEP
-#define NIF_S6_EARLYDEP 0    // 1 (r5, measured and NOT kept): deposit j is written INSIDE the last chunk step of adjoint layer j (its operands
-                             // are complete after the first one) so that it is visible at that step's barrier and the consumer waves run 5
-                             // of its 8 tiles during the producers' long vector interval of the next layer -- where they idle -- and 3 in
-                             // the chunk step behind it (default: 3 + 3 + 2 in three chunk steps); one barrier per round less.  Parity
-                             // green, 1.268 vs 1.254 ms per step (three same-box pairs): the s_memtime timeline
-                             // (profiles/r05_timeline_earlydep.txt) shows the deposit's ~150 vector instructions costing 1.1 k ticks in
-                             // the chunk step and saving 0.25-0.4 k in the vector block -- both producer waves of a SIMD run them at the
-                             // same moment wherever they stand, and behind the step's matrix instructions they do not overlap its LDS wait
-#endif
-#ifndef NIF_S6_PF
-#define NIF_S6_PF 0
-#endif
-#ifndef NIF_S6_BIGCHUNK
-#define NIF_S6_BIGCHUNK 1    // 1 (r6, exact-product form; brings the NIF_S6_DBAR schedule with it; 0: the r5 form, 2: + the pipelined plane step, measured slower): chunks of 16 KB = a whole plane of a hidden matrix (both K steps), TWO chunk
-                             // steps per layer and direction instead of four: half the per-step fixed costs (DMA issue 170-380 ticks, s_waitcnt
-                             // 140, barrier >= 140, loop glue 120 of a ~1 250-tick forward step: r6 timeline)
-#endif
-#ifndef NIF_S6_EARLYDMA
-#define NIF_S6_EARLYDMA 1    // 1 (r6, with NIF_S6_BIGCHUNK; the product form: 1.154-1.166 vs 1.169-1.185 ms on same-box triples): the chunk DMA of an adjoint layer's second step is issued at the TOP of the
-                             // layer's vector block instead of inside its first chunk step (an LDS-DMA piece costs 25-60 cycles to issue in a
-                             // VALU-only stretch, 100-185 inside a phase with matrix and LDS traffic: MI355X_MICROARCH.md)
-#endif
 #ifndef NIF_S6_DBAR_T0
 #define NIF_S6_DBAR_T0 5     // tiles of the deposit taken under the vector block + the first chunk step (timeline r6: 240 ticks per tile there,
                              // 650 once the producers' matrix instructions compete)
 #endif
-#ifndef NIF_S6_DBAR
-#define NIF_S6_DBAR 0        // 1 (r6): a barrier right BEHIND every hidden deposit (not only deposit 0's): the consumer waves take deposit j
-                             // during the producers' vector block of layer j - 1 (the matrix pipe idles there) and its first chunk step
-                             // (5 + 3 tiles) instead of in chunk steps 1-3 (3 + 3 + 2), where they were the last at every barrier
-#endif
-#ifndef NIF_S6_CONS_PRIO
-#define NIF_S6_CONS_PRIO 0     // s_setprio of the consumer waves
-#endif
+
+// launch geometry, shared by the kernel and the host-side sizes (snet6_rows, snet6_ring_floats): S6_WAVES producer waves (= 16-point
+// tiles per round) per workgroup, at most S6_MAX_WG workgroups, and per producer wave a private h ring of s6_ring(NBL) floats per hidden
+// matrix: [16 NBL features][16 points]
+constexpr int S6_WAVES = 8, S6_MAX_WG = 256;
+constexpr int s6_ring(int NBL) { return 16 * NBL * 16; }
 
 // PR (late r4): the producers' hidden n x n products under a Keras policy -- 1 = mixed_bfloat16 (ONE bf16 product per operand pair),
 // 2 = mixed_float16 (half operands, per-point loss scale on dL/da; k_snet4_dev.h) -- as in k_snet4<.., PR>.  The CONSUMER side is
@@ -154,7 +78,7 @@ template <int NBL, int PR = 0>
 __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   extern __shared__ __attribute__((aligned(256))) char smem6[];
   const SNetArgs& A = F.s;
-  constexpr int NT = 512, WAVES = 8, r = 1;             // producer threads / waves (= tiles per round); 8 consumer waves behind them
+  constexpr int NT = 512, WAVES = S6_WAVES, r = 1;             // producer threads / waves (= tiles per round); 8 consumer waves behind them
   constexpr int NCH = NBL / 2;
   // PR = 0 (r5): fp32-exact products on HALF pairs -- planes (hi, lo) x operand (hi, lo), three v_mfma_f32_16x16x32_f16 per pair in both
   // directions (k_pack16b mode 3, split2h; forward: half of r4's six bf16 products and two thirds of its chunk bytes; adjoint: 22
@@ -164,24 +88,17 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   constexpr int CF = X16 ? NBL * 2 * 64 : NBL * 3 * 64, CB = NBL * 2 * 64;   // 16-byte units per forward / adjoint chunk
   constexpr bool CP = PR != 0;                           // the policies' compact plane set (k_snet4_dev.h): one plane per block
   constexpr int CFH = CP ? NBL * 64 : CF, CBH = CP ? NBL * 64 : CB;
-  constexpr bool BIG = X16 && NIF_S6_BIGCHUNK;
-  static_assert(!NIF_S6_BIGCHUNK || (!NIF_S6_PF && !NIF_S6_EARLYDEP), "NIF_S6_BIGCHUNK: without NIF_S6_PF / NIF_S6_EARLYDEP");
-  constexpr bool DBAR = BIG || (NIF_S6_DBAR != 0);      // a barrier behind every hidden deposit: always with the big chunks (the consumers' only
-                                                        // other window would be ONE chunk step per layer), optional on the 8 KB forms (the policies)
+  // BIG (r6, the exact-product form): chunks of 16 KB = a whole plane of a hidden matrix (both K steps), TWO chunk steps per layer and
+  // direction instead of four: half the per-step fixed costs (DMA issue 170-380 ticks, s_waitcnt 140, barrier >= 140, loop glue 120 of a
+  // ~1 250-tick forward step: r6 timeline).  It brings a barrier behind every hidden deposit with it: the consumers' only other window
+  // would be ONE chunk step per layer.  The policy forms keep 8 KB chunks, four steps per layer
+  constexpr bool BIG = X16;
   constexpr int CFB = BIG ? 2 * CF : CF;                 // units of one chunk BUFFER
   constexpr int QF = (CFB + NT - 1) / NT;
   // (r5: three buffers with the DMA two chunk steps ahead measured no gain -- 1.185 vs 1.15-1.19 ms -- although the s_memtime timeline
   // shows ~300 ticks of every step in front of the barrier's s_waitcnt: tools/exp/k_snet6_3buf.hip, profiles/r05_timeline_*.txt)
-  // r6 (NIF_S6_PF = 1, exact-product form): THREE buffers, the DMA two steps ahead, so that a step can read the first operands of the next
-  // chunk behind its own first products (mfma_x3_pf)
-  constexpr bool PF = X16 && NIF_S6_PF;
-  constexpr int NBUF = PF ? 3 : 2;
+  constexpr int NBUF = 2;
   constexpr int NPL = 6;                                // planes per tile: h (hi, lo), zt h (hi, lo), dL/da (hi, lo)
-#if defined(NIF_ABL_NOSTORE) || defined(NIF_ABL_NOLOAD) || !NIF_S6_RING
-  constexpr int NRING = 0;
-#else
-  constexpr int NRING = NIF_S6_RING_V4 ? NBL : 4 * NBL; // vector-memory instructions of one ring_store16 / ring_load16
-#endif
   constexpr int EXT = NPL * FUSE_PLANE_BYTES;
   // per-tile weight vectors [hi 16 | lo 16] bf16 = 64 B.  Last layer (WVL): du_o (o < 3), zt, ones.  First layer (WVF), per plane k:
   // k * 4 + c = (zt | 1) x_c, k * 4 + 3 = (zt | 1)
@@ -197,7 +114,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   char* WVF = WVL + WAVES * WVLT;
   bf16x8* chunks = reinterpret_cast<bf16x8*>(WVF + WAVES * WVFT);
   float* sm = reinterpret_cast<float*>(chunks + NBUF * CFB);
-  constexpr int NP = 16 * NBL;
+  constexpr int NP = 16 * NBL, RING = s6_ring(NBL);
   // r5: the LDS image of the small hyper-vectors has a FIXED layout -- three first-layer rows, three last-layer rows, the first bias, four
   // hidden biases, the last bias (the shape's unused rows are zeros): every offset into it is a compile-time constant that folds into the
   // ds_read's immediate.  With offsets made of si / so / nh the tile program spent ~300 v_add_u32 per tile on LDS addresses (a tenth of
@@ -206,7 +123,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   constexpr int sm_tot = ((r + 1) * nsm + 3) & ~3;
   // r6: the input set of a tile is EIGHT rows of 16 points -- x_0..x_2 | z | y_0..y_2 | sample weight (si, so <= 3, r = 1: snet6_supported) --
   // fetched by TWO LDS-DMA instructions whose lane groups point at different arrays (r5: sixteen rows, four instructions, most of them
-  // duplicates): 8 KB of LDS back per workgroup -- what the 16 KB chunk buffers of NIF_S6_BIGCHUNK need
+  // duplicates): 8 KB of LDS back per workgroup -- what the 16 KB chunk buffers of BIG need
   constexpr int CX = 3, CZ = 1, CY = 3;
   constexpr int NI = (CX + CZ + CY + 1) * 16;
   constexpr int pw = 2 * r * 64 + 2 * NI;               // per-wave LDS floats (producers)
@@ -285,7 +202,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
       reinterpret_cast<__bf16*>(WVL + t * WVLT)[4 * 32 + q] = (__bf16)1.0f;
       reinterpret_cast<__bf16*>(WVF + t * WVFT)[7 * 32 + q] = (__bf16)1.0f;
     }
-    __builtin_amdgcn_s_setprio(NIF_S6_CONS_PRIO);
+    __builtin_amdgcn_s_setprio(0);
     f32x16 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -339,42 +256,29 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
       ah_ = ah2_; al_ = al2_; bh_ = bh2_; bl_ = bl2_;                                                       \
     }                                                                                                       \
   }
-    // the four chunk steps of an adjoint layer with the consumption of hidden deposit DJ_ (a compile-time index: the accumulators
-    // are never selected at run time -- a switch over them made hipcc copy and spill whole accumulators around every call)
-#if NIF_S6_EARLYDEP
-#define S6_HID_LAYER(DJ_)      /* entered behind the barrier of the step that deposited DJ_ */              \
+    // the chunk steps of an adjoint layer with the consumption of hidden deposit DJ_ (a compile-time index: the accumulators
+    // are never selected at run time -- a switch over them made hipcc copy and spill whole accumulators around every call).
+    // BIG: entered in front of the barrier behind deposit DJ_ -- NIF_S6_DBAR_T0 tiles under the producers' vector block of layer DJ_ - 1
+    // (the matrix pipe idles there) and its first chunk step, the rest in the second; else in front of the first chunk barrier of
+    // layer DJ_ - 1, 3 + 3 + 2 tiles over its chunk steps 1-3
+#define S6_HID_LAYER(DJ_)                                                                                   \
   if (DJ_ < nh) {                                                                                           \
-    S6_DO(S6_HID_TILES(DJ_, 0, 5))                                                                          \
-    S6_CBAR()                                                                                               \
-    S6_DO(S6_HID_TILES(DJ_, 5, 8))                                                                          \
-    S6_CBAR()                                                                                               \
-    S6_CBAR()                                                                                               \
-    S6_CBAR()                                                                                               \
-  }
-#else
-#define S6_HID_LAYER(DJ_)      /* DBAR: entered in front of the barrier behind deposit DJ_; else in front of the first chunk barrier of layer DJ_ - 1 */ \
-  if (DJ_ < nh) {                                                                                           \
-    if (DBAR) {                                                                                             \
+    if (BIG) {                                                                                              \
       S6_CBAR()                                                                                             \
-      S6_DO(S6_HID_TILES(DJ_, 0, NIF_S6_DBAR_T0))                                                           \
+      S6_HID_TILES(DJ_, 0, NIF_S6_DBAR_T0)                                                                  \
       S6_CBAR()                                                                                             \
-      S6_DO(S6_HID_TILES(DJ_, NIF_S6_DBAR_T0, 8))                                                           \
+      S6_HID_TILES(DJ_, NIF_S6_DBAR_T0, 8)                                                                  \
       S6_CBAR()                                                                                             \
-      if (!BIG) {                                                                                           \
-        S6_CBAR()                                                                                           \
-        S6_CBAR()                                                                                           \
-      }                                                                                                     \
     } else {                                                                                                \
       S6_CBAR()                                                                                             \
-      S6_DO(S6_HID_TILES(DJ_, 0, 3))                                                                        \
+      S6_HID_TILES(DJ_, 0, 3)                                                                               \
       S6_CBAR()                                                                                             \
-      S6_DO(S6_HID_TILES(DJ_, 3, 6))                                                                        \
+      S6_HID_TILES(DJ_, 3, 6)                                                                               \
       S6_CBAR()                                                                                             \
-      S6_DO(S6_HID_TILES(DJ_, 6, 8))                                                                        \
+      S6_HID_TILES(DJ_, 6, 8)                                                                               \
       S6_CBAR()                                                                                             \
     }                                                                                                       \
   }
-#endif
     // last layer (h_nh, zt h_nh deposited as the A planes, du_o as vectors).  The skinny sums run as ROLLED loops over the tiles:
     // unrolled, hipcc fetched the weight vectors of all tiles first and spilled the accumulators to make room
     auto consume_last = [&](int t0, int t1) __attribute__((always_inline)) {
@@ -415,21 +319,14 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         }
       }
     };
-#ifdef NIF_S6_NOCONS
-#define S6_DO(...)
-#else
-#define S6_DO(...) __VA_ARGS__
-#endif
     // the barrier sequence of the producers' tile program, with this wave's share of the products between the barriers
     if (cs_left <= 0) cs_left = -1;
     cs_next(0, false);                      // (chunk 0: issued by the producers in their prologue)
     int nb_c = 1;
-    if (PF) { cs_next(1, false); nb_c = 2; }     // (PF: chunk 1 too; a step issues the chunk two steps ahead)
-#define S6_ROTC() { if (PF) nb_c = nb_c == 2 ? 0 : nb_c + 1; else nb_c ^= 1; }
     // a forward interval: this wave's slice of the NEXT step's chunk goes out first and has landed in front of the barrier
 #define S6_CFWD(...)                                                          \
   {                                                                           \
-    cs_next(nb_c, true); S6_ROTC()                                            \
+    cs_next(nb_c, true); nb_c ^= 1;                                           \
     __VA_ARGS__                                                               \
     __builtin_amdgcn_s_waitcnt(0x0070);        /* vmcnt(0) lgkmcnt(0) */      \
     S6_TL(400);                                                               \
@@ -445,58 +342,45 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         // skinny sums are rolled, latency-bound loops; spread over all 2 nh - 1 intervals behind the first they hide under the producers' steps)
         const int nq = 2 * nh - 1;
         for (int j = 0; j < nh; ++j) {
-          S6_CFWD(if (j > 0) { const int q_ = 2 * j - 1; S6_DO(consume_first(q_ * 8 / nq, (q_ + 1) * 8 / nq);) })
-          S6_CFWD({ const int q_ = 2 * j; S6_DO(consume_first(q_ * 8 / nq, (q_ + 1) * 8 / nq);) })
+          S6_CFWD(if (j > 0) { const int q_ = 2 * j - 1; consume_first(q_ * 8 / nq, (q_ + 1) * 8 / nq); })
+          S6_CFWD({ const int q_ = 2 * j; consume_first(q_ * 8 / nq, (q_ + 1) * 8 / nq); })
         }
-        for (int q = 0; q < (r + 1) * nh; ++q) { cs_next(nb_c, false); S6_ROTC() }
+        for (int q = 0; q < (r + 1) * nh; ++q) { cs_next(nb_c, false); nb_c ^= 1; }
         S6_CBAR()                              // behind the last layer's deposit
-        S6_DO(consume_last(0, 5);)
+        consume_last(0, 5);
         S6_CBAR()                              // first chunk step of adjoint layer nh - 1
-        S6_DO(consume_last(5, 8);)
+        consume_last(5, 8);
         S6_CBAR()                              // second
         S6_HID_LAYER(3) S6_HID_LAYER(2) S6_HID_LAYER(1)
         S6_CBAR()                              // deposit 0 next to the first layer's adjoint
-        S6_DO(S6_HID_TILES(0, 0, 8))
+        S6_HID_TILES(0, 0, 8)
         S6_CBAR()
         continue;
       }
       for (int j = 0; j < nh; ++j) {        // forward: the previous round's first-layer deposit next to hidden matrix 0
         S6_CFWD()
-        S6_CFWD(if (j == 0) { S6_DO(consume_first(0, 3);) })      // (three intervals: at four tiles the consumers were the last at these barriers, r5 timeline)
-        S6_CFWD(if (j == 0) { S6_DO(consume_first(3, 6);) })
-        S6_CFWD(if (j == 0) { S6_DO(consume_first(6, 8);) })
+        S6_CFWD(if (j == 0) { consume_first(0, 3); })      // (three intervals: at four tiles the consumers were the last at these barriers, r5 timeline)
+        S6_CFWD(if (j == 0) { consume_first(3, 6); })
+        S6_CFWD(if (j == 0) { consume_first(6, 8); })
       }
-      for (int q = 0; q < 4 * nh; ++q) { cs_next(nb_c, false); S6_ROTC() }      // (the adjoint steps' chunks: the producers issue them)
+      for (int q = 0; q < 4 * nh; ++q) { cs_next(nb_c, false); nb_c ^= 1; }      // (the adjoint steps' chunks: the producers issue them)
       // adjoint: the last layer's deposit next to the steps of layer nh - 1, then deposit j + 1 next to layer j
-#if NIF_S6_EARLYDEP
       S6_CBAR()
-      S6_DO(consume_last(0, 4);)
+      consume_last(0, 3);
       S6_CBAR()
-      S6_DO(consume_last(4, 8);)
-      S6_CBAR()                              // (the producers write deposit nh - 1 over the last layer's during this step)
+      consume_last(3, 6);
       S6_CBAR()
-      S6_HID_LAYER(3) S6_HID_LAYER(2) S6_HID_LAYER(1)
-      S6_DO(S6_HID_TILES(0, 0, 8))           // deposit 0 (visible since the last chunk barrier) next to the first layer's adjoint
-      S6_CBAR()
-#else
-      S6_CBAR()
-      S6_DO(consume_last(0, 3);)
-      S6_CBAR()
-      S6_DO(consume_last(3, 6);)
-      S6_CBAR()
-      S6_DO(consume_last(6, 8);)
+      consume_last(6, 8);
       S6_CBAR()
       S6_HID_LAYER(3) S6_HID_LAYER(2) S6_HID_LAYER(1)
       S6_CBAR()                              // deposit 0 next to the first layer's adjoint
-      S6_DO(S6_HID_TILES(0, 0, 8))
+      S6_HID_TILES(0, 0, 8)
       S6_CBAR()
-#endif
     }
     __syncthreads();
-    S6_DO(consume_first(0, 8);)
+    consume_first(0, 8);
     __syncthreads();
 #undef S6_CFWD
-#undef S6_DO
 #undef S6_HID_LAYER
 #undef S6_HID_TILES
 #undef S6_HID_LOAD
@@ -579,19 +463,13 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   prefetch_inputs(blockIdx.x, 0);
   if (cs_left <= 0) cs_left = -1;
   cs_next(0, true);
-  if (PF) cs_next(1, true);
   __syncthreads();
   bool dma_mine = false;                                 // forward steps: the consumer waves issue the chunk DMA
-  bool dma_early = false;                                // NIF_S6_EARLYDMA: the next S6_CHUNK's DMA went out already
-  int cbuf = 0, nbuf = PF ? 2 : 1;
-  bf16x8 pf[4]; (void)pf;                                // PF: the next chunk's first block pair (live inside a layer's four steps only)
-#define S6_ROT() { if (PF) { cbuf = cbuf == 2 ? 0 : cbuf + 1; nbuf = nbuf == 2 ? 0 : nbuf + 1; } else { cbuf ^= 1; nbuf ^= 1; } }
+  bool dma_early = false;                                // the next S6_CHUNK's DMA went out already (BIG adjoint layers)
+  int cbuf = 0, nbuf = 1;
   int tlc = 0, tlr = 0; (void)tlc; (void)tlr;
   float loss_lane = 0.f;
-  const long sstride = A.slot_stride, tstride = (long)stash_fp(n) * 32;
-  float* IN0 = A.stash;
-  float* ring = A.stash + ((long)blockIdx.x * WAVES + wid) * (long)nh * (NP * 16);    // NIF_S6_RING: [matrix][NP features][16 points]
-  (void)ring; (void)IN0; (void)sstride; (void)tstride;
+  float* ring = A.stash + ((long)blockIdx.x * WAVES + wid) * (long)nh * RING;    // [matrix][NP features][16 points]
   const FuseDep dep = fuse_dep_addr(p, g);
   char* exw = EX + wid * EXT;                            // this wave's tile images
 
@@ -610,72 +488,11 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
     __builtin_amdgcn_s_barrier();                                             \
     asm volatile("" ::: "memory");                                            \
     S6_TL(500);                                                               \
-    S6_ROT()                                                                  \
-  }
-// r6 (NIF_S6_PRE): the exact-product steps read the first block pair's A operands IN FRONT of the next chunk's DMA issue -- the issue
-// (60-180 cycles per piece, MI355X_MICROARCH.md) then overlaps the LDS latency of the reads the step's first MFMAs wait for
-#ifndef NIF_S6_PRE
-#define NIF_S6_PRE 0
-#endif
-#define S6_CHUNKP(ZI_, B0_, B1_, T_)                                          \
-  {                                                                           \
-    S6_TL(100);                                                               \
-    const bf16x8* cur = chunks + cbuf * CFB;                                  \
-    const bf16x8 pa_[4] = {cur[lane], cur[64 + lane], cur[128 + lane], cur[192 + lane]};   \
-    __builtin_amdgcn_sched_barrier(0);                                        \
-    cs_next(nbuf, dma_mine);                                                  \
-    S6_TL(200);                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                        \
-    mfma_x3_pre<NBL, ZI_>(cur, pa_, B0_, B1_, T_, lane);                      \
-    S6_TL(300);                                                               \
-    __builtin_amdgcn_s_waitcnt(0x0070);                                       \
-    S6_TL(400);                                                               \
-    asm volatile("" ::: "memory");                                            \
-    __builtin_amdgcn_s_barrier();                                             \
-    asm volatile("" ::: "memory");                                            \
-    S6_TL(500);                                                               \
-    S6_ROT()                                                                  \
+    cbuf ^= 1; nbuf ^= 1;                                                     \
   }
 // BIG: one step = a whole plane (two K-step halves of the 16 KB chunk)
 #define S6_CHUNK2(ZI_, Q0_, Q1_, T_)                                          \
-  S6_CHUNK({ if (NIF_S6_BIGCHUNK == 2) mfma_x3_plane<NBL, ZI_, CF>(cur, Q0_, Q1_, T_, lane); else { mfma_x3<NBL, 3, ZI_, NBL, 0, false>(cur, Q0_[0], Q1_[0], T_, lane); mfma_x3<NBL, 3, false, NBL, 0, false>(cur + CF, Q0_[1], Q1_[1], T_, lane); } })
-#define S6_CHUNKF(USE_, MAKE_, ZI_, B0_, B1_, T_)                             \
-  {                                                                           \
-    S6_TL(100);                                                               \
-    cs_next(nbuf, dma_mine);                                                  \
-    S6_TL(200);                                                               \
-    const bf16x8* cur = chunks + cbuf * CFB;                                  \
-    const bf16x8* nxt = chunks + (cbuf == 2 ? 0 : cbuf + 1) * CF;             \
-    mfma_x3_pf<NBL, ZI_, USE_, MAKE_>(cur, nxt, pf, B0_, B1_, T_, lane);      \
-    S6_TL(300);                                                               \
-    __builtin_amdgcn_s_waitcnt(0x0070);                                       \
-    S6_TL(400);                                                               \
-    asm volatile("" ::: "memory");                                            \
-    __builtin_amdgcn_s_barrier();                                             \
-    asm volatile("" ::: "memory");                                            \
-    S6_TL(500);                                                               \
-    S6_ROT()                                                                  \
-  }
-// the chunk step that carries the layer's ring traffic: the NRING ring instructions are issued BEHIND the next chunk's DMA, so the
-// wait at the end of the step may leave exactly them in flight (vmcnt counts in issue order: "at most NRING outstanding" = every
-// DMA instruction has landed) -- their latency gets the following chunk step as well instead of sitting in front of this barrier
-#if NIF_S6_VMRING
-#define S6_CHUNK_RING(PRE_, ...)                                              \
-  {                                                                           \
-    cs_next(nbuf, dma_mine);                                                  \
-    PRE_                                                                      \
-    asm volatile("" ::: "memory");                                            \
-    const bf16x8* cur = chunks + cbuf * CFB;                                  \
-    __VA_ARGS__                                                               \
-    __builtin_amdgcn_s_waitcnt(0x0070 | (NRING & 15) | ((NRING >> 4) << 14));   /* vmcnt(NRING) lgkmcnt(0) */ \
-    asm volatile("" ::: "memory");                                            \
-    __builtin_amdgcn_s_barrier();                                             \
-    asm volatile("" ::: "memory");                                            \
-    S6_ROT()                                                                  \
-  }
-#else
-#define S6_CHUNK_RING(PRE_, ...) { PRE_ S6_CHUNK(__VA_ARGS__) }
-#endif
+  S6_CHUNK({ mfma_x3<NBL, 3, ZI_, NBL, 0, false>(cur, Q0_[0], Q1_[0], T_, lane); mfma_x3<NBL, 3, false, NBL, 0, false>(cur + CF, Q0_[1], Q1_[1], T_, lane); })
 
   int iset = 0;
   for (long tg = blockIdx.x; tg < ngroups; tg += gridDim.x, ++iset, ++tlr) {
@@ -692,8 +509,6 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
     const float* ys = zs + CZ * 16 + p;
     const float* wsp = zs + (CZ + CY) * 16 + p;
     const float* zt_base = zs + p;
-    const long row0 = tile32 * tstride + poff;
-    (void)row0;
     dzs[lane] = 0.f;
 
     f32x4 h[NBL], acc[NBL];
@@ -726,9 +541,6 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
     // ---- hidden hyper-matrices, forward ---------------------------------------------------------------------------------------
     dma_mine = false;
     for (int j = 0; j < nh; ++j) {
-#if !NIF_S6_RING
-      if (active) st_store16<NBL>(IN0 + (long)j * sstride, row0, h, g);
-#endif
       bf16x8 b0[NCH], b1[NCH], b2[NCH];
       if (X16) split2h<NBL>(h, 4096.0f, b0, b1);
       else split3p<NBL, PR>(h, b0, b1, b2);
@@ -743,31 +555,23 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         const float* sb = sm + o_bh + j * NP + 4 * g;
 #pragma unroll
         for (int b = 0; b < NBL; ++b) T[b] = *reinterpret_cast<const f32x4*>(sb + 16 * b);
-#if NIF_S6_RING
-#define S6_FWD(KS_, T_) { if (X16) mfma_x3<NBL, 3, false, NBL, 0, false>(cur, b0[KS_], b1[KS_], T_, lane); else mfma_x6<NBL, PR, false, NBL, 0, CP>(cur, b0[KS_], b1[KS_], b2[KS_], T_, lane); }
-        if (BIG) {
-          if (!NIF_S6_RECOMP0 || j > 0) ring_store16<NBL>(ring + j * (NP * 16), h, g, p);
-          S6_CHUNK2(false, b0, b1, T)
-        } else if (PF) {
-          if (!NIF_S6_RECOMP0 || j > 0) ring_store16<NBL>(ring + j * (NP * 16), h, g, p);
-          S6_CHUNKF(false, true, false, b0[0], b1[0], T)
-        } else S6_CHUNK_RING({ if (!NIF_S6_RECOMP0 || j > 0) ring_store16<NBL>(ring + j * (NP * 16), h, g, p); }, S6_FWD(0, T))
-#else
-        S6_CHUNK(S6_FWD(0, T))
-#endif
-        if (BIG) { }
-        else if (PF) S6_CHUNKF(true, true, false, b0[1], b1[1], T)
-        else S6_CHUNK(S6_FWD(1, T))
+#define S6_FWD(KS_, T_) mfma_x6<NBL, PR, false, NBL, 0, CP>(cur, b0[KS_], b1[KS_], b2[KS_], T_, lane);      // (the policy forms: 8 KB chunks)
+        // h_0 is not stored: the adjoint recomputes it from the tile's inputs (si FMAs + a sine per element), a quarter of the ring traffic less
+        if (j > 0) ring_store16<NBL>(ring + j * RING, h, g, p);
+        if (BIG) S6_CHUNK2(false, b0, b1, T)
+        else {
+          S6_CHUNK(S6_FWD(0, T))
+          S6_CHUNK(S6_FWD(1, T))
+        }
         const float zt = X16 ? zt_base[0] * (s1_ * is0_) : zt_base[0];      // (plane 0's chain carries s0, the sum s1)
 #pragma unroll
         for (int b = 0; b < NBL; ++b) acc[b] += zt * T[b];
       }
       if (BIG) S6_CHUNK2(false, b0, b1, acc)
-      else if (PF) S6_CHUNKF(true, true, false, b0[0], b1[0], acc)
-      else S6_CHUNK(S6_FWD(0, acc))
-      if (BIG) { }
-      else if (PF) S6_CHUNKF(true, false, false, b0[1], b1[1], acc)
-      else S6_CHUNK(S6_FWD(1, acc))
+      else {
+        S6_CHUNK(S6_FWD(0, acc))
+        S6_CHUNK(S6_FWD(1, acc))
+      }
 #undef S6_FWD
       if (X16) sine16_tag_sc<NBL>(acc, acc, is1_ * (1.0f / 4096.0f));
       else sine16_tag<NBL>(acc, acc);
@@ -854,11 +658,10 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
     dma_mine = true;
     for (int j = nh - 1; j >= 0; --j) {
       f32x4 ga[NBL];
-      if (BIG && NIF_S6_EARLYDMA) { cs_next(nbuf, true); dma_early = true; }
+      // BIG: the chunk DMA of the layer's second step goes out at the TOP of its vector block instead of inside its first chunk step (an
+      // LDS-DMA piece costs 25-60 cycles to issue in a VALU-only stretch, 100-185 inside a phase with matrix and LDS traffic: MI355X_MICROARCH.md)
+      if (BIG) { cs_next(nbuf, true); dma_early = true; }
       tag_cos<NBL>(hin, dnext);
-#if !NIF_S6_RING
-      st_load16<NBL>(IN0 + (long)j * sstride, row0, hin, g);
-#endif
 #pragma unroll
       for (int b = 0; b < NBL; ++b) ga[b] = dnext[b] * gh[b];
       {
@@ -873,8 +676,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         dzs[lane] += X16 ? sbv * (scl[j * 4 + 1] * (1.0f / 4096.0f)) : sbv;     // (the LDS image holds 4096 s0 b^(0))
       }
       bf16x8 b0[NCH], b1[NCH];
-      constexpr bool LATE_SPLIT = X16 && NIF_S6_EARLYDEP;   // the deposit's pair is formed where it is deposited (dL/da stays live instead of it: same registers)
-      if (!LATE_SPLIT) split2<NBL>(ga, b0, b1);             // the deposit's (hi, lo) pair; b0 is also the bf16 policy's operand
+      split2<NBL>(ga, b0, b1);                // the deposit's (hi, lo) pair; b0 is also the bf16 policy's operand
       bf16x8 q0[NCH], q1[NCH];                // the products' operand: b0, or half(s dL/da), s per point (mixed_float16: hi alone; X16: (hi, lo))
       const float s1_ = X16 ? scl[j * 4 + 2] : 1.0f, is0_ = X16 ? scl[j * 4 + 1] : 1.0f, is1_ = X16 ? scl[j * 4 + 3] : 1.0f;
       float ils = 1.0f;
@@ -897,24 +699,15 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
 #pragma unroll
         for (int ks = 0; ks < NCH; ++ks) q1[ks] = b1[ks];
       }
-      constexpr int PB = X16 ? 3 : PR;
       {
         f32x4 U[NBL];
-#if NIF_S6_RING     // h_j (dz dot product, this layer's A planes, the cosine of the layer below) -- dnext was taken from hin above
-        if (BIG) {
-          if (NIF_S6_RECOMP0 && j == 0) first_layer(hin); else ring_load16<NBL>(ring + j * (NP * 16), hin, g, p);
-          S6_CHUNK2(true, q0, q1, U)
-        } else if (PF) {
-          if (NIF_S6_RECOMP0 && j == 0) first_layer(hin); else ring_load16<NBL>(ring + j * (NP * 16), hin, g, p);
-          S6_CHUNKF(false, true, true, q0[0], q1[0], U)
-        } else S6_CHUNK_RING({ if (NIF_S6_RECOMP0 && j == 0) first_layer(hin); else ring_load16<NBL>(ring + j * (NP * 16), hin, g, p); }, { mfma_x3<NBL, PB, true, NBL, 0, CP>(cur, q0[0], q1[0], U, lane); })
-#else
-        S6_CHUNK({ mfma_x3<NBL, PB, true, NBL, 0, CP>(cur, q0[0], q1[0], U, lane); })
-#endif
-        if (BIG) { }
-        else if (PF) S6_CHUNKF(true, true, false, q0[1], q1[1], U)
-        else if (X16 && NIF_S6_PRE) S6_CHUNKP(false, q0[1], q1[1], U)
-        else S6_CHUNK({ mfma_x3<NBL, PB, false, NBL, 0, CP>(cur, q0[1], q1[1], U, lane); })
+        // h_j (dz dot product, this layer's A planes, the cosine of the layer below) -- dnext was taken from hin above
+        if (j == 0) first_layer(hin); else ring_load16<NBL>(ring + j * RING, hin, g, p);
+        if (BIG) S6_CHUNK2(true, q0, q1, U)
+        else {
+          S6_CHUNK({ mfma_x3<NBL, PR, true, NBL, 0, CP>(cur, q0[0], q1[0], U, lane); })
+          S6_CHUNK({ mfma_x3<NBL, PR, false, NBL, 0, CP>(cur, q0[1], q1[1], U, lane); })
+        }
         float s = 0.f;
 #pragma unroll
         for (int b = 0; b < NBL; ++b)
@@ -925,46 +718,33 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         for (int b = 0; b < NBL; ++b) gh[b] = ztc * U[b];
         dzs[lane] += X16 ? (ils * is0_) * s : (PR == 2 ? ils * s : s);
       }
-      // deposit j: (h_j ; zt h_j ; dL/da) of this tile -- the consumer waves take it during the steps of layer j - 1
-#define S6_DEPOSIT()                                                          \
-      {                                                                       \
-        if (LATE_SPLIT) split2<NBL>(ga, b0, b1);                              \
-        fuse_deposit4(exw + 4 * FUSE_PLANE_BYTES, dep, b0);                   \
-        fuse_deposit4(exw + 5 * FUSE_PLANE_BYTES, dep, b1);                   \
-        bf16x8 a0[NCH], a1[NCH];                                              \
-        split2<NBL>(hin, a0, a1);                                             \
-        fuse_deposit4(exw, dep, a0);                                          \
-        fuse_deposit4(exw + FUSE_PLANE_BYTES, dep, a1);                       \
-        f32x4 zh[NBL];                                                        \
-        _Pragma("unroll") for (int b = 0; b < NBL; ++b) zh[b] = zt0 * hin[b]; \
-        split2<NBL>(zh, a0, a1);                                              \
-        fuse_deposit4(exw + 2 * FUSE_PLANE_BYTES, dep, a0);                   \
-        fuse_deposit4(exw + 3 * FUSE_PLANE_BYTES, dep, a1);                   \
-      }
       if (BIG) S6_CHUNK2(false, q0, q1, gh)
-      else if (PF) S6_CHUNKF(true, true, false, q0[0], q1[0], gh)
-      else if (X16 && NIF_S6_PRE) S6_CHUNKP(false, q0[0], q1[0], gh)
-      else S6_CHUNK({ mfma_x3<NBL, PB, false, NBL, 0, CP>(cur, q0[0], q1[0], gh, lane); })
-#if NIF_S6_EARLYDEP
-      // (the slot's previous deposit was consumed two barriers ago; the splits run behind this step's matrix instructions)
-      S6_CHUNK({ mfma_x3<NBL, PB, false, NBL, 0, CP>(cur, q0[1], q1[1], gh, lane); S6_DEPOSIT() })
-#else
-      if (BIG) { }
-      else if (PF) S6_CHUNKF(true, false, false, q0[1], q1[1], gh)
-      else if (X16 && NIF_S6_PRE) S6_CHUNKP(false, q0[1], q1[1], gh)
-      else S6_CHUNK({ mfma_x3<NBL, PB, false, NBL, 0, CP>(cur, q0[1], q1[1], gh, lane); })
-#endif
+      else {
+        S6_CHUNK({ mfma_x3<NBL, PR, false, NBL, 0, CP>(cur, q0[0], q1[0], gh, lane); })
+        S6_CHUNK({ mfma_x3<NBL, PR, false, NBL, 0, CP>(cur, q0[1], q1[1], gh, lane); })
+      }
       if (PR == 2 || X16) {
         const float f_ = X16 ? ils * is1_ : ils;
 #pragma unroll
         for (int b = 0; b < NBL; ++b) gh[b] *= f_;
       }
-#if !NIF_S6_EARLYDEP
-      S6_DEPOSIT()
-#endif
-#undef S6_DEPOSIT
-#if !NIF_S6_EARLYDEP
-      if (DBAR && j > 0) {      // deposit j is visible NOW: the consumers start on it under this wave's next vector block
+      {     // deposit j: (h_j ; zt h_j ; dL/da) of this tile -- the consumer waves take it during the steps of layer j - 1
+        fuse_deposit4(exw + 4 * FUSE_PLANE_BYTES, dep, b0);
+        fuse_deposit4(exw + 5 * FUSE_PLANE_BYTES, dep, b1);
+        bf16x8 a0[NCH], a1[NCH];
+        split2<NBL>(hin, a0, a1);
+        fuse_deposit4(exw, dep, a0);
+        fuse_deposit4(exw + FUSE_PLANE_BYTES, dep, a1);
+        f32x4 zh[NBL];
+#pragma unroll
+        for (int b = 0; b < NBL; ++b) zh[b] = zt0 * hin[b];
+        split2<NBL>(zh, a0, a1);
+        fuse_deposit4(exw + 2 * FUSE_PLANE_BYTES, dep, a0);
+        fuse_deposit4(exw + 3 * FUSE_PLANE_BYTES, dep, a1);
+      }
+      // BIG: deposit j is visible NOW, the consumers start on it under this wave's next vector block (where the matrix pipe idles) and
+      // its first chunk step (NIF_S6_DBAR_T0 + 3 tiles) instead of in chunk steps 1-3 (3 + 3 + 2), where they were the last at every barrier
+      if (BIG && j > 0) {
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
         S6_TL(600);
@@ -972,14 +752,11 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         asm volatile("" ::: "memory");
         S6_TL(700);
       }
-#endif
     }
-#if !NIF_S6_EARLYDEP
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): the deposits have landed
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#endif
     // ---- first layer (the consumer waves take deposit 0 meanwhile) ------------------------------------------------------------
     {
       f32x4 ga[NBL];
@@ -1037,7 +814,8 @@ static size_t snet6_shmem(const SNetArgs& a, int NBL) {
   const size_t sm_tot = (((size_t)(a.r + 1) * (11 * 16 * NBL + 4)) + 3) & ~(size_t)3;      // (the kernel's fixed small-vector layout)
   const size_t ni = 8 * 16;      // (the kernel's input set: x_0..x_2 | z | y_0..y_2 | sample weight, 16 points each)
   const size_t pw = 2 * a.r * 64 + 2 * ni;
-  return 8 * (6 * FUSE_PLANE_BYTES + (5 + 8) * 64) + (size_t)((a.prec == 0 && NIF_S6_PF) ? 3 : 2) * ((a.prec == 0 && NIF_S6_BIGCHUNK) ? 2 : 1) * NBL * (a.prec == 0 ? 2 : 3) * 64 * 16 + (sm_tot + 8 * pw + 16 + 16) * sizeof(float)
+  const size_t chunk = (size_t)(a.prec == 0 ? 2 : 1) * NBL * (a.prec == 0 ? 2 : 3) * 64 * 16;      // (one chunk buffer: BIG holds a whole plane)
+  return 8 * (6 * FUSE_PLANE_BYTES + (5 + 8) * 64) + 2 * chunk + (sm_tot + 8 * pw + 16 + 16) * sizeof(float)
 #ifdef NIF_TIMELINE
          + 2 * 380 * 8
 #endif
@@ -1054,12 +832,16 @@ bool snet6_supported(const SNetArgs& a) {
   if (a.prec == 0 && (!a.WF4x || !a.WB4x || !a.wscale)) return false;
   return snet6_shmem(a, 4) <= 160u * 1024u;
 }
-// workgroups = partial-gradient rows = loss partials of the launch
-int snet6_rows(const SNetArgs& a) {
-  const long nt16 = 2 * ((a.B + 31) / 32);
-  const long ngroups = (nt16 + 7) / 8;
-  return (int)(ngroups < 256 ? ngroups : 256);
+static long s6_workgroups(long B) {
+  const long nt16 = 2 * ((B + 31) / 32);
+  const long ngroups = (nt16 + S6_WAVES - 1) / S6_WAVES;
+  return ngroups < S6_MAX_WG ? ngroups : S6_MAX_WG;
 }
+// workgroups = partial-gradient rows = loss partials of the launch
+int snet6_rows(const SNetArgs& a) { return (int)s6_workgroups(a.B); }
+// floats of the h rings of a launch over B points (the kernel writes them into the ShapeNet stash): EVERY producer wave of a workgroup
+// writes its slice, active or not
+long snet6_ring_floats(long B, int nh) { return s6_workgroups(B) * S6_WAVES * nh * s6_ring(4); }
 int launch_snet6(const SNetArgs& a, float* partial, long pstride, hipStream_t st) {
   const int nblk = snet6_rows(a);
   S6Args f; f.s = a; f.partial = partial; f.pstride = pstride;

@@ -185,11 +185,7 @@ __global__ __launch_bounds__(64 * NIF_SOBW_WMAX(NBL), (NBL <= 4 ? NIF_SOBW_OCC :
   int cbuf = 0, nbuf = 1;
   float loss_lane = 0.f;
   // a'_d of hidden layer j (tangent waves): ring tile j of this wave
-#ifdef NIF_ABL_NORING      // measurement builds: every workgroup on the same ring tiles (cache resident; results are wrong)
-  const long ring_wg = 0;
-#else
   const long ring_wg = blockIdx.x;
-#endif
   f32x4* ring = reinterpret_cast<f32x4*>(J.ring) + (ring_wg * (WAVES - TPG) + (wid >= TPG ? wid - TPG : 0)) * (long)nh * (NBL * 64) + lane;
   // MODE 2: (c, -f'') of layer l (0 = first) of this primal wave's tile: tiles ((l * 2 + which) * NBL + b) * 64, behind every
   // workgroup's tangent rings (the buffer holds 20 (nh + 1) tiles per workgroup: (WAVES - TPG) nh + 2 TPG (nh + 1) are used)

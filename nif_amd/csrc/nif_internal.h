@@ -220,6 +220,7 @@ bool sob_writes_da_bf16(const SNetArgs& a, int ns, bool any_par);   // same for 
 // loss partial per workgroup; no dL/da stash, no k_gw_* launches
 bool snet6_supported(const SNetArgs& a);
 int snet6_rows(const SNetArgs& a);
+long snet6_ring_floats(long B, int nh);
 int launch_snet6(const SNetArgs& a, float* partial, long pstride, hipStream_t st);
 int snet4_nsm_ll(int si, int sop, int nh, int n, int sou, int rl);
 // Sobolev step (k_sob.hip): primal + tangents w.r.t. `ns` coordinate seeds, loss mse(u,y) + wj*mse(du/dx,gt), adjoint
@@ -390,9 +391,9 @@ void launch_tiles_to_rows(const float* tiles, long B, int c, float* rows, hipStr
 #ifdef __HIPCC__
 __device__ __forceinline__ int fmap(int v, int hf) { return 8 * (v >> 2) + 4 * hf + (v & 3); }
 
-// sin and cos of x in one go: 3-term Cody-Waite reduction by pi/2 (exact products via fma) and the
-// cephes single-precision minimax kernels on [-pi/4, pi/4].  Max abs error 1.1e-7 for |x| < 2^20
-// (checked against fp64 on 2e6 samples per decade); larger arguments reduce in double precision.
+// the cephes single-precision minimax kernels of sin and cos on [-pi/4, pi/4], quadrant q: nif_sincosf_big reduces a large
+// argument by pi/2 in double precision and finishes here.  (Behind a 3-term Cody-Waite reduction in fp32 the pair measured max
+// abs error 1.1e-7 for |x| < 2^20 against fp64, 2e6 samples per decade.)
 __device__ __forceinline__ void nif_sincos_poly(float r, int q, float* sp, float* cp) {
   const float r2 = r * r;
   float ps = fmaf(r2, -1.9515295891e-4f, 8.3321608736e-3f);
@@ -406,15 +407,11 @@ __device__ __forceinline__ void nif_sincos_poly(float r, int q, float* sp, float
   *sp = (q & 2) ? -ss : ss;
   *cp = ((q + 1) & 2) ? -cc : cc;
 }
-#ifndef NIF_HW_SINCOS
-#define NIF_HW_SINCOS 1
-#endif
-#if NIF_HW_SINCOS
 // Fast path: v_sin_f32 / v_cos_f32 take their argument in REVOLUTIONS; the reduction f = x/2pi - rint(x/2pi)
 // is done with two fmas against a hi/lo split of 1/2pi (the first fma is exact up to its single rounding, so
 // |f| <= 0.5 carries <= 2^-25 rev = 1.9e-7 rad).  Measured on MI355X against fp64 (tools/exp/hw_sincos.hip,
 // 4M samples per range, |x| <= 0.5 ... 1e6): max abs error 2.6e-7, rms 5.3e-8 -- the same as fp32 rounding of the
-// result, and ~2.3x fewer VALU issue cycles than the polynomial kernels below (2 quarter-rate + 4 full-rate ops).
+// result, and ~2.3x fewer VALU issue cycles than the polynomial kernels above (2 quarter-rate + 4 full-rate ops).
 __device__ __forceinline__ void nif_sincosf_core(float x, float* sp, float* cp) {
   const float k = rintf(x * 0.15915493667125702f);
   float f = fmaf(x, 0.15915493667125702f, -k);
@@ -431,15 +428,6 @@ __device__ __forceinline__ void nif_sin_cossign_core(float x, float* sp, float* 
   *sp = __builtin_amdgcn_sinf(f);
   *csign = 0.25f - fabsf(f);
 }
-#else
-__device__ __forceinline__ void nif_sincosf_core(float x, float* sp, float* cp) {
-  const float k = rintf(x * 0.63661977236758134308f);
-  float r = fmaf(-k, 1.57079637050628662109375f, x);
-  r = fmaf(-k, -4.371138828673793e-08f, r);
-  r = fmaf(-k, -1.7151245100058819e-15f, r);
-  nif_sincos_poly(r, (int)k, sp, cp);
-}
-#endif
 // |x| >= 2^20: same kernels, argument reduction in fp64 (2-term Cody-Waite, k < 2^52)
 __device__ __forceinline__ void nif_sincosf_big(float x, float* sp, float* cp) {
   const double xd = (double)x;
@@ -655,32 +643,6 @@ __device__ __forceinline__ void act_tile_sel(int act, const f32x16 (&a)[NB], f32
   if (ACT == ACT_SINE) sine_tile<NB>(a, h, d, n, hf);
   else if (ACT == ACT_SWISH) act_tile_t<NB, ACT_SWISH>(a, h, d, n, hf);
   else act_tile<NB>(act, a, h, d, n, hf);
-}
-
-// same, A operands from an LDS-resident plane; ACCUM keeps the incoming T
-template <int NBI, int NBO, bool ACCUM>
-__device__ __forceinline__ void dense_mfma_lds(const f32x4* plane, const f32x16 (&hin)[NBI], f32x16 (&T)[NBO], int lane) {
-#pragma unroll
-  for (int ob = 0; ob < NBO; ++ob) {
-    f32x16 t;
-    if (ACCUM) t = T[ob];
-    else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) t[i] = 0.f;
-    }
-#pragma unroll
-    for (int ib = 0; ib < NBI; ++ib) {
-#pragma unroll
-      for (int vq = 0; vq < 4; ++vq) {
-        const f32x4 a = plane[((ob * NBI + ib) * 4 + vq) * 64 + lane];
-        t = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], hin[ib][4 * vq + 0], t, 0, 0, 0);
-        t = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], hin[ib][4 * vq + 1], t, 0, 0, 0);
-        t = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], hin[ib][4 * vq + 2], t, 0, 0, 0);
-        t = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], hin[ib][4 * vq + 3], t, 0, 0, 0);
-      }
-    }
-    T[ob] = t;
-  }
 }
 
 template <int NB>
