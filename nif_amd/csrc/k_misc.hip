@@ -350,13 +350,18 @@ __global__ __launch_bounds__(NIF_L2W_T) void k_latent_to_w_flat(const float* __r
         if (e + c >= 0 && e + c < n) w[e + c] = v[c];
     }
     e += 4L * NIF_L2W_T;
-    sc += ds; a += da;                         // (a unit that starts in front of the buffer has a = 0, sc < 0: the same step)
+    sc += ds; a += da;
     if (sc >= po) { sc -= po; ++a; }
+    // the unit that starts in front of the buffer (thread 0 of block 0, e = sc = -wmis, a = 0) can still have sc < 0 here when
+    // ds < wmis: its unit now starts at the END of row da - 1 (po = 195: ds = 1, wmis = 2 / 3 wrote zeros into w[20, 193:195])
+    else if (sc < 0) { sc += po; --a; }
   }
 }
 void launch_latent_to_w(const float* theta, long off_Wh, long off_bh, int r, long po, const float* lr, long B, float* w,
                         hipStream_t st) {
-  if ((size_t)(r + 1) * (4 * ((po + 3) / 4)) * sizeof(float) <= 144u * 1024u) {
+  // rows of latents that fit the 160 KB of a workgroup beside the (r+1) planes of the flat form
+  const long lds_rows = (160L * 1024 / 4 - (long)(r + 1) * (4 * ((po + 3) / 4))) / r;
+  if ((size_t)(r + 1) * (4 * ((po + 3) / 4)) * sizeof(float) <= 144u * 1024u && (4 * NIF_L2W_T + po - 1) / po + 2 <= lds_rows) {
     const long nunits = (B * po + 3 + 3) / 4;
     const long nb = NIF_L2W_NB;
     long span = ((nunits + nb - 1) / nb + NIF_L2W_T - 1) / NIF_L2W_T * NIF_L2W_T;
@@ -364,6 +369,13 @@ void launch_latent_to_w(const float* theta, long off_Wh, long off_bh, int r, lon
     const long max_rows = (8 * 1024 / 4) / r;
     const long span_cap = ((max_rows - 2) * po / 4) / NIF_L2W_T * NIF_L2W_T;
     if (span > span_cap && span_cap >= NIF_L2W_T) span = span_cap;
+    // ... and the planes and the latents together must fit the LDS: a tiny net with a large latent (po = 97, r = 64) has
+    // span_cap < NIF_L2W_T, and its uncapped span asked for 290 KB at 2^22 points.  NR <= 4 span / po + 3, and one unit per
+    // thread (span = NIF_L2W_T) fits by the test above.  Only spans the LDS could not take are changed
+    if ((4 * span + po - 1) / po + 2 > lds_rows) {
+      span = ((lds_rows - 3) * po / 4) / NIF_L2W_T * NIF_L2W_T;
+      if (span < NIF_L2W_T) span = NIF_L2W_T;
+    }
     const int NR = (int)((4 * span + po - 1) / po + 2);
     const long nblk = (nunits + span - 1) / span;
     const size_t shm = sizeof(float) * ((size_t)(r + 1) * (4 * ((po + 3) / 4)) + (size_t)NR * r);
