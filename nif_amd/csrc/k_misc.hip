@@ -1,5 +1,5 @@
 // k_misc.hip -- the HBM-bound kernels of the path: per-sample-weight ShapeNet ("given w"), the
-// latent->weights map, gradient-row reduction, Adam, and row<->tile layout changes (gfx950).
+// latent->weights map and row<->tile layout changes (gfx950); the gradient-row reduction and the optimizer updates are in k_opt.hip.
 #include "nif_internal.h"
 
 // ============================================================================================
@@ -408,141 +408,6 @@ void launch_latent_to_w(const float* theta, long off_Wh, long off_bh, int r, lon
   (void)hipFuncSetAttribute((const void*)k_latent_to_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   hipLaunchKernelGGL(k_latent_to_w, dim3((unsigned)ncw, (unsigned)nrb), dim3(NIF_L2W_T), shm, st, theta, off_Wh, off_bh, r, po, lr, B,
                      w, (int)CU, LW, rpb);
-}
-
-// ============================================================================================
-// gradient rows -> flat gradient (fixed summation order), loss partials -> g[P]
-// ============================================================================================
-__global__ __launch_bounds__(512) void k_reduce(const float* __restrict__ partial, long pstride, int rows,
-                                                const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P) {
-  // block = 64 columns x 8 row groups, four independent partial sums per thread (the kernel is a latency-bound
-  // stream of <= 256 rows: more loads in flight, not more bandwidth, is what it needs); fixed order => deterministic
-  __shared__ float red[8][64];
-  const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const long i = (long)blockIdx.x * 64 + col;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (i < P) {
-    const float* p = partial + i;
-    int rrow = rg;
-    for (; rrow + 24 < rows; rrow += 32) {
-      s0 += p[(long)rrow * pstride]; s1 += p[(long)(rrow + 8) * pstride];
-      s2 += p[(long)(rrow + 16) * pstride]; s3 += p[(long)(rrow + 24) * pstride];
-    }
-    for (; rrow < rows; rrow += 8) s0 += p[(long)rrow * pstride];
-  }
-  red[rg][col] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (rg == 0 && i < P)
-    g[i] = ((red[0][col] + red[1][col]) + (red[2][col] + red[3][col])) + ((red[4][col] + red[5][col]) + (red[6][col] + red[7][col]));
-  if (blockIdx.x == gridDim.x - 1) {
-    // the loss: every thread sums a strided subset in a fixed order, then a fixed tree
-    __syncthreads();
-    float ls = 0.f;
-    for (int b = threadIdx.x; b < nloss; b += 512) ls += lossp[b];
-    red[rg][col] = ls;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      float v = ((red[0][col] + red[1][col]) + (red[2][col] + red[3][col])) + ((red[4][col] + red[5][col]) + (red[6][col] + red[7][col]));
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-      if (threadIdx.x == 0) g[P] = v;
-    }
-  }
-}
-void launch_reduce(const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g, long P,
-                   hipStream_t st) {
-  dim3 grid((unsigned)((P + 63) / 64)), block(512);
-  hipLaunchKernelGGL(k_reduce, grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P);
-}
-
-// k_reduce with the Adam update of column i behind its sum (r6: the deferred row reduction of a plain single-GPU step; the same
-// summation order and the same update expressions as k_reduce + k_adam: bit-identical results, g is still written)
-__global__ __launch_bounds__(512) void k_reduce_adam(const float* __restrict__ partial, long pstride, int rows,
-                                                     const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P,
-                                                     float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
-                                                     float lr_t, float b1, float b2, float eps) {
-  __shared__ float red[8][64];
-  const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const long i = (long)blockIdx.x * 64 + col;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (i < P) {
-    const float* p = partial + i;
-    int rrow = rg;
-    for (; rrow + 24 < rows; rrow += 32) {
-      s0 += p[(long)rrow * pstride]; s1 += p[(long)(rrow + 8) * pstride];
-      s2 += p[(long)(rrow + 16) * pstride]; s3 += p[(long)(rrow + 24) * pstride];
-    }
-    for (; rrow < rows; rrow += 8) s0 += p[(long)rrow * pstride];
-  }
-  red[rg][col] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (rg == 0 && i < P) {
-    const float gi = ((red[0][col] + red[1][col]) + (red[2][col] + red[3][col])) + ((red[4][col] + red[5][col]) + (red[6][col] + red[7][col]));
-    g[i] = gi;
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-    const float vi = v[i] + (gi * gi - v[i]) * (1.0f - b2);
-    m[i] = mi; v[i] = vi;
-    theta[i] -= lr_t * mi / (sqrtf(vi) + eps);
-  }
-  if (blockIdx.x == gridDim.x - 1) {
-    __syncthreads();
-    float ls = 0.f;
-    for (int b = threadIdx.x; b < nloss; b += 512) ls += lossp[b];
-    red[rg][col] = ls;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      float vv = ((red[0][col] + red[1][col]) + (red[2][col] + red[3][col])) + ((red[4][col] + red[5][col]) + (red[6][col] + red[7][col]));
-      for (int off = 32; off > 0; off >>= 1) vv += __shfl_down(vv, off);
-      if (threadIdx.x == 0) g[P] = vv;
-    }
-  }
-}
-void launch_reduce_adam(const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g, long P,
-                        float* theta, float* m, float* v, float lr_t, float b1, float b2, float eps, hipStream_t st) {
-  dim3 grid((unsigned)((P + 63) / 64)), block(512);
-  hipLaunchKernelGGL(k_reduce_adam, grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, lr_t, b1, b2, eps);
-}
-
-// Keras-2.11 Adam (SURVEY a-11): lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed on the host
-__global__ void k_adam(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, long P, float lr_t, float b1, float b2, float eps) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const float gi = g[i];
-  const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-  const float vi = v[i] + (gi * gi - v[i]) * (1.0f - b2);
-  m[i] = mi; v[i] = vi;
-  theta[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
-// The same update with the hyper-parameters and the iteration count in DEVICE memory (AdamDev: lr, beta1, beta2, eps, step): what a
-// captured hipGraph of training steps needs -- a replayed launch cannot carry this step's lr_t as a kernel argument.  Every block
-// forms lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), t = step + 1, in fp64 like the host does; k_adam_step_inc bumps the counter behind it.
-__global__ void k_adam_dev(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long P,
-                           const AdamDev* __restrict__ ad) {
-  __shared__ float lr_s;
-  if (threadIdx.x == 0) {
-    const double t = (double)(ad->step + 1);
-    lr_s = (float)((double)ad->lr * sqrt(1.0 - pow((double)ad->beta2, t)) / (1.0 - pow((double)ad->beta1, t)));
-  }
-  __syncthreads();
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const float b1 = ad->beta1, b2 = ad->beta2, eps = ad->eps, lr_t = lr_s;
-  const float gi = g[i];
-  const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-  const float vi = v[i] + (gi * gi - v[i]) * (1.0f - b2);
-  m[i] = mi; v[i] = vi;
-  theta[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
-__global__ void k_adam_step_inc(AdamDev* ad) { ad->step += 1; }
-void launch_adam_dev(float* theta, const float* g, float* m, float* v, long P, AdamDev* ad, hipStream_t st) {
-  dim3 grid((unsigned)((P + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_adam_dev, grid, block, 0, st, theta, g, m, v, P, ad);
-  hipLaunchKernelGGL(k_adam_step_inc, dim3(1), dim3(1), 0, st, ad);
-}
-void launch_adam(float* theta, const float* g, float* m, float* v, long P, float lr_t, float b1, float b2, float eps,
-                 hipStream_t st) {
-  dim3 grid((unsigned)((P + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_adam, grid, block, 0, st, theta, g, m, v, P, lr_t, b1, b2, eps);
 }
 
 // rows [B][c]  <->  tiles [ceil(B/32)][c][32]

@@ -1,19 +1,29 @@
-// k_opt.hip -- the reference's Lion and AdaBelief updates (nif/optimizers/external_optimizers.py:631-735, :322-628) on the flat
-// parameter vector (gfx950).  Three forms of each, like Adam's in k_misc.hip:
-//   * k_lion / k_adabelief<AMS>: the update alone over [0, P), behind an all-reduce, a regulariser or a flushed row reduction.  A stream
-//     bound by bandwidth: Lion reads theta, g, m (12 B) and writes theta, m (8 B) per parameter; AdaBelief 16 B / 12 B, with amsgrad
-//     20 B / 16 B.  Four parameters per thread with 16-byte accesses where every buffer is 16-byte aligned, a scalar tail for P % 4.
-//   * k_reduce_lion / k_reduce_adabelief<AMS>: k_reduce's row sum of column i (same summation order), g[i] and the loss g[P] still
-//     written, then the update of column i behind its sum -- bit-identical to k_reduce followed by the standalone update.
-//   * k_lion_dev / k_adabelief_dev<AMS>: hyper-parameters and iteration count from device memory (OptDev) for captured graphs; each
-//     block forms the step's scalars in fp64 (opt_scalars, the host's own function), k_opt_step_inc bumps the count behind the update.
-// Every form runs the same per-element expressions (lion_1 / adab_1) with contraction off, so that the update is the same float
-// sequence the NumPy restatement of the tests computes, whichever form ran it.
+// k_opt.hip -- the optimizer updates on the flat parameter vector (gfx950): Keras-2.11 Adam (SURVEY a-11) and the reference's Lion and
+// AdaBelief (nif/optimizers/external_optimizers.py:631-735, :322-628), and the fixed-order row reduction of the gradient (k_reduce), which
+// the fused forms share.  Three forms of each update, each one template over (kind, amsgrad):
+//   * k_opt: the update alone over [0, P), behind an all-reduce, a regulariser or a flushed row reduction.  A stream bound by bandwidth:
+//     Adam reads theta, g, m, v (16 B) and writes theta, m, v (12 B) per parameter; Lion 12 B / 8 B; AdaBelief as Adam, with amsgrad
+//     20 B / 16 B.  Lion and AdaBelief four parameters per thread with 16-byte accesses where every buffer is 16-byte aligned, a
+//     scalar tail for P % 4; Adam one parameter per thread (stream_shape).
+//   * k_reduce_opt: k_reduce's row sum of column i (same summation order), g[i] and the loss g[P] still written, then the update of
+//     column i behind its sum -- bit-identical to k_reduce followed by the standalone update.
+//   * k_opt_dev: hyper-parameters and iteration count from device memory (OptDev) for captured graphs; each block forms the step's
+//     scalars in fp64 (opt_scalars / opt_args, the host's own functions), k_opt_step_inc bumps the count behind the update.
+// Every form runs the same per-element expressions (adam_1 / lion_1 / adab_1) with contraction off, so that the update is the same float
+// sequence whichever form ran it; Adam's one fused multiply-add is written out.
 #include "nif_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+// Adam (Keras 2.11): m = m + (g - m)(1-b1); v = v + (g^2 - v)(1-b2) rounded once (fmaf); theta -= lr_t m / (sqrt(v) + eps), where
+// a.lr = lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) (opt_args).  The roundings of Adam's earlier kernels, which had contraction on.
+__device__ __forceinline__ void adam_1(float& th, float g, float& m, float& v, const OptArgs& a) {
+  m = m + (g - m) * (1.0f - a.b1);
+  v = fmaf(g * g - v, 1.0f - a.b2, v);
+  th = th - a.lr * m / (sqrtf(v) + a.eps);
+}
 
 // Lion (dense apply :682-703): c = b1 m + (1-b1) g; theta -= lr (sign(c) + wd theta); m = b2 m + (1-b2) g from the OLD m.
 // sign as tf.math.sign: 0 for +-0 (returned as is: with wd = 0 such a theta does not move), NaN stays NaN.
@@ -41,7 +51,15 @@ __device__ __forceinline__ void adab_1(float& th, float g, float& m, float& v, f
   th = th - a.lr * u;
 }
 
-// KIND = OPT_LION: slot m; OPT_ADABELIEF: m, v (+ vhat with AMS).  n4 = P / 4 when every buffer is 16-byte aligned, else 0 (all scalar)
+// one parameter of any kind: Adam slots m, v; Lion m; AdaBelief m, v (+ vhat with AMS)
+template <int KIND, bool AMS>
+__device__ __forceinline__ void opt_1(float& th, float g, float& m, float& v, float& vh, const OptArgs& a) {
+  if (KIND == OPT_ADAM) adam_1(th, g, m, v, a);
+  else if (KIND == OPT_LION) lion_1(th, g, m, a);
+  else adab_1<AMS>(th, g, m, v, vh, a);
+}
+
+// n4 = P / 4 when every buffer is 16-byte aligned, else 0 (all scalar)
 template <int KIND, bool AMS>
 __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
                                            float* __restrict__ v, float* __restrict__ vh, long P, long n4, const OptArgs& a) {
@@ -52,34 +70,33 @@ __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const floa
     const f32x4 g4 = reinterpret_cast<const f32x4*>(g)[q];
     f32x4 m4 = reinterpret_cast<const f32x4*>(m)[q];
     f32x4 v4 = {0.f, 0.f, 0.f, 0.f}, h4 = {0.f, 0.f, 0.f, 0.f};
-    if (KIND == OPT_ADABELIEF) v4 = reinterpret_cast<const f32x4*>(v)[q];
+    if (KIND != OPT_LION) v4 = reinterpret_cast<const f32x4*>(v)[q];
     if (AMS) h4 = reinterpret_cast<const f32x4*>(vh)[q];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float tj = t4[j], mj = m4[j], vj = v4[j], hj = h4[j];
-      if (KIND == OPT_LION) lion_1(tj, g4[j], mj, a);
-      else adab_1<AMS>(tj, g4[j], mj, vj, hj, a);
+      opt_1<KIND, AMS>(tj, g4[j], mj, vj, hj, a);
       t4[j] = tj; m4[j] = mj; v4[j] = vj; h4[j] = hj;
     }
     reinterpret_cast<f32x4*>(theta)[q] = t4;
     reinterpret_cast<f32x4*>(m)[q] = m4;
-    if (KIND == OPT_ADABELIEF) reinterpret_cast<f32x4*>(v)[q] = v4;
+    if (KIND != OPT_LION) reinterpret_cast<f32x4*>(v)[q] = v4;
     if (AMS) reinterpret_cast<f32x4*>(vh)[q] = h4;
   }
   for (long i = 4 * n4 + tid; i < P; i += stride) {
     float tj = theta[i], mj = m[i], vj = 0.f, hj = 0.f;
-    if (KIND == OPT_ADABELIEF) vj = v[i];
+    if (KIND != OPT_LION) vj = v[i];
     if (AMS) hj = vh[i];
-    if (KIND == OPT_LION) lion_1(tj, g[i], mj, a);
-    else adab_1<AMS>(tj, g[i], mj, vj, hj, a);
+    opt_1<KIND, AMS>(tj, g[i], mj, vj, hj, a);
     theta[i] = tj; m[i] = mj;
-    if (KIND == OPT_ADABELIEF) v[i] = vj;
+    if (KIND != OPT_LION) v[i] = vj;
     if (AMS) vh[i] = hj;
   }
 }
 
-// k_reduce's body (k_misc.hip), shared by the fused forms: block = 64 columns x 8 row groups, four partial sums per thread, a fixed tree
-// over the row groups -- the same order, so the same float.  Returns the column sum on row group 0 (and i < P).
+// the row sum of k_reduce and the fused forms: block = 64 columns x 8 row groups, four independent partial sums per thread (a latency-
+// bound stream of <= 256 rows: more loads in flight, not more bandwidth, is what it needs), a fixed tree over the row groups -- fixed
+// order, so deterministic.  Returns the column sum on every row group (stored by row group 0, i < P).
 __device__ __forceinline__ float reduce_col(const float* __restrict__ partial, long pstride, int rows, float (*red)[64], int col,
                                             int rg, long i, long P) {
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -96,7 +113,7 @@ __device__ __forceinline__ float reduce_col(const float* __restrict__ partial, l
   __syncthreads();
   return ((red[0][col] + red[1][col]) + (red[2][col] + red[3][col])) + ((red[4][col] + red[5][col]) + (red[6][col] + red[7][col]));
 }
-// k_reduce's loss sum into g[P] (last block only, every thread of it)
+// the loss partials into g[P] (last block only, every thread of it): a strided subset per thread in a fixed order, then a fixed tree
 __device__ __forceinline__ void reduce_loss(const float* __restrict__ lossp, int nloss, float (*red)[64], int col, int rg, float* gP) {
   __syncthreads();
   float ls = 0.f;
@@ -110,10 +127,14 @@ __device__ __forceinline__ void reduce_loss(const float* __restrict__ lossp, int
   }
 }
 
+// the step's scalars from device memory, formed once per block.  od->kind is KIND (a graph is replayed only with the kind it recorded):
+// stating it lets the compiler drop the other kinds' scalar code from the block's prologue
+template <int KIND>
 __device__ __forceinline__ OptArgs block_args(const OptDev* __restrict__ od) {
   __shared__ OptArgs sa;
   if (threadIdx.x == 0) {
-    const OptDev o = *od;
+    OptDev o = *od;
+    o.kind = KIND;
     sa = opt_args(o, opt_scalars(o, o.step + 1));
   }
   __syncthreads();
@@ -122,73 +143,64 @@ __device__ __forceinline__ OptArgs block_args(const OptDev* __restrict__ od) {
 
 }  // namespace
 
-// ---- standalone updates -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_lion(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m, long P,
-                                              long n4, OptArgs a) {
-  opt_stream<OPT_LION, false>(theta, g, m, nullptr, nullptr, P, n4, a);
-}
-template <bool AMS>
-__global__ __launch_bounds__(256) void k_adabelief(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, float* __restrict__ vh, long P, long n4, OptArgs a) {
-  opt_stream<OPT_ADABELIEF, AMS>(theta, g, m, v, vh, P, n4, a);
-}
-
-// ---- device-state forms (captured graphs) -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_lion_dev(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m, long P,
-                                                  long n4, const OptDev* __restrict__ od) {
-  const OptArgs a = block_args(od);
-  opt_stream<OPT_LION, false>(theta, g, m, nullptr, nullptr, P, n4, a);
-}
-template <bool AMS>
-__global__ __launch_bounds__(256) void k_adabelief_dev(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, float* __restrict__ vh, long P, long n4,
-                                                       const OptDev* __restrict__ od) {
-  const OptArgs a = block_args(od);
-  opt_stream<OPT_ADABELIEF, AMS>(theta, g, m, v, vh, P, n4, a);
-}
-__global__ void k_opt_step_inc(OptDev* od) { od->step += 1; }
-
-// ---- fused tails: row reduction + update of the column -----------------------------------------------------------------------
-__global__ __launch_bounds__(512) void k_reduce_lion(const float* __restrict__ partial, long pstride, int rows,
-                                                     const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P,
-                                                     float* __restrict__ theta, float* __restrict__ m, OptArgs a) {
+// ---- gradient rows -> flat gradient (fixed summation order), loss partials -> g[P] ----------------------------------------------
+__global__ __launch_bounds__(512) void k_reduce(const float* __restrict__ partial, long pstride, int rows,
+                                                const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P) {
   __shared__ float red[8][64];
   const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
   const long i = (long)blockIdx.x * 64 + col;
   const float gi = reduce_col(partial, pstride, rows, red, col, rg, i, P);
-  if (rg == 0 && i < P) {
-    g[i] = gi;
-    float th = theta[i], mi = m[i];
-    lion_1(th, gi, mi, a);
-    theta[i] = th; m[i] = mi;
-  }
+  if (rg == 0 && i < P) g[i] = gi;
   if (blockIdx.x == gridDim.x - 1) reduce_loss(lossp, nloss, red, col, rg, g + P);
 }
-template <bool AMS>
-__global__ __launch_bounds__(512) void k_reduce_adabelief(const float* __restrict__ partial, long pstride, int rows,
-                                                          const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P,
-                                                          float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
-                                                          float* __restrict__ vh, OptArgs a) {
+
+// ---- the three update forms -------------------------------------------------------------------------------------------------------
+template <int KIND, bool AMS>
+__global__ __launch_bounds__(256) void k_opt(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, float* __restrict__ vh, long P, long n4, OptArgs a) {
+  opt_stream<KIND, AMS>(theta, g, m, v, vh, P, n4, a);
+}
+template <int KIND, bool AMS>
+__global__ __launch_bounds__(256) void k_opt_dev(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, float* __restrict__ vh, long P, long n4,
+                                                 const OptDev* __restrict__ od) {
+  const OptArgs a = block_args<KIND>(od);
+  opt_stream<KIND, AMS>(theta, g, m, v, vh, P, n4, a);
+}
+__global__ void k_opt_step_inc(OptDev* od) { od->step += 1; }
+template <int KIND, bool AMS>
+__global__ __launch_bounds__(512) void k_reduce_opt(const float* __restrict__ partial, long pstride, int rows,
+                                                    const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P,
+                                                    float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
+                                                    float* __restrict__ vh, OptArgs a) {
   __shared__ float red[8][64];
   const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
   const long i = (long)blockIdx.x * 64 + col;
   const float gi = reduce_col(partial, pstride, rows, red, col, rg, i, P);
   if (rg == 0 && i < P) {
     g[i] = gi;
-    float th = theta[i], mi = m[i], vi = v[i], hi = AMS ? vh[i] : 0.f;
-    adab_1<AMS>(th, gi, mi, vi, hi, a);
-    theta[i] = th; m[i] = mi; v[i] = vi;
+    float th = theta[i], mi = m[i], vi = KIND != OPT_LION ? v[i] : 0.f, hi = AMS ? vh[i] : 0.f;
+    opt_1<KIND, AMS>(th, gi, mi, vi, hi, a);
+    theta[i] = th; m[i] = mi;
+    if (KIND != OPT_LION) v[i] = vi;
     if (AMS) vh[i] = hi;
   }
   if (blockIdx.x == gridDim.x - 1) reduce_loss(lossp, nloss, red, col, rg, g + P);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
+void launch_reduce(const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g, long P,
+                   hipStream_t st) {
+  hipLaunchKernelGGL(k_reduce, dim3((unsigned)((P + 63) / 64)), dim3(512), 0, st, partial, pstride, rows, loss_partial, nloss, g, P);
+}
+
 static bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-// n4 and the grid of a stream over P parameters: at most 2048 blocks of 256 threads, the rest grid-strided
-static void stream_shape(const float* theta, const float* g, const float* m, const float* v, const float* vh, long P, long* n4,
-                         dim3* grid) {
-  *n4 = (al16(theta) && al16(g) && al16(m) && al16(v) && al16(vh)) ? P / 4 : 0;
+// n4 and the grid of a stream over P parameters (v, vh: nullptr where the kind does not use them): at most 2048 blocks of 256 threads,
+// the rest grid-strided.  Adam runs one parameter per thread (n4 = 0), the shape of its earlier kernels: four per thread serialise
+// four divisions and square roots, and made the captured configs[0] step (P = 6 627, 7 blocks instead of 26) 0.5 us slower
+static void stream_shape(int kind, const float* theta, const float* g, const float* m, const float* v, const float* vh, long P,
+                         long* n4, dim3* grid) {
+  *n4 = (kind != OPT_ADAM && al16(theta) && al16(g) && al16(m) && al16(v) && al16(vh)) ? P / 4 : 0;
   const long work = *n4 > 0 ? *n4 : P;
   long blocks = (work + 255) / 256;
   if (blocks > 2048) blocks = 2048;
@@ -196,45 +208,42 @@ static void stream_shape(const float* theta, const float* g, const float* m, con
   *grid = dim3((unsigned)blocks);
 }
 
+// kind OPT_*, ams: AdaBelief's amsgrad.  The slots a kind does not use are not touched (v for Lion, vhat without amsgrad: may be null)
 void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, const OptArgs& a,
                 hipStream_t st) {
+  if (kind == OPT_LION) v = nullptr;
+  if (!ams) vhat = nullptr;
   long n4; dim3 grid;
-  if (kind == OPT_LION) {
-    stream_shape(theta, g, m, nullptr, nullptr, P, &n4, &grid);
-    hipLaunchKernelGGL(k_lion, grid, dim3(256), 0, st, theta, g, m, P, n4, a);
-  } else if (ams) {
-    stream_shape(theta, g, m, v, vhat, P, &n4, &grid);
-    hipLaunchKernelGGL(k_adabelief<true>, grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
-  } else {
-    stream_shape(theta, g, m, v, nullptr, P, &n4, &grid);
-    hipLaunchKernelGGL(k_adabelief<false>, grid, dim3(256), 0, st, theta, g, m, v, (float*)nullptr, P, n4, a);
-  }
+  stream_shape(kind, theta, g, m, v, vhat, P, &n4, &grid);
+  if (kind == OPT_ADAM) hipLaunchKernelGGL((k_opt<OPT_ADAM, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
+  else if (kind == OPT_LION) hipLaunchKernelGGL((k_opt<OPT_LION, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
+  else if (ams) hipLaunchKernelGGL((k_opt<OPT_ADABELIEF, true>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
+  else hipLaunchKernelGGL((k_opt<OPT_ADABELIEF, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
 }
 
 void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g,
                        long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st) {
-  dim3 grid((unsigned)((P + 63) / 64)), block(512);
-  if (kind == OPT_LION)
-    hipLaunchKernelGGL(k_reduce_lion, grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, a);
+  const dim3 grid((unsigned)((P + 63) / 64)), block(512);
+  if (kind == OPT_ADAM)
+    hipLaunchKernelGGL((k_reduce_opt<OPT_ADAM, false>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
+  else if (kind == OPT_LION)
+    hipLaunchKernelGGL((k_reduce_opt<OPT_LION, false>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
   else if (ams)
-    hipLaunchKernelGGL(k_reduce_adabelief<true>, grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
+    hipLaunchKernelGGL((k_reduce_opt<OPT_ADABELIEF, true>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
   else
-    hipLaunchKernelGGL(k_reduce_adabelief<false>, grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v,
-                       (float*)nullptr, a);
+    hipLaunchKernelGGL((k_reduce_opt<OPT_ADABELIEF, false>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
 }
 
 void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
                     hipStream_t st) {
+  if (kind == OPT_LION) v = nullptr;
+  if (!ams) vhat = nullptr;
   long n4; dim3 grid;
-  if (kind == OPT_LION) {
-    stream_shape(theta, g, m, nullptr, nullptr, P, &n4, &grid);
-    hipLaunchKernelGGL(k_lion_dev, grid, dim3(256), 0, st, theta, g, m, P, n4, (const OptDev*)od);
-  } else if (ams) {
-    stream_shape(theta, g, m, v, vhat, P, &n4, &grid);
-    hipLaunchKernelGGL(k_adabelief_dev<true>, grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, (const OptDev*)od);
-  } else {
-    stream_shape(theta, g, m, v, nullptr, P, &n4, &grid);
-    hipLaunchKernelGGL(k_adabelief_dev<false>, grid, dim3(256), 0, st, theta, g, m, v, (float*)nullptr, P, n4, (const OptDev*)od);
-  }
+  stream_shape(kind, theta, g, m, v, vhat, P, &n4, &grid);
+  const OptDev* o = od;
+  if (kind == OPT_ADAM) hipLaunchKernelGGL((k_opt_dev<OPT_ADAM, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
+  else if (kind == OPT_LION) hipLaunchKernelGGL((k_opt_dev<OPT_LION, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
+  else if (ams) hipLaunchKernelGGL((k_opt_dev<OPT_ADABELIEF, true>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
+  else hipLaunchKernelGGL((k_opt_dev<OPT_ADABELIEF, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
   hipLaunchKernelGGL(k_opt_step_inc, dim3(1), dim3(1), 0, st, od);
 }

@@ -13,7 +13,7 @@
 //     half wave, layer inputs and dL/da rows of every layer kept in an LDS tape;
 //   * behind ONE barrier the workgroup's 512 threads form every entry of the flat gradient over its 16 points from the tapes
 //     (K = 16 sums in registers) and write ONE partial row per workgroup -- the existing k_reduce sums the rows in fixed order
-//     (deterministic), k_adam / the RCCL all-reduce see the same [grad | loss] buffer as after the large-batch kernels.
+//     (deterministic), the optimizer update / the RCCL all-reduce see the same [grad | loss] buffer as after the large-batch kernels.
 // Shapes: class NIF (any Keras activation, skip connections) and plain-SIREN NIFMultiScale; ParameterNet MLP_SimpleShortCut / SIREN
 // hidden layers; units <= 32 in both nets, <= 4 hidden matrices each, latent_dim <= 4, <= 4 inputs / outputs; float32 policy;
 // batches <= NIF_SMALL_MAX_B points.  Everything else (and NIF_SMALL_STEP=0 / nif_set_option("small_step", 0)) keeps the tile kernels.

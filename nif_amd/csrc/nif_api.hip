@@ -205,9 +205,8 @@ extern "C" int nif_destroy(nif_ctx* c) {
   if (c->ev_done) hipEventDestroy(c->ev_done);
   for (hipEvent_t e : c->ev_chunk) hipEventDestroy(e);
   for (hipGraphExec_t ex : c->graphs) if (ex) (void)hipGraphExecDestroy(ex);
-  if (c->adam_host) (void)hipHostFree(c->adam_host);
   if (c->opt_host) (void)hipHostFree(c->opt_host);
-  void* ptrs[] = {c->adam_dev, c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
+  void* ptrs[] = {c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
                   c->DU, c->ZL, c->partial, c->loss_partial, c->dring, c->metric, c->tl, c->lWF, c->lWB, c->sWF4, c->sWB4, c->sWF4x, c->sWB4x, c->sWscale, c->sWF4h, c->sWB4h, c->ll_slots, c->ll_wpf, c->ll_wpb, c->stash_l, c->PHI, c->DPHI, c->DA, c->DZL, c->d_a, c->d_b, c->d_c, c->d_d};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->st) hipStreamDestroy(c->st);
@@ -1455,8 +1454,8 @@ static int ensure_small_tables(nif_ctx* c, const PNetArgs& pa, const SNetArgs& s
   HIPCHK(hipMemcpy(c->small_desc, desc.data(), desc.size() * sizeof(int), hipMemcpyHostToDevice));
   return NIF_OK;
 }
-// r6: the row reduction of a plain step waits for its consumer when nothing else needs [grad | loss] first: nif_adam_step_dev runs it fused
-// with the update (k_reduce_adam: one launch less per step -- 5 of the 31 us of a 512-point step, 0.5 % of the 2^20-point one).  Every
+// r6: the row reduction of a plain step waits for its consumer when nothing else needs [grad | loss] first: the optimizer step runs it fused
+// with the update (k_reduce_opt: one launch less per step -- 5 of the 31 us of a 512-point step, 0.5 % of the 2^20-point one).  Every
 // other entry point of the library starts with nif_tail_flush; the reduction is NOT deferred with a communicator attached, inside a graph
 // capture, under the profiler (its per-group events would lose the REDUCE group) or when a regulariser adds to the gradient behind it.
 int nif_tail_flush(nif_ctx* c) {
@@ -1987,53 +1986,12 @@ extern "C" int nif_metric_read(nif_ctx* c, double* sum, double* cnt, int reset) 
   *sum = h[0]; *cnt = h[1];
   return NIF_OK;
 }
-extern "C" int nif_adam_step_dev(nif_ctx* c, const nif_adam* opt) {
-  if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
-  if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
-  if (c->capturing && c->cap_kind > OPT_ADAM)
-    return fail(NIF_ERR_STATE, "nif_adam_step_dev: this capture already holds Lion / AdaBelief steps (one optimizer kind per graph)");
-  HIPCHK(hipSetDevice(c->dev));
-  if (c->tail_pending && !c->capturing && tail_can_defer(c)) {      // the step's row reduction and the update in ONE launch
-    c->tail_pending = false;
-    c->step += 1;
-    const double t = (double)c->step;
-    const double lr_t = (double)opt->lr * std::sqrt(1.0 - std::pow((double)opt->beta2, t)) / (1.0 - std::pow((double)opt->beta1, t));
-    launch_reduce_adam(c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m, c->v,
-                       (float)lr_t, opt->beta1, opt->beta2, opt->eps, c->st);
-    HIPCHK(hipGetLastError());
-    c->packed = false; c->packed32 = false; c->packed_p32 = false;
-    c->reg_applied = false;
-    return NIF_OK;
-  }
-  TAIL_FLUSH(c)
-  apply_reg(c);
-  if (c->capturing) {      // inside nif_graph_begin / _end: hyper-parameters and iteration count come from device memory at replay time
-    launch_adam_dev(c->theta, c->grad, c->m, c->v, c->P, c->adam_dev, c->st);
-    HIPCHK(hipGetLastError());
-    c->step += 1; c->cap_steps += 1; c->cap_kind = OPT_ADAM;
-    c->packed = false; c->packed32 = false; c->packed_p32 = false;
-    c->reg_applied = false;
-    return NIF_OK;
-  }
-  c->step += 1;
-  const double t = (double)c->step;
-  const double lr_t = (double)opt->lr * std::sqrt(1.0 - std::pow((double)opt->beta2, t)) / (1.0 - std::pow((double)opt->beta1, t));
-  { ProfScope p_(c, NIF_PROF_ADAM);
-    launch_adam(c->theta, c->grad, c->m, c->v, c->P, (float)lr_t, opt->beta1, opt->beta2, opt->eps, c->st); }
-  HIPCHK(hipGetLastError());
-  c->packed = false; c->packed32 = false; c->packed_p32 = false;
-  // the regulariser term belongs to ONE gradient: a following step that skips nif_loss_grad_dev (nif_zero_grad on a rank
-  // whose shard ran out of rows) must add it again, like the ranks that did compute a gradient
-  c->reg_applied = false;
-  return NIF_OK;
-}
-
 // ---- captured training steps ----------------------------------------------------------------------------------------------------
 // Small batches are launch bound (configs[0]: 13 kernels of 3-5 us behind 4-8 us of launch overhead each): between nif_graph_begin
 // and nif_graph_end every device-side call of this context (nif_loss_grad_dev, nif_sobolev_loss_grad_dev[_y], nif_adam_step_dev,
 // nif_metric_accumulate, nif_gather_rows_dev ...) is RECORDED into a hipGraph instead of executed; nif_graph_launch replays the
 // whole sequence -- an epoch of Model.fit -- with one submission.  The batch pointers are baked in (the resident table does not
-// move between epochs); Adam's hyper-parameters and iteration count live in device memory (AdamDev) and are refreshed per launch.
+// move between epochs); the optimizer's hyper-parameters and iteration count live in device memory (OptDev) and are refreshed per launch.
 // Everything a step needs must exist before the capture (nif_reserve): a workspace that would have to grow fails the capture.
 extern "C" int nif_graph_begin(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
@@ -2050,8 +2008,6 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
     if (small_supported(pa, sa)) { rc = ensure_small_tables(c, pa, sa); if (rc) return rc; }
   }
   if (!c->metric) { HIPCHK(hipMalloc(&c->metric, 2 * sizeof(double))); HIPCHK(hipMemsetAsync(c->metric, 0, 2 * sizeof(double), c->st)); }
-  if (!c->adam_dev) HIPCHK(hipMalloc(&c->adam_dev, sizeof(AdamDev)));
-  if (!c->adam_host) HIPCHK(hipHostMalloc(&c->adam_host, sizeof(AdamDev)));
   if (!c->opt_dev) HIPCHK(hipMalloc(&c->opt_dev, sizeof(OptDev)));
   if (!c->opt_host) HIPCHK(hipHostMalloc(&c->opt_host, sizeof(OptDev)));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -2080,29 +2036,13 @@ extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   *graph_id = (int32_t)c->graphs.size() - 1;
   return NIF_OK;
 }
-extern "C" int nif_graph_launch(nif_ctx* c, int32_t graph_id, const nif_adam* opt) {
-  if (!c || !opt || graph_id < 0 || graph_id >= (int32_t)c->graphs.size() || !c->graphs[graph_id]) return fail(NIF_ERR_INVALID, "bad argument");
-  if (c->capturing) return fail(NIF_ERR_STATE, "nif_graph_launch while capturing");
-  if (c->graph_kind[graph_id] > OPT_ADAM)
-    return fail(NIF_ERR_STATE, "nif_graph_launch: the graph holds Lion / AdaBelief steps (nif_graph_launch_opt with that optimizer)");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
-  c->adam_host->lr = opt->lr; c->adam_host->beta1 = opt->beta1; c->adam_host->beta2 = opt->beta2; c->adam_host->eps = opt->eps;
-  c->adam_host->step = c->step;
-  HIPCHK(hipMemcpyAsync(c->adam_dev, c->adam_host, sizeof(AdamDev), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipGraphLaunch(c->graphs[graph_id], c->st));
-  c->step += c->graph_steps[graph_id];
-  c->packed = false; c->packed32 = false; c->packed_p32 = false; c->reg_applied = false;
-  return NIF_OK;
-}
 extern "C" int nif_graph_destroy(nif_ctx* c, int32_t graph_id) {
   if (!c || graph_id < 0 || graph_id >= (int32_t)c->graphs.size()) return fail(NIF_ERR_INVALID, "bad argument");
   if (c->graphs[graph_id]) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipGraphExecDestroy(c->graphs[graph_id]); c->graphs[graph_id] = nullptr; }
   return NIF_OK;
 }
 
-// ---- Lion / AdaBelief (include/nif_hip.h nif_opt_step_dev; reference nif/optimizers/external_optimizers.py:322-735) -----------------
+// ---- optimizer steps (include/nif_hip.h nif_adam_step_dev, nif_opt_step_dev; reference nif/optimizers/external_optimizers.py:322-735) ----
 static int opt_check(const nif_opt* o) {
   if (o->kind < NIF_OPT_ADAM || o->kind > NIF_OPT_ADABELIEF) return fail(NIF_ERR_INVALID, "nif_opt: kind must be NIF_OPT_ADAM, _LION or _ADABELIEF");
   if (o->reserved0 || o->reserved[0] || o->reserved[1] || o->reserved[2] || o->reserved[3]) return fail(NIF_ERR_INVALID, "nif_opt: reserved fields must be zero");
@@ -2136,56 +2076,65 @@ extern "C" int nif_opt_scalars(const nif_opt* o, int64_t t, double* out) {
   out[0] = s.lr; out[1] = s.bc1; out[2] = s.bc2; out[3] = s.r; out[4] = (double)s.div;
   return NIF_OK;
 }
-// The same place in the step as nif_adam_step_dev and the same three forms: fused with the deferred row reduction (tail_can_defer),
-// inside a capture from device memory, else after the flushed reduction and the regulariser term
-extern "C" int nif_opt_step_dev(nif_ctx* c, const nif_opt* opt) {
-  if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
-  int rc = opt_check(opt); if (rc) return rc;
-  if (opt->kind == NIF_OPT_ADAM) { const nif_adam a = {opt->lr, opt->beta1, opt->beta2, opt->eps}; return nif_adam_step_dev(c, &a); }
+// The epilogue of every update of theta by an optimizer step: the packed weight planes are stale, and the regulariser term belongs to ONE
+// gradient -- a following step that skips nif_loss_grad_dev (nif_zero_grad on a rank whose shard ran out of rows) must add it again,
+// like the ranks that did compute a gradient
+static void theta_stepped(nif_ctx* c) {
+  c->packed = false; c->packed32 = false; c->packed_p32 = false;
+  c->reg_applied = false;
+}
+// One optimizer step of any kind, after the all-reduce, in one of three forms: fused with the deferred row reduction (tail_can_defer);
+// inside a capture with the scalars from c->opt_dev at replay time (graph_replay refreshes it); else after the flushed reduction and the
+// regulariser term.  `who` names the entry point in the error messages.
+static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
   const bool ams = opt_ams(opt);
   if (c->capturing && c->cap_kind >= 0 && (c->cap_kind != opt->kind || c->cap_ams != ams))
-    return fail(NIF_ERR_STATE, "nif_opt_step_dev: this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
+    return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
   HIPCHK(hipSetDevice(c->dev));
-  if (ams) { rc = ensure_vhat(c); if (rc) return rc; }
-  if (c->tail_pending && !c->capturing && tail_can_defer(c)) {      // the step's row reduction and the update in ONE launch
+  if (ams) { const int rc = ensure_vhat(c); if (rc) return rc; }
+  const bool fused = c->tail_pending && !c->capturing && tail_can_defer(c);    // the step's row reduction and the update in ONE launch
+  if (fused) {
     c->tail_pending = false;
-    c->step += 1;
-    const OptDev d = opt_dev_of(opt, c->step - 1);
-    launch_reduce_opt(opt->kind, ams, c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m,
-                      c->v, c->vhat, opt_args(d, opt_scalars(d, c->step)), c->st);
-    HIPCHK(hipGetLastError());
-    c->packed = false; c->packed32 = false; c->packed_p32 = false;
-    c->reg_applied = false;
-    return NIF_OK;
-  }
-  TAIL_FLUSH(c)
-  apply_reg(c);
-  if (c->capturing) {      // the scalars from c->opt_dev at replay time (nif_graph_launch_opt refreshes it)
-    launch_opt_dev(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, c->opt_dev, c->st);
-    HIPCHK(hipGetLastError());
-    c->step += 1; c->cap_steps += 1; c->cap_kind = opt->kind; c->cap_ams = ams;
-    c->packed = false; c->packed32 = false; c->packed_p32 = false;
-    c->reg_applied = false;
-    return NIF_OK;
+  } else {
+    TAIL_FLUSH(c)
+    apply_reg(c);
   }
   c->step += 1;
   const OptDev d = opt_dev_of(opt, c->step - 1);
-  { ProfScope p_(c, NIF_PROF_ADAM);
-    launch_opt(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, opt_args(d, opt_scalars(d, c->step)), c->st); }
+  const OptArgs a = opt_args(d, opt_scalars(d, c->step));
+  if (fused) {
+    launch_reduce_opt(opt->kind, ams, c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m,
+                      c->v, c->vhat, a, c->st);
+  } else if (c->capturing) {
+    launch_opt_dev(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, c->opt_dev, c->st);
+    c->cap_steps += 1; c->cap_kind = opt->kind; c->cap_ams = ams;
+  } else {
+    ProfScope p_(c, NIF_PROF_ADAM);
+    launch_opt(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, a, c->st);
+  }
   HIPCHK(hipGetLastError());
-  c->packed = false; c->packed32 = false; c->packed_p32 = false;
-  c->reg_applied = false;
+  theta_stepped(c);
   return NIF_OK;
 }
-extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt* opt) {
-  if (!c || !opt || graph_id < 0 || graph_id >= (int32_t)c->graphs.size() || !c->graphs[graph_id]) return fail(NIF_ERR_INVALID, "bad argument");
-  int rc = opt_check(opt); if (rc) return rc;
-  const int rk = c->graph_kind[graph_id];
-  if (rk >= 0 && (rk != opt->kind || (c->graph_ams[graph_id] != 0) != opt_ams(opt)))
-    return fail(NIF_ERR_INVALID, "nif_graph_launch_opt: the graph was recorded with another optimizer kind / amsgrad flag");
-  if (opt->kind == NIF_OPT_ADAM) { const nif_adam a = {opt->lr, opt->beta1, opt->beta2, opt->eps}; return nif_graph_launch(c, graph_id, &a); }
-  if (c->capturing) return fail(NIF_ERR_STATE, "nif_graph_launch_opt while capturing");
+static nif_opt opt_of_adam(const nif_adam* a) {
+  nif_opt o = {};
+  o.kind = NIF_OPT_ADAM; o.lr = a->lr; o.beta1 = a->beta1; o.beta2 = a->beta2; o.eps = a->eps;
+  return o;
+}
+extern "C" int nif_adam_step_dev(nif_ctx* c, const nif_adam* opt) {
+  if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
+  const nif_opt o = opt_of_adam(opt);
+  return opt_step(c, &o, "nif_adam_step_dev");
+}
+extern "C" int nif_opt_step_dev(nif_ctx* c, const nif_opt* opt) {
+  if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
+  const int rc = opt_check(opt); if (rc) return rc;
+  return opt_step(c, opt, "nif_opt_step_dev");
+}
+// replays a captured graph with opt's hyper-parameters (its kind checked by the caller) and the context's iteration count
+static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const char* who) {
+  if (c->capturing) return fail(NIF_ERR_STATE, std::string(who) + " while capturing");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
@@ -2193,8 +2142,24 @@ extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt*
   HIPCHK(hipMemcpyAsync(c->opt_dev, c->opt_host, sizeof(OptDev), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipGraphLaunch(c->graphs[graph_id], c->st));
   c->step += c->graph_steps[graph_id];
-  c->packed = false; c->packed32 = false; c->packed_p32 = false; c->reg_applied = false;
+  theta_stepped(c);
   return NIF_OK;
+}
+static bool graph_ok(const nif_ctx* c, int32_t graph_id) { return graph_id >= 0 && graph_id < (int32_t)c->graphs.size() && c->graphs[graph_id]; }
+extern "C" int nif_graph_launch(nif_ctx* c, int32_t graph_id, const nif_adam* opt) {
+  if (!c || !opt || !graph_ok(c, graph_id)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (c->graph_kind[graph_id] > OPT_ADAM)
+    return fail(NIF_ERR_STATE, "nif_graph_launch: the graph holds Lion / AdaBelief steps (nif_graph_launch_opt with that optimizer)");
+  const nif_opt o = opt_of_adam(opt);
+  return graph_replay(c, graph_id, &o, "nif_graph_launch");
+}
+extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt* opt) {
+  if (!c || !opt || !graph_ok(c, graph_id)) return fail(NIF_ERR_INVALID, "bad argument");
+  const int rc = opt_check(opt); if (rc) return rc;
+  const int rk = c->graph_kind[graph_id];
+  if (rk >= 0 && (rk != opt->kind || (c->graph_ams[graph_id] != 0) != opt_ams(opt)))
+    return fail(NIF_ERR_INVALID, "nif_graph_launch_opt: the graph was recorded with another optimizer kind / amsgrad flag");
+  return graph_replay(c, graph_id, opt, "nif_graph_launch_opt");
 }
 extern "C" int nif_get_opt_slot(nif_ctx* c, int32_t slot, float* host, int64_t n) {
   if (!c || !host || slot < 0 || slot > 2) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat)");

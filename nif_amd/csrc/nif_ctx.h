@@ -62,13 +62,12 @@ struct nif_ctx {
   float* zt_par = nullptr; long zt_par_cap = 0; float* dzt_par = nullptr; long dzt_par_cap = 0;
   float* dat_par = nullptr; long dat_par_cap = 0; float* ztl_par = nullptr; long ztl_par_cap = 0;   // last-layer class: dL/da', z' in latent-row layout   // Sobolev with parameter seeds: dz/dp, dL/d(dz/dp)
   float jac_l1 = 0.f; float* jac_mu = nullptr; long jac_mu_cap = 0; float* jac_tmp = nullptr;   // latent Jacobian regulariser (k_pjac)
-  // captured training steps (nif_graph_*): hipGraph executables, the steps each one carries, the device-side Adam state
+  // captured training steps (nif_graph_*): hipGraph executables, the steps each one carries, the device-side optimizer state (and its
+  // pinned staging copy), and the optimizer kind / amsgrad flag each capture recorded (-1: no update step) -- a graph is replayed only
+  // with the kind it holds
   std::vector<hipGraphExec_t> graphs; std::vector<int> graph_steps; bool capturing = false; int cap_steps = 0; long cap_step0 = 0;
-  AdamDev* adam_dev = nullptr; AdamDev* adam_host = nullptr;
-  // Lion / AdaBelief (nif_opt_step_dev): AdaBelief's amsgrad slot (allocated on first use), the device-side state of captured steps, and
-  // the optimizer kind / amsgrad flag each capture recorded (-1: no update step) -- a graph is replayed only with the kind it holds
-  float* vhat = nullptr;
   OptDev* opt_dev = nullptr; OptDev* opt_host = nullptr;
+  float* vhat = nullptr;       // AdaBelief's amsgrad slot, allocated on first use
   int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
   // magnitude pruning (nif_prune_*): the segment table (host copy: the k of the last update), its span [prune_lo, prune_hi), a byte mask
   // over the whole of theta (1 outside the segments), the thresholds and the select's histograms / per-segment state
@@ -105,7 +104,7 @@ struct nif_ctx {
   int* small_idx = nullptr; int* small_desc = nullptr;     // k_small's tables (offsets only), built at the first small step
   bool metric_pending = false; float metric_pending_w = 0.f;   // a nif_metric_accumulate deferred into the next k_small launch
   bool last_step_small = false;
-  // r6: the row reduction of a plain step may wait for its consumer -- nif_adam_step_dev then runs it fused with the update (one launch
+  // r6: the row reduction of a plain step may wait for its consumer -- the optimizer step then runs it fused with the update (one launch
   // less per step); every other entry point of the library runs it first (tail_flush).  nif_set_option("fuse_tail") / NIF_FUSE_TAIL
   bool tail_pending = false; int tail_rows = 0, tail_nloss = 0; bool opt_fuse_tail = true;
   bool opt_small_step = true;      // nif_set_option("small_step"): batches <= NIF_SMALL_MAX_B points of a net k_small takes run on it (one launch for loss + gradient); default from NIF_SMALL_STEP
@@ -131,7 +130,7 @@ struct ProfScope {
 
 // host batch -> this context's staging buffers (asynchronous H2D on c->st); used by the host-pointer entry points
 int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, float** dx, float** dy, float** dsw);
-// the deferred row reduction of the last plain step (nif_ctx::tail_pending), run before anything but nif_adam_step_dev touches
+// the deferred row reduction of the last plain step (nif_ctx::tail_pending), run before anything but the optimizer step touches
 // [grad | loss], the partial rows or the weights (nif_api.hip)
 int nif_tail_flush(nif_ctx* c);
 #define TAIL_FLUSH(c_) { const int rct_ = nif_tail_flush(c_); if (rct_) return rct_; }

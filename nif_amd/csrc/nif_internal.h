@@ -261,14 +261,9 @@ void launch_reduce(const float* partial, long pstride, int rows, const float* lo
                    float* g, long P, hipStream_t st);
 void launch_reg(const float* theta, float* g, long lo, long hi, long P, float l1, float l2, hipStream_t st);
 void launch_metric(const float* g, long P, float weight, double* acc, hipStream_t st);
-void launch_reduce_adam(const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g, long P,
-                        float* theta, float* m, float* v, float lr_t, float b1, float b2, float eps, hipStream_t st);
-struct AdamDev { float lr, beta1, beta2, eps; long step; };      // device-resident Adam state of a captured graph of steps (k_adam_dev)
-void launch_adam_dev(float* theta, const float* g, float* m, float* v, long P, AdamDev* ad, hipStream_t st);
-void launch_adam(float* theta, const float* g, float* m, float* v, long P, float lr_t, float b1, float b2,
-                 float eps, hipStream_t st);
-// Lion / AdaBelief (k_opt.hip, include/nif_hip.h nif_opt_step_dev).  OptDev: the hyper-parameters of a nif_opt and the iteration count,
-// in device memory for a captured graph of steps (as AdamDev); the host forms the same scalars from the same struct for eager steps.
+// the optimizer updates (k_opt.hip, include/nif_hip.h nif_adam_step_dev / nif_opt_step_dev).  OptDev: the hyper-parameters of a nif_opt
+// and the iteration count, in device memory for a captured graph of steps; the host forms the same scalars from the same struct for
+// eager steps.
 enum { OPT_ADAM = 0, OPT_LION = 1, OPT_ADABELIEF = 2 };
 enum { OPT_RECTIFY = 1, OPT_AMSGRAD = 2 };
 struct OptDev { int kind, flags; float lr, beta1, beta2, eps, wd, decay, sma_threshold, warmup_proportion, min_lr; long total_steps; long step; };
@@ -303,11 +298,11 @@ __host__ __device__ inline OptScalars opt_scalars(const OptDev& o, long t_) {
   s.lr = lr;
   return s;
 }
-// what one update kernel receives (floats; the fp64 scalars rounded once)
+// what one update kernel receives (floats; the fp64 scalars rounded once).  Adam's lr is its step size lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
 struct OptArgs { float lr, b1, b2, eps, wd, bc1, bc2, r; int div; };
 __host__ __device__ inline OptArgs opt_args(const OptDev& o, const OptScalars& s) {
   OptArgs a;
-  a.lr = (float)s.lr; a.b1 = o.beta1; a.b2 = o.beta2; a.eps = o.eps; a.wd = o.wd;
+  a.lr = (float)(o.kind == OPT_ADAM ? s.lr * sqrt(s.bc2) / s.bc1 : s.lr); a.b1 = o.beta1; a.b2 = o.beta2; a.eps = o.eps; a.wd = o.wd;
   a.bc1 = (float)s.bc1; a.bc2 = (float)s.bc2; a.r = (float)s.r; a.div = s.div;
   return a;
 }

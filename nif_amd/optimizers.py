@@ -1,6 +1,6 @@
 """Optimizers accepted by Model.compile.  The hot path uses stock Keras-2.11 Adam (README.md:33;
-SURVEY a-11); the update itself is the k_adam HIP kernel.  The reference's Lion and AdaBeliefOptimizer
-(nif/optimizers/__init__.py) run on the k_opt.hip kernels."""
+SURVEY a-11); the reference's Lion and AdaBeliefOptimizer (nif/optimizers/__init__.py) are the other two kinds.  All three
+update on the k_opt.hip kernels (k_opt, k_reduce_opt, k_opt_dev)."""
 import numbers
 
 import numpy as np
@@ -65,7 +65,7 @@ class _LrProperty(object):
 
 
 class Lion(_LrProperty):
-    """nif.optimizers.Lion (reference nif/optimizers/external_optimizers.py:631-735), updated by the k_lion kernels:
+    """nif.optimizers.Lion (reference nif/optimizers/external_optimizers.py:631-735), updated by the k_opt.hip kernels:
     theta -= lr_d (sign(b1 m + (1-b1) g) + wd theta), then m = b2 m + (1-b2) g; lr_d = lr / (1 + decay (t - 1))."""
     kind = _lib.OPT_LION
     amsgrad = False
@@ -88,7 +88,7 @@ class Lion(_LrProperty):
 
 
 class AdaBeliefOptimizer(_LrProperty):
-    """nif.optimizers.AdaBeliefOptimizer (reference nif/optimizers/external_optimizers.py:322-628), updated by the k_adabelief kernels:
+    """nif.optimizers.AdaBeliefOptimizer (reference nif/optimizers/external_optimizers.py:322-628), updated by the k_opt.hip kernels:
     Adam on the belief (g - m)^2, optional rectification (RAdam) behind sma_threshold, AMSGrad, weight_decay * theta added to the
     step, and a warm-up / linear decay of the learning rate over total_steps.  epsilon 0 becomes Keras' 1e-7."""
     kind = _lib.OPT_ADABELIEF

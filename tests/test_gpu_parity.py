@@ -1983,7 +1983,7 @@ def test_small_batch_step_matches_oracle_and_tile_kernels(name, weighted):
 
 
 def test_small_batch_fit_follows_the_oracle_adam_steps():
-    """Model.fit at configs[0]'s shape (batch 512 of a 2 000-point table, no shuffle): four Adam steps through k_small + k_reduce + k_adam
+    """Model.fit at configs[0]'s shape (batch 512 of a 2 000-point table, no shuffle): four Adam steps through k_small + k_reduce + k_opt
     against the oracle's Keras-2.11 updates, teacher-forced per step as in test_adam_steps_follow_oracle"""
     import nif_amd
     m, model, spec, ws, x, y, sw = _make((_cfg("NIF", 32, 2, 32, 2, 1, 1, 1, 1), 2000))

@@ -1,5 +1,5 @@
-"""The deferred row reduction of a plain step (r6: nif_adam_step_dev runs it fused with the update, k_reduce_adam; every other entry point of
-the library runs it first).  Same summation order and update expressions as k_reduce + k_adam: the two forms must agree bit for bit, and no
+"""The deferred row reduction of a plain step (r6: nif_adam_step_dev runs it fused with the update, k_reduce_opt; every other entry point of
+the library runs it first).  Same summation order and update expressions as k_reduce + k_opt: the two forms must agree bit for bit, and no
 API order may see a stale [grad | loss] buffer."""
 import numpy as np
 import pytest

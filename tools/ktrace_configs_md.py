@@ -6,6 +6,7 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +27,8 @@ def main(tag):
                     rec = json.loads(line.partition(" ")[2])
         except OSError:
             pass
-        steps = max(int(r["Calls"]) for r in rows if r["Name"].startswith("k_adam"))
+        # every step runs one optimizer update: k_opt, k_reduce_opt (the fused tail) or k_opt_dev (captured); k_opt_step_inc not counted
+        steps = sum(int(r["Calls"]) for r in rows if re.match(r"(void )?k_(reduce_)?opt(_dev)?<", r["Name"]))
         head = "## %s" % cfg
         if rec:
             head += " — %d points, %.3f ms / step under the tracer (%.1f M points/s)" % (rec["points"], rec["ms_per_step"], rec["Mpts_per_s"])
