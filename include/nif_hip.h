@@ -216,6 +216,19 @@ int nif_sobolev_loss_grad_dev(nif_ctx* ctx, const float* xin_dev, const float* y
 int nif_sobolev_loss_grad_dev_y(nif_ctx* ctx, const float* xin_dev, const float* y_dev, const float* dydx_dev,
                                 const float* sw_dev_or_null, int64_t B_local, int64_t B_global, const int32_t* x_idx,
                                 int32_t nx, const int32_t* y_idx_or_null, int32_t ny, float w_jac);
+/* Second-order Sobolev training: the Keras model  Model(x, HessianLayer(nif, y_index, x_index)(x))  -- outputs (u, du/dx, d2u/dx2),
+ * compiled with one loss and loss_weights=[1, w_jac, w_hess] (nif/layers/gradient.py:130-180, :234-261 used as a trainable output;
+ * Keras differentiates through both nested tapes).  loss = 1/B sum_a sw_a (mean_i l(u - y) + w_jac mean_{i in Y, j} l(J - G)
+ * + w_hess mean_{i in Y, j, k} l(H - T)) with d2ydx2_dev rows [so][nx][nx] (T need not be symmetric: both (j, k) and (k, j) enter the
+ * mean), dydx_dev rows [so][nx]; y_idx / the loss kind / the regularisers as nif_sobolev_loss_grad_dev_y.  Pass 0 is that first-order
+ * step, then one second-order pass (k_sob<.., HESS>) per coordinate pair j <= k, nx (nx + 1) / 2 of them, whose [grad | loss] add up.
+ * Built for NIFMultiScale (with or without resblocks) and the last-layer class, coordinate columns in x_idx, policy float32; class NIF,
+ * parameter columns, mixed policies and shapes whose working set exceeds one CU's LDS return NIF_ERR_INVALID.  Not capturable: inside
+ * nif_graph_begin / nif_graph_end it returns NIF_ERR_STATE.  Same conventions as nif_loss_grad_dev (nif_grad_dev(), 1/B_global). */
+int nif_sobolev2_loss_grad_dev(nif_ctx* ctx, const float* xin_dev, const float* y_dev, const float* dydx_dev,
+                               const float* d2ydx2_dev, const float* sw_dev_or_null, int64_t B_local, int64_t B_global,
+                               const int32_t* x_idx, int32_t nx, const int32_t* y_idx_or_null, int32_t ny,
+                               float w_jac, float w_hess);
 /* predict() of that two-output model: u [B,so] and du/dx [B,so,nx], device pointers */
 int nif_sobolev_forward_dev(nif_ctx* ctx, const float* xin_dev, int64_t B, const int32_t* x_idx, int32_t nx, float* u_dev,
                             float* dudx_dev);

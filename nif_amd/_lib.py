@@ -115,6 +115,8 @@ SIGNATURES = {
                                             C.c_float]),
     "nif_sobolev_loss_grad_dev_y": (C.c_int, [_CTX, _VP, _VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32,
                                               C.POINTER(C.c_int32), C.c_int32, C.c_float]),
+    "nif_sobolev2_loss_grad_dev": (C.c_int, [_CTX, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32,
+                                             C.POINTER(C.c_int32), C.c_int32, C.c_float, C.c_float]),
     "nif_graph_begin": (C.c_int, [_CTX]),
     "nif_graph_end": (C.c_int, [_CTX, C.POINTER(C.c_int32)]),
     "nif_graph_launch": (C.c_int, [_CTX, C.c_int32, C.POINTER(nif_adam)]),

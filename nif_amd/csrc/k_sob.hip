@@ -10,6 +10,8 @@ int launch_sob(const SNetArgs& a, bool train, int ns, const int* seeds, const fl
                bool query_only, hipStream_t st, const SobPar* par) {
   bool any_par = false;
   if (par) for (int d = 0; d < ns; ++d) any_par = any_par || par->par[d] >= 0;
+  const bool hess = par && par->hess;     // second-order pair pass (k_sob_hess.hip): 3 streams + coordinate seeds, training only
+  if (hess && (!train || ns != NIF_SOB_MAXSEED || any_par)) return -1;
   const int NBL = snet3_nbl(a.n);
   const long nt16 = 2 * ((a.B + 31) / 32);
   long ngroups = (nt16 + 3) / 4;
@@ -18,7 +20,7 @@ int launch_sob(const SNetArgs& a, bool train, int ns, const int* seeds, const fl
   // and what still falls back to k_sob (NIF_SOBW=0, exchange tiles beyond the LDS) runs the general 3-stream form
   const bool slim = false, two = false;
   (void)bf_;
-  const bool wav = sobw_supported(a, ns, any_par);      // k_sobw.hip: one 12-wave (65..128 units: 8-wave) workgroup per CU; r4: predict() too
+  const bool wav = !hess && sobw_supported(a, ns, any_par);      // k_sobw.hip: one 12-wave (65..128 units: 8-wave) workgroup per CU; r4: predict() too
   if (wav) ngroups = (nt16 + sobw_tiles_per_group(a.n, ns) - 1) / sobw_tiles_per_group(a.n, ns);
   const long cap = wav ? sobw_grid_cap() : (two ? 512 : (NBL <= 4 ? 256 * NIF_SOB_OCC : 256));
   const int nblk = (int)(ngroups < cap ? ngroups : cap);
@@ -79,10 +81,12 @@ int launch_sob(const SNetArgs& a, bool train, int ns, const int* seeds, const fl
     const size_t llw = (size_t)(2 * a.rl + (1 + NIF_SOB_MAXSEED) * (a.so + a.so_u) + NIF_SOB_MAXSEED * (2 * a.rl + a.so_u)) * 16;
     size_t shm_ll = shm + 4 * llw * sizeof(float);
     if (!one_buf && shm_ll > 160u * 1024u && 4 * llw <= plane) { J.ll_plane = 1; shm_ll = shm; }   // scratch in the idle plane buffer
-    launch_sob_ll(J, train, bf, nblk, shm_ll, st);
+    if (hess) launch_sob_hess(J, bf, nblk, shm_ll, st);
+    else launch_sob_ll(J, train, bf, nblk, shm_ll, st);
     return nblk;
   }
   if (any_par) { launch_sob_par(J, train, bf, nblk, shm, st); return nblk; }
+  if (hess) { launch_sob_hess(J, bf, nblk, shm, st); return nblk; }
 #define SBL(NBL_, MODE_, TR_, BF_, SGN_)                                                                            \
   {                                                                                                             \
     if (shm > 48 * 1024)                                                                                        \

@@ -17,6 +17,16 @@
 //     lambda_in += w0 sum_k zt'_k M^(k) nu ,   dL/dzt'_k = w0 <h_in, M^(k) nu> + <nu, b^(k)>
 //     dL/dM^(k) += w0 sum_p zt'_k h_in nu^T ,  dL/db^(k) += sum_p zt'_k nu   -> a second reduction over (h_in, nu) with zt'
 //                                                                               in the latent's place (nif_api.hip)
+// HESS (k_sob_hess.hip): the second-order step of HessianLayer as a trained output (reference nif/layers/gradient.py:130-180,
+// :234-261).  Streams 0: primal, 1 / 2: tangents of the coordinate pair (j, k) (seeds 0 / 1; j = k runs stream 2 as a second copy
+// of stream 1, which is the same graph), 3: the second-order stream, no seed (a'' = 0 at the first layer).  Forward as k_jac<HESS>:
+//     a'' = w0 W h'' ,  h'' = c a'' - s a'_j a'_k            (the ring's three tangent slots hold a'_j, a'_k, a'')
+// adjoint with kappa = dL/dh'':
+//     nu''  = kappa c ,  nu_j = mu_j c - kappa s a'_k ,  nu_k = mu_k c - kappa s a'_j
+//     da    = lambda c - s (mu_j a'_j + mu_k a'_k) - kappa (s a'' + c a'_j a'_k)
+// and the MFMA planes, dz and the weight-gradient pseudo-tiles see one more linear stream, unchanged.  The loss is the second-order
+// term alone (the host's pass 0 is the first-order step): sum over the target entries (j, k) and (k, j) of d2ydx2 [B][so][nx][nx]
+// (gcol[0] / gcol[1] = positions of j / k in x_index, gstride = nx), weighted wjn = w_hess / (ny nx nx)
 #pragma once
 #include "k_snet3_dev.h"
 
@@ -66,6 +76,8 @@ int sobw_tiles_per_group(int n, int ns);
 int sobw_grid_cap();
 // last-layer class (k_sob_ll.hip)
 void launch_sob_ll(const SobArgs& J, bool train, bool bf, int nblk, size_t shm, hipStream_t st);
+// second-order pair pass of both hypernetwork and last-layer classes (k_sob_hess.hip)
+void launch_sob_hess(const SobArgs& J, bool bf, int nblk, size_t shm, hipStream_t st);
 
 // BF: n x n products as exact bf16 splits on v_mfma_f32_16x16x32_bf16 (forward 6-product, adjoint 3-product form, see
 // k_snet4.hip), whole bf16 planes per LDS step; otherwise the f32-input MFMA planes (odd block counts, n = 128)
@@ -74,6 +86,19 @@ void launch_sob_ll(const SobArgs& J, bool train, bool bf, int nblk, size_t shm, 
 // the ring was 5 blocks written + 5 read per layer, now ns written + ns read and one stash read
 // (h, c, sn) of a pre-activation tile: SIREN: (sin, cos, sin); class NIF (MODE 2): (f, f', -f'') of the runtime activation, so that
 // the adjoint formulas  nu = mu c ,  da = lambda c - sum mu sn a'  hold for both
+// HESS: loss of the second-order output h against T[j][k] and, for j != k, T[k][j] (both entries are in the Keras mean); returns
+// dL/dh per unit weight and adds the loss to v
+__device__ __forceinline__ float sob_hess_loss(int kind, float h, const float* trow, int gs, int j, int k, float& v) {
+  const float e1 = h - trow[j * gs + k];
+  NIF_LOSS_ACC(kind, e1, v, df1)
+  if (j != k) {
+    const float e2 = h - trow[k * gs + j];
+    NIF_LOSS_ACC(kind, e2, v, df2)
+    df1 += df2;
+  }
+  return df1;
+}
+
 template <int NBL, int MODE>
 __device__ __forceinline__ void sob_act(int act, const f32x4 (&a)[NBL], f32x4 (&h)[NBL], f32x4 (&c)[NBL], f32x4 (&sn)[NBL], int n, int g) {
   if (MODE != 2) {
@@ -89,6 +114,18 @@ __device__ __forceinline__ void sob_act(int act, const f32x4 (&a)[NBL], f32x4 (&
   }
 }
 
+// HESS: the adjoint of one pre-activation block (header formulas); lam / vq = (lambda, mu_j, mu_k, kappa) / (da, nu_j, nu_k, nu'')
+template <int NQ, int NBL>
+__device__ __forceinline__ void sob_hess_adj(const f32x4 (&lam)[NQ][NBL], f32x4 (&vq)[NQ][NBL], int b, f32x4 c, f32x4 sn, f32x4 a1,
+                                             f32x4 a2, f32x4 a3) {
+  static_assert(NQ == 4, "the second-order step carries four streams");
+  const f32x4 ks = lam[3][b] * sn;
+  vq[1][b] = lam[1][b] * c - ks * a2;
+  vq[2][b] = lam[2][b] * c - ks * a1;
+  vq[3][b] = lam[3][b] * c;
+  vq[0][b] = lam[0][b] * c - sn * (lam[1][b] * a1 + lam[2][b] * a2) - lam[3][b] * (sn * a3 + c * a1 * a2);
+}
+
 // BF: 0 = f32-input MFMA planes, 1 = exact bf16 splits, 2 = one bf16 product (mixed_bfloat16 policy)
 // NSD: seed streams the instantiation carries (register arrays and loops are sized by it): 1 or 2 seeds at n <= 64 leave room
 // for TWO workgroups per CU (256 registers), the 3-seed form needs all 512
@@ -96,7 +133,7 @@ __device__ __forceinline__ void sob_act(int act, const f32x4 (&a)[NBL], f32x4 (&
 // (fill_snet_ll: r = 0, one shared plane per layer, so = so_u * rl outputs phi, Z = the ParameterNet output a [tiles][rl][32]).
 // u_i = sum_c phi[i*rl+c] a_c + bias_i and du_i/dx_d = sum_c phi'_d[i*rl+c] a_c; the adjoint starts from dphi = du (x) a,
 // dphi'_d = du'_d (x) a and also yields dL/da (and dL/dlatent through the rl x rl map of the ParameterNet's last layer).
-template <int NBL, int MODE, bool TRAIN, int BF, bool SGN, int NSD = NIF_SOB_MAXSEED, bool PAR = false, bool LL = false>
+template <int NBL, int MODE, bool TRAIN, int BF, bool SGN, int NSD = NIF_SOB_MAXSEED, bool PAR = false, bool LL = false, bool HESS = false>
 __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD == 1)) ? 2 : (NBL <= 4 ? NIF_SOB_OCC : 1)) void k_sob(SobArgs J) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const SNetArgs& A = J.s;
@@ -257,7 +294,7 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
 #pragma unroll
         for (int d = 0; d < NS; ++d) {
           if (PAR && ispar[d]) { if (k < r) aq[1 + d][b] += ztd_base[(d * r + k) * 16] * t0; }
-          else if (d < ns) aq[1 + d][b] += (zt * A.omega) * *reinterpret_cast<const f32x4*>(s0 + o_w1 + J.seed[d] * NP + 16 * b);
+          else if (d < ns && !(HESS && d == 2)) aq[1 + d][b] += (zt * A.omega) * *reinterpret_cast<const f32x4*>(s0 + o_w1 + J.seed[d] * NP + 16 * b);
         }
       }
     }
@@ -271,6 +308,7 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
         for (int d = 0; d < NS; ++d) {
           if (TRAIN && d < ns) ring[(2 + d) * NBL * 64 + b * 64 + lane] = aq[1 + d][b];
           hq[1 + d][b] = c[b] * aq[1 + d][b];
+          if (HESS && d == 2) hq[3][b] -= sn0[b] * aq[1][b] * aq[2][b];        // h'' = c a'' - s a'_j a'_k
         }
       }
       if (TRAIN && SGN) sgn_push(sg_lo, sg_hi, sgn_pack<NBL>(c), 4 * NBL);
@@ -363,7 +401,8 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
       for (int q = 0; q < NQ; ++q)
 #pragma unroll
         for (int b = 0; b < NBL; ++b) {
-          const f32x4 t = q == 0 ? sn[b] : c[b] * aq[q][b];   // f(a) | f'(a) a'
+          f32x4 t = q == 0 ? sn[b] : c[b] * aq[q][b];         // f(a) | f'(a) a'
+          if (HESS && q == 3) t -= snr[b] * aq[1][b] * aq[2][b];
           if (MODE == 0) hq[q][b] = t;
           else if (MODE == 2) hq[q][b] += t;                   // class NIF: h = f(a) + h_in
           else if (!(j & 1)) { ub[q][b] = hq[q][b]; hq[q][b] = t; }
@@ -459,7 +498,14 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
 #pragma unroll
           for (int d = 0; d < NS; ++d) {
             dq[1 + d] = 0.f;
-            if (d < ns) {
+            if (HESS) {
+              if (d == 2) {
+                float vj = 0.f;
+                const float dfh = sob_hess_loss(A.loss_kind, uq[3], J.gt + (ptc * sou + i) * nxt * nxt, nxt, J.gcol[0], J.gcol[1], vj);
+                sej = fmaf(ysel, vj, sej);
+                dq[3] = ysel * dfh * J.wjn * wsamp * A.inv_bg;
+              }
+            } else if (d < ns) {
               const float ej = uq[1 + d] - J.gt[(ptc * sou + i) * nxt + J.gcol[d]];
               float vj = 0.f;
               NIF_LOSS_ACC(A.loss_kind, ej, vj, dfj)
@@ -609,7 +655,15 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
 #pragma unroll
         for (int d = 0; d < NS; ++d) {
           dq[1 + d] = 0.f;
-          if (d < ns) {
+          if (HESS) {
+            if (d == 2) {
+              float vj = 0.f;
+              const int gs = J.gstride;
+              const float dfh = sob_hess_loss(A.loss_kind, part[3], J.gt + (ptc * so + o) * gs * gs, gs, J.gcol[0], J.gcol[1], vj);
+              sej = fmaf(ysel, vj, sej);
+              dq[3] = ysel * dfh * J.wjn * wsamp * A.inv_bg;
+            }
+          } else if (d < ns) {
             const float ej = part[1 + d] - J.gt[(ptc * so + o) * J.gstride + J.gcol[d]];
             float vj = 0.f;
             NIF_LOSS_ACC(A.loss_kind, ej, vj, dfj)
@@ -695,6 +749,11 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
 #pragma unroll
         for (int b = 0; b < NBL; ++b) {
           const f32x4 c = cv[b], sn = snv[b];
+          if constexpr (HESS) {
+            sob_hess_adj(lam, vq, b, c, sn, rl[2 * NBL * 64 + b * 64 + lane], rl[3 * NBL * 64 + b * 64 + lane],
+                         rl[4 * NBL * 64 + b * 64 + lane]);
+            continue;
+          }
           f32x4 da = lam[0][b] * c;
 #pragma unroll
           for (int d = 0; d < NS; ++d) {
@@ -804,6 +863,11 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
 #pragma unroll
         for (int b = 0; b < NBL; ++b) {
           const f32x4 c = cv[b], sn = snv[b];
+          if constexpr (HESS) {
+            sob_hess_adj(lam, vq, b, c, sn, ring[2 * NBL * 64 + b * 64 + lane], ring[3 * NBL * 64 + b * 64 + lane],
+                         ring[4 * NBL * 64 + b * 64 + lane]);
+            continue;
+          }
           f32x4 da = lam[0][b] * c;
 #pragma unroll
           for (int d = 0; d < NS; ++d) {
@@ -833,7 +897,7 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
             for (int d = 0; d < NS; ++d)
               if (PAR && ispar[d]) {
                 sd[d] += (vq[1 + d][b][0] * t[0] + vq[1 + d][b][1] * t[1]) + (vq[1 + d][b][2] * t[2] + vq[1 + d][b][3] * t[3]);
-              } else if (d < ns) {
+              } else if (d < ns && !(HESS && d == 2)) {
                 const f32x4 wd = A.omega * *reinterpret_cast<const f32x4*>(s0 + o_w1 + J.seed[d] * NP + 16 * b);
                 s += (vq[1 + d][b][0] * wd[0] + vq[1 + d][b][1] * wd[1]) + (vq[1 + d][b][2] * wd[2] + vq[1 + d][b][3] * wd[3]);
               }

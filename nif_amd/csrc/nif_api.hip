@@ -19,7 +19,8 @@ static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int
 // Sobolev streams of one x_index: coordinate seeds first, then the parameter seeds (their pseudo-tiles trail the stashes, so
 // that the first-layer reduction simply stops in front of them); gcol = the x_index position (column of dydx) of each stream
 struct SobPlan { int ns, nsc; int seeds[3]; int par[3]; int gcol[3]; bool any_par;
-                 int gstride, nx_all, ny, no_primal; unsigned ymask; };      // r4: one group of the x_index columns / a y_index subset (SobPar)
+                 int gstride, nx_all, ny, no_primal; unsigned ymask;
+                 int hess; };      // 1: a second-order pair pass (nif_sobolev2_loss_grad_dev, SobPar::hess)      // r4: one group of the x_index columns / a y_index subset (SobPar)
 static int sob_par_pass(nif_ctx* c, const float* xin, long B, long Bg, const SobPlan& sp, const SNetArgs& sa);
 static int fill_snet_ll_sob(nif_ctx* c, SNetArgs& sa, const float* xin, long B, bool f32_planes = false);
 
@@ -206,7 +207,7 @@ extern "C" int nif_destroy(nif_ctx* c) {
   for (hipEvent_t e : c->ev_chunk) hipEventDestroy(e);
   for (hipGraphExec_t ex : c->graphs) if (ex) (void)hipGraphExecDestroy(ex);
   if (c->opt_host) (void)hipHostFree(c->opt_host);
-  void* ptrs[] = {c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
+  void* ptrs[] = {c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->sob2_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
                   c->DU, c->ZL, c->partial, c->loss_partial, c->dring, c->metric, c->tl, c->lWF, c->lWB, c->sWF4, c->sWB4, c->sWF4x, c->sWB4x, c->sWscale, c->sWF4h, c->sWB4h, c->ll_slots, c->ll_wpf, c->ll_wpb, c->stash_l, c->PHI, c->DPHI, c->DA, c->DZL, c->d_a, c->d_b, c->d_c, c->d_d};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->st) hipStreamDestroy(c->st);
@@ -1066,13 +1067,17 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   if (ns > 0) {   // Sobolev: primal + tangents + their adjoint on k_sob<.., LL>; stashes and DPHI hold (1 + ns) blocks of tiles
     SNetArgs sa; int rc = fill_snet_ll_sob(c, sa, xin, B); if (rc) return rc;
     sa.y = y; sa.sw = sw; sa.loss_partial = c->loss_partial; sa.inv_bg = 1.0f / (float)Bg;
-    nloss = launch_sob(sa, true, nsc, sp->seeds, nullptr, 0.f, nullptr, nullptr, true, c->st);
+    SobPar spq{};
+    for (int d = 0; d < 3; ++d) spq.par[d] = -1;
+    spq.hess = sp->hess;
+    nloss = launch_sob(sa, true, nsc, sp->seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spq);
     if (nloss < 0) return fail(NIF_ERR_INVALID, "Sobolev step: the kernel's working set of this shape does not fit the 160 KB LDS of a CU");
     const long need = (long)nloss * 4 * sob_ring_floats_per_wave(c->n, c->nh);
     if (need > c->dring_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->dring, &c->dring_cap, need); if (rc) return rc; }
     SobPar spar{};
     for (int d = 0; d < 3; ++d) { spar.par[d] = -1; spar.gcol[d] = sp->gcol[d]; }
     spar.gstride = sp->gstride; spar.nx_all = sp->nx_all; spar.ny = sp->ny; spar.no_primal = sp->no_primal; spar.ymask = sp->ymask;
+    spar.hess = sp->hess;
     if (nhead > 0) {     // parameter columns: heads of the epilogue (z' = dz/dp sits in c->zt_par, loss_grad_core)
       const long need_a = 3 * ntiles * 32 * c->r, need_l = 3 * ntiles * 32 * 32 * c->RB;
       if (need_a > c->dat_par_cap || need_l > c->ztl_par_cap) HIPCHK(hipStreamSynchronize(c->st));
@@ -1146,6 +1151,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     };
     // ShapeNet (dense SIREN): first, hidden matrices, bottleneck (n -> r*so), last_layer_bias
     sbase(g); g.DA = sST + (long)(nms + 1) * c->slot_s; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.scale = ma.omega;
+    if (ns > 0 && sp->hess) g.ntiles = ntiles * 3;      // (the second-order stream has no first-layer input: a'' = 0 there)
     g.W = dense_ref(c->s_first_w, c->si, c->n); g.Bv = vec_ref(c->s_first_b, c->n);
     launch_gw_first(g, c->NB, rows, c->st);
     for (int mi = 0; mi < nms; ++mi) {
@@ -1219,11 +1225,12 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
 // Workspace sizing of the fused ShapeNet kernel the step will launch (no launch): number of workgroups (= loss partials),
 // the act'(a) ring, the optional edge-gradient partials.  Grows buffers when needed (stream sync + hipMalloc): call
 // nif_reserve() once up front to keep that out of the timed steps.
-static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nloss, const int* par_of = nullptr) {
+static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nloss, const int* par_of = nullptr, bool hess = false) {
   int rc;
   if (ns > 0) {
     SobPar spq{};     // (the parameter streams' extra per-wave LDS counts)
     for (int d = 0; d < 3; ++d) spq.par[d] = par_of ? par_of[d] : -1;
+    spq.hess = hess ? 1 : 0;
     const int nblk = launch_sob(sa, true, ns, seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spq);
     if (nblk < 0)
       return fail(NIF_ERR_INVALID, "Sobolev step: the kernel's working set of this shape (units, latent_dim, parameter columns) does not fit the 160 KB LDS of a CU");
@@ -1315,7 +1322,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   sa.y = y; sa.sw = sw; sa.u_out = nullptr; sa.loss_partial = loss_partial; sa.inv_bg = 1.0f / (float)Bg;
   if (!whole) sa.wg_cap = c->opt_pipe_wgs;        // leave room on every CU for the reductions of the previous chunk
   int nloss = (int)((ntiles + 3) / 4);
-  rc = snet_plan(c, sa, ns, seeds, &nloss, sp ? sp->par : nullptr); if (rc) return rc;
+  rc = snet_plan(c, sa, ns, seeds, &nloss, sp ? sp->par : nullptr, sp && sp->hess); if (rc) return rc;
   // plain SIREN step on the bf16-split kernel: every ShapeNet weight gradient inside the training kernel (k_snet6) -- its workgroups
   // are the partial-gradient rows, so the row count of this step has to be the kernel's grid
   const bool fused_gw = ns == 0 && whole && c->use_snet4 && c->opt_fuse_gw && snet6_supported(sa) &&
@@ -1342,7 +1349,8 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
     ProfScope p_(c, NIF_PROF_SNET, sa_st);
     if (ns > 0) {
       SobPar spar{}; const SobPar* sparp = nullptr;
-      if (sp) { spar.gstride = sp->gstride; spar.nx_all = sp->nx_all; spar.ny = sp->ny; spar.no_primal = sp->no_primal; spar.ymask = sp->ymask; }
+      if (sp) { spar.gstride = sp->gstride; spar.nx_all = sp->nx_all; spar.ny = sp->ny; spar.no_primal = sp->no_primal; spar.ymask = sp->ymask;
+                spar.hess = sp->hess; }
       if (sp && sp->any_par) {
         for (int d = 0; d < 3; ++d) { spar.par[d] = sp->par[d]; spar.gcol[d] = sp->gcol[d]; }
         spar.ZT = c->zt_par; spar.DZT = c->dzt_par; sparp = &spar;
@@ -1397,6 +1405,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   g.W = hyper_ref(c, 0, c->n, c->si, c->n);
   g.Bv = hyper_ref(c, (long)c->si * c->n + (long)c->nh * c->n * c->n + (long)c->n * c->so, 0, 1, c->n);
   if (sp) g.ntiles = ntiles * (1 + sp->nsc);      // a parameter stream has no tangent input here (x' = 0): its pairs go to sob_par_pass
+  if (sp && sp->hess) g.ntiles = ntiles * 3;      // nor has the second-order stream (a'' = 0 at the first layer)
   launch_gw_first(g, c->NB, rows, sb_st);
   // ShapeNet hidden matrices
   for (int j = 0; j < c->nh; ++j) {
@@ -1735,6 +1744,50 @@ extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const f
 extern "C" int nif_sobolev_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, const float* dydx, const float* sw,
                                          int64_t B, int64_t Bg, const int32_t* x_idx, int32_t nx, float w_jac) {
   return nif_sobolev_loss_grad_dev_y(c, xin, y, dydx, sw, B, Bg, x_idx, nx, nullptr, 0, w_jac);
+}
+// Second-order Sobolev step (HessianLayer as a trained output, gradient.py:130-180, :234-261): pass 0 is the first-order step above
+// (u, du/dx and every regulariser), then one k_sob<.., HESS> pass per unordered coordinate pair j <= k with the primal and first-order
+// terms off; the passes' [grad | loss] add up in sob2_acc
+extern "C" int nif_sobolev2_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, const float* dydx, const float* d2ydx2,
+                                          const float* sw, int64_t B, int64_t Bg, const int32_t* x_idx, int32_t nx,
+                                          const int32_t* y_idx, int32_t ny, float w_jac, float w_hess) {
+  if (!c || !xin || !y || !dydx || !d2ydx2 || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
+  static const char* built = "built: NIFMultiScale (SIREN, with or without resblocks) and NIFMultiScaleLastLayerParameterized, "
+                             "coordinate columns in x_index, policy float32";
+  if (c->kind == NIF_KIND_NIF) return fail(NIF_ERR_INVALID, std::string("second-order Sobolev step: class NIF is not built (") + built + ")");
+  if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
+    return fail(NIF_ERR_INVALID, std::string("second-order Sobolev step: mixed precision policies are not built (") + built + ")");
+  unsigned ymask; int nys;
+  int rc = sobolev_check(c, x_idx, nx, y_idx, ny, &ymask, &nys); if (rc) return rc;
+  for (int d = 0; d < nx; ++d)
+    if (x_idx[d] < c->pi)
+      return fail(NIF_ERR_INVALID, std::string("second-order Sobolev step: parameter columns in x_index are not built (") + built + ")");
+  if (c->capturing) return fail(NIF_ERR_STATE, "second-order Sobolev step inside a graph capture (not supported: run it uncaptured)");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  rc = nif_sobolev_loss_grad_dev_y(c, xin, y, dydx, sw, B, Bg, x_idx, nx, y_idx, ny, w_jac); if (rc) return rc;
+  if (!c->sob2_acc) HIPCHK(hipMalloc(&c->sob2_acc, sizeof(float) * (size_t)(c->P + 1)));
+  HIPCHK(hipMemcpyAsync(c->sob2_acc, c->grad, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
+  const float jac_l1 = c->jac_l1, act_l1 = c->act_l1, act_l2 = c->act_l2;
+  c->jac_l1 = 0.f; c->act_l1 = 0.f; c->act_l2 = 0.f;      // the regularisation losses belong to pass 0
+  for (int j = 0; j < nx && !rc; ++j)
+    for (int k = j; k < nx && !rc; ++k) {
+      SobPlan sp;
+      memset(&sp, 0, sizeof(sp));
+      sp.ns = 3; sp.nsc = 3; sp.hess = 1;
+      sp.seeds[0] = x_idx[j] - c->pi; sp.seeds[1] = x_idx[k] - c->pi; sp.seeds[2] = 0;
+      for (int q = 0; q < 3; ++q) sp.par[q] = -1;
+      sp.gcol[0] = j; sp.gcol[1] = k; sp.gcol[2] = 0;
+      sp.gstride = nx; sp.nx_all = nx * nx; sp.ny = nys; sp.ymask = ymask; sp.no_primal = 1;
+      rc = loss_grad_core(c, xin, y, sw, B, Bg, 3, sp.seeds, d2ydx2, w_hess, &sp);
+      if (!rc) launch_axpy_cols(c->sob2_acc, c->grad, c->P, c->P, c->st);
+    }
+  c->jac_l1 = jac_l1; c->act_l1 = act_l1; c->act_l2 = act_l2;
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(c->grad, c->sob2_acc, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
+  c->reg_applied = false;
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
 }
 static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const SobPlan& sp, int nx, float* u, float* dudx);
 extern "C" int nif_sobolev_forward_dev(nif_ctx* c, const float* xin, int64_t B, const int32_t* x_idx, int32_t nx, float* u,

@@ -76,6 +76,7 @@ struct nif_ctx {
   unsigned* prune_hist = nullptr; PruneSel* prune_sel = nullptr;
   bool ll_mlp_packed = false;        // last-layer class: the f32 planes of the 32-point MLP kernels are current
   int loss_kind = 0;                 // NIF_LOSS_* (nif_set_loss)
+  float* sob2_acc = nullptr;         // [grad | loss] summed over the passes of a second-order Sobolev step (nif_sobolev2_loss_grad_dev)
   float* sob_acc = nullptr;          // [grad | loss] summed over the column groups of a Sobolev step with more than three x_index columns
   float act_l1 = 0.f, act_l2 = 0.f; float* act_part = nullptr; long act_part_cap = 0; float* act_loss = nullptr; long act_loss_cap = 0;
   float *stash_l = nullptr, *PHI = nullptr, *DPHI = nullptr, *DA = nullptr, *DZL = nullptr; long slot_l = 0;

@@ -235,6 +235,9 @@ struct SobPar {
   // r4, all "0 = as before": the launch carries one GROUP of the x_index columns (gt / JU rows have gstride columns, the derivative
   // term averages over nx_all columns), only the outputs of ymask (ny of them) enter the derivative term, no_primal drops mse(u)
   int gstride, nx_all, ny, no_primal; unsigned ymask;
+  // 1: the second-order pair pass (k_sob<.., HESS>): streams (j, k, second order), gt = d2ydx2 rows [so][gstride][gstride], gcol[0] /
+  // gcol[1] = positions of j / k in x_index, nx_all = nx * nx
+  int hess;
 };
 int launch_sob(const SNetArgs& a, bool train, int ns, const int* seeds, const float* gt, float wj, float* ring, float* ju,
                bool query_only, hipStream_t st, const SobPar* par = nullptr);

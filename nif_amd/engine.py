@@ -316,6 +316,40 @@ class Engine(object):
         check(self.lib.nif_sobolev_loss_grad_dev_y(self.ctx, d_x, d_y, d_g, d_sw, int(b_local), int(b_global), xi, len(x_index),
                                                    yi, 0 if y_index is None else len(y_index), float(w_jac)))
 
+    def sobolev2_loss_grad_dev(self, d_x, d_y, d_g, d_h, d_sw, b_local, b_global, x_index, w_jac, w_hess, y_index=None):
+        """the three-output model's step (u, du/dx, d2u/dx2; nif_sobolev2_loss_grad_dev): d_g rows [so][nx], d_h rows [so][nx][nx]"""
+        xi = (C.c_int32 * len(x_index))(*[int(i) for i in x_index])
+        yi = None if y_index is None else (C.c_int32 * len(y_index))(*[int(i) for i in y_index])
+        check(self.lib.nif_sobolev2_loss_grad_dev(self.ctx, d_x, d_y, d_g, d_h, d_sw, int(b_local), int(b_global), xi, len(x_index),
+                                                  yi, 0 if y_index is None else len(y_index), float(w_jac), float(w_hess)))
+
+    def sobolev2_loss_and_grad(self, inputs, y, dydx, d2ydx2, x_index, w_jac, w_hess, sample_weight=None, want_grad=True,
+                               y_index=None):
+        """(total loss incl. the weight regularisers, flat gradient) of the three-output model on host arrays"""
+        x = self._inputs(inputs)
+        B, so, nx = x.shape[0], self.spec.so_dim, len(x_index)
+        y, g, h = self._targets(y, B), _f32(dydx), _f32(d2ydx2)
+        if g.size != B * so * nx or h.size != B * so * nx * nx:
+            raise ValueError("dydx / d2ydx2: expected %d x %d x %d (x %d) values, got shapes %s, %s" % (B, so, nx, nx, g.shape, h.shape))
+        sample_weight = self._weights(sample_weight, B)
+        d_x, d_y, d_g, d_h = DeviceArray(self, x.size), DeviceArray(self, y.size), DeviceArray(self, g.size), DeviceArray(self, h.size)
+        d_sw = DeviceArray(self, B) if sample_weight is not None else None
+        try:
+            d_x.upload(x); d_y.upload(y); d_g.upload(g); d_h.upload(h)
+            if d_sw is not None:
+                d_sw.upload(_f32(sample_weight))
+            self.sobolev2_loss_grad_dev(d_x.at(0), d_y.at(0), d_g.at(0), d_h.at(0), d_sw.at(0) if d_sw is not None else None, B, B,
+                                        x_index, w_jac, w_hess, y_index)
+            if want_grad:
+                loss, grad = self.grad_read()
+            else:
+                loss, grad = self.grad_read_loss(), None
+        finally:
+            d_x.free(); d_y.free(); d_g.free(); d_h.free()
+            if d_sw is not None:
+                d_sw.free()
+        return loss, grad
+
     def sobolev_forward(self, inputs, x_index):
         x = self._inputs(inputs)
         B, nx, so = x.shape[0], len(x_index), self.spec.so_dim

@@ -678,12 +678,31 @@ class SobolevModel(Model):
     ParameterNet inputs, as gradient.py:207-231 allows; more than three columns run as passes over groups of three tangent streams),
     any positive loss_weights[0].
         m = SobolevModel(JacobianLayer(model, y_index, x_index)); m.compile("adam", "mse", loss_weights=[1, .1])
-        m.fit(x, [y, dydx], ...);  u, dudx = m.predict(x)"""
+        m.fit(x, [y, dydx], ...);  u, dudx = m.predict(x)
+    Over a HessianLayer it is the three-output model (u, du/dx, d2u/dx2) of gradient.py:130-180 compiled with loss_weights=[w0, w1, w2]:
+        m = SobolevModel(HessianLayer(model, y_index, x_index)); m.compile("adam", "mse", loss_weights=[1, .1, .01])
+        m.fit(x, [y, dydx, d2ydx2], ...);  u, dudx, d2udx2 = m.predict(x)
+    built for NIFMultiScale (SIREN ShapeNet, with or without resblocks) and NIFMultiScaleLastLayerParameterized, coordinate columns in
+    x_index, policy float32 (nif_sobolev2_loss_grad_dev: the first-order step plus one second-order pass per coordinate pair)."""
+
+    _HESS_BUILT = ("built: NIFMultiScale (SIREN ShapeNet, with or without resblocks) and NIFMultiScaleLastLayerParameterized, "
+                   "coordinate columns in x_index, policy float32")
 
     def __init__(self, jac_layer):
-        if not isinstance(jac_layer, JacobianLayer):
-            raise TypeError("SobolevModel wraps a JacobianLayer")
+        if not isinstance(jac_layer, (JacobianLayer, HessianLayer)):
+            raise TypeError("SobolevModel wraps a JacobianLayer or a HessianLayer")
+        self._order = 2 if isinstance(jac_layer, HessianLayer) else 1
         base = jac_layer.model
+        if self._order == 2:
+            owner = base._owner
+            if owner._spec.kind == "NIF":
+                raise NotImplementedError("SobolevModel(HessianLayer(...)) of class NIF is not built (%s)" % self._HESS_BUILT)
+            if owner.mixed_policy_name != "float32":
+                raise NotImplementedError("SobolevModel(HessianLayer(...)) under mixed_policy=%r is not built (%s)"
+                                          % (owner.mixed_policy_name, self._HESS_BUILT))
+            if any(int(i) < owner._spec.pi_dim for i in jac_layer.x_index):
+                raise NotImplementedError("SobolevModel(HessianLayer(...)) with parameter columns in x_index is not built (%s)"
+                                          % self._HESS_BUILT)
         Model.__init__(self, base._owner, "full")
         so, ncol = base._owner._spec.so_dim, base._owner._spec.pi_dim + base._owner._spec.si_dim
         # any subset / order of outputs and input columns (gradient.py:207-231); a column or output listed twice would make the
@@ -695,7 +714,7 @@ class SobolevModel(Model):
         if len(set(self.x_index)) != len(self.x_index) or not all(0 <= i < ncol for i in self.x_index):
             raise ValueError("x_index: distinct input columns in [0, %d)" % ncol)
         self._all_y = self.y_index == list(range(so))
-        self.loss_weights = [1.0, 1.0]
+        self.loss_weights = [1.0] * (1 + self._order)
 
     def compile(self, optimizer="adam", loss="mse", loss_weights=None, **kwargs):
         if isinstance(loss, (list, tuple)):
@@ -705,24 +724,50 @@ class SobolevModel(Model):
         Model.compile(self, optimizer=optimizer, loss=loss, **kwargs)
         if loss_weights is not None:
             lw = [float(v) for v in loss_weights]
-            if len(lw) != 2 or lw[0] <= 0.0:
+            if self._order == 2:
+                if len(lw) != 3 or lw[0] <= 0.0 or lw[1] < 0.0 or lw[2] < 0.0:
+                    raise ValueError("loss_weights = [w_u > 0, w_dudx >= 0, w_d2udx2 >= 0] (three outputs)")
+            elif len(lw) != 2 or lw[0] <= 0.0:
                 raise ValueError("loss_weights = [w_u > 0, w_dudx]")
             self.loss_weights = lw
 
     def _run(self, x):
+        if self._order == 2:       # HessianLayer(model, y_index, x_index)(x), the layer the model wraps
+            return list(self._engine.hessian(x, self.y_index, self.x_index))
         u, j = self._engine.sobolev_forward(x, self.x_index)
         return [u, j if self._all_y else np.ascontiguousarray(j[:, self.y_index, :])]
 
     def _loss_host(self, e, x, targets, sw):
         """Model.evaluate's chunk loss for the two-output model: w0 mse(u) + w1 mse(du/dx) + the regularisation losses -- the
         same total `fit` logs (r3 returned the data term alone, computed on the host)"""
+        if self._order == 2:
+            w0, w1, w2 = self.loss_weights
+            return e.sobolev2_loss_and_grad(x, targets[0], targets[1], targets[2], self.x_index, w1 / w0, w2 / w0,
+                                            self._scaled_weights(sw, x.shape[0]), want_grad=False,
+                                            y_index=None if self._all_y else self.y_index)[0]
         w0, w1 = self.loss_weights
         return e.sobolev_loss_and_grad(x, targets[0], targets[1], self.x_index, w1 / w0, self._scaled_weights(sw, x.shape[0]),
                                        want_grad=False, y_index=None if self._all_y else self.y_index)[0]
 
     def _targets(self, y, n_rows):
+        if self._order == 2:
+            if not (isinstance(y, (list, tuple)) and len(y) == 3):
+                raise ValueError("the Sobolev model over a HessianLayer has three outputs: fit(x, [y, dydx, d2ydx2])")
+            ty, tj = SobolevModel._targets_first(self, y[:2], n_rows)
+            so, nx, ny = self._owner._spec.so_dim, len(self.x_index), len(self.y_index)
+            th = np.ascontiguousarray(y[2], dtype=np.float32)
+            if th.shape != (n_rows, ny, nx, nx):
+                raise ValueError("d2ydx2 must have shape (N, len(y_index)=%d, len(x_index)=%d, %d), got %r" % (ny, nx, nx, th.shape))
+            if not self._all_y:   # engine rows [so][nx][nx]: the listed outputs' blocks in place, the others unused (zeros)
+                full = np.zeros((n_rows, so, nx, nx), dtype=np.float32)
+                full[:, self.y_index] = th
+                th = full
+            return [ty, tj, th.reshape(n_rows, so * nx * nx)]
         if not (isinstance(y, (list, tuple)) and len(y) == 2):
             raise ValueError("the Sobolev model has two outputs: fit(x, [y, dydx])")
+        return SobolevModel._targets_first(self, y, n_rows)
+
+    def _targets_first(self, y, n_rows):
         so, nx, ny = self._owner._spec.so_dim, len(self.x_index), len(self.y_index)
         ty = Model._targets(self, y[0], n_rows)[0]
         tj = np.ascontiguousarray(y[1], dtype=np.float32).reshape(n_rows, ny, nx)
@@ -733,7 +778,7 @@ class SobolevModel(Model):
         return [ty, tj.reshape(n_rows, so * nx)]
 
     def _n_tangents(self):
-        return len(self.x_index)
+        return 3 if self._order == 2 else len(self.x_index)     # (the second-order pair passes carry three tangent streams)
 
     def _scaled_weights(self, sw, n_rows):
         """Keras total loss = w0 mse(u) + w1 mse(du/dx) (+ regularisers, unscaled).  The kernels compute
@@ -747,6 +792,11 @@ class SobolevModel(Model):
         return np.ascontiguousarray(np.asarray(sw, dtype=np.float32) * np.float32(w0))
 
     def _loss_grad_dev(self, e, d_x, d_targets, d_sw, b, bg):
+        if self._order == 2:
+            w0, w1, w2 = self.loss_weights
+            e.sobolev2_loss_grad_dev(d_x, d_targets[0], d_targets[1], d_targets[2], d_sw, b, bg, self.x_index, w1 / w0, w2 / w0,
+                                     None if self._all_y else self.y_index)
+            return
         w0, w1 = self.loss_weights
         e.sobolev_loss_grad_dev(d_x, d_targets[0], d_targets[1], d_sw, b, bg, self.x_index, w1 / w0,
                                 None if self._all_y else self.y_index)

@@ -325,6 +325,9 @@ class TFPLBFGS(object):
         self._np = np
         if getattr(model, "_is_pruned", False):
             raise NotImplementedError("TFPLBFGS / LBFGSOptimizer on a pruned model (nif_amd.sparsity): strip_pruning(model) first")
+        if getattr(model, "_order", 1) == 2:
+            raise NotImplementedError("TFPLBFGS / LBFGSOptimizer on the three-output Sobolev model (HessianLayer) is not built: its "
+                                      "loss has a second-derivative term the L-BFGS closure does not fit; train it with fit()")
         name = loss_fun if isinstance(loss_fun, str) else getattr(loss_fun, "name", None) or getattr(loss_fun, "__name__", None)
         if not isinstance(loss_fun, str) and loss_fun is not None:      # loss OBJECTS: only their defaults are built (as Model.compile)
             if float(getattr(loss_fun, "delta", 1.0)) != 1.0:

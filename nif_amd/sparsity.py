@@ -237,7 +237,8 @@ def prune_low_magnitude(to_prune, pruning_schedule=None, block_size=(1, 1), bloc
     if isinstance(to_prune, PrunedModel):
         raise ValueError("prune_low_magnitude: the model is already pruned")
     if isinstance(to_prune, SobolevModel):
-        raise NotImplementedError("prune_low_magnitude: the two-output Sobolev model (JacobianLayer) is not built")
+        raise NotImplementedError("prune_low_magnitude: the Sobolev models (SobolevModel over a JacobianLayer, two outputs, or a "
+                                  "HessianLayer, three outputs) are not built")
     if not isinstance(to_prune, Model) or to_prune._role != "full":
         raise NotImplementedError("prune_low_magnitude: the model NIF(...).build() / .model() returns (not the sub-models)")
     if to_prune._jac_reg:
