@@ -146,7 +146,14 @@ int nif_copy_wait_host(nif_ctx* ctx, int32_t slot);
  * dst[i][:] = src[perm[i]][:] for n rows of ncol floats; perm is a device int32 array */
 int nif_gather_rows_dev(nif_ctx* ctx, const float* src_dev, const int32_t* perm_dev, int64_t n, int32_t ncol, float* dst_dev);
 void* nif_stream(nif_ctx* ctx);          /* hipStream_t of the context */
-void* nif_grad_dev(nif_ctx* ctx);        /* device float[P+1]: flat gradient || loss  (the RCCL all-reduce buffer) */
+/* device float[P+1]: flat gradient || loss (the RCCL all-reduce buffer).  The row reduction of a plain training step may be deferred
+ * ("fuse_tail", the default: nif_adam_step_dev / nif_opt_step_dev then run it fused with the update), so the buffer is complete only
+ * after a call of this library on the context that follows nif_loss_grad_dev: THIS call runs the deferred reduction before it returns
+ * the pointer, and so does every other entry point.  A pointer cached from an earlier call and read behind nif_loss_grad_dev without
+ * such a call in between sees the previous step's gradient: call nif_grad_dev() again, or set the option "fuse_tail" to 0.
+ * The weight-regulariser term is not in the buffer before the optimizer step, nif_grad_read or nif_grad_transform_dev added it.  After
+ * an optimizer step with a gradient transform set (nif_set_grad_transform) the buffer holds the TRANSFORMED gradient. */
+void* nif_grad_dev(nif_ctx* ctx);
 void* nif_params_dev(nif_ctx* ctx);      /* device float[P] */
 
 /* ---- inference ------------------------------------------------------------------------ */
@@ -194,6 +201,7 @@ int nif_hessian_dev(nif_ctx* ctx, const float* xin_dev, int64_t B, const int32_t
  * d loss / d theta (GradientTape).  Result stays on the device in nif_grad_dev():
  * grad[0..P) and grad[P] = loss, both already scaled by 1/B_global so that a SUM all-reduce
  * over shards gives the global-batch mean (tf.distribute.MirroredStrategy, README.md:39-49). */
+/* With "fuse_tail" on (the default) the rows of the gradient may still be unreduced when this returns: see nif_grad_dev(). */
 int nif_loss_grad_dev(nif_ctx* ctx, const float* xin_dev, const float* y_dev, const float* sw_dev_or_null,
                       int64_t B_local, int64_t B_global);
 /* Sobolev training: the Keras model  Model(x, JacobianLayer(nif, y_index=all, x_index)(x))  compiled with
@@ -285,6 +293,40 @@ int nif_set_opt_slot(nif_ctx* ctx, int32_t slot, const float* host, int64_t n);
  * out[0] learning rate, out[1] 1 - b1^t, out[2] 1 - b2^t, out[3] r_t, out[4] 1 when the update divides by (v_hat + eps), else 0
  * (AdaBelief's momentum branch); Lion fills out[0] only */
 int nif_opt_scalars(const nif_opt* opt, int64_t t, double* out5);
+/* Gradient transform in front of the update of every optimizer step of the context (k_gradtf.hip): the reference's
+ * centralized_gradients_for_optimizer (nif/optimizers/gtcf.py:7-67) and Keras' clipnorm / clipvalue / global_clipnorm.  A tensor is one
+ * entry of nif_param_layout; g is the step's flat gradient behind the row reduction, the all-reduce and the weight-regulariser term.
+ * Stages in this order, each off unless asked for:
+ *   1  NIF_GT_CENTRALIZE: every tensor with cols > 0: g[i][j] -= mean_i g[i][j] (the mean over the rows of each column; a matrix
+ *      with ONE row gets a gradient of exactly zero, as in the reference)
+ *   2  Keras route, clipvalue = c:        g = min(max(g, -c), c)
+ *   3  Keras route, clipnorm = c:         per tensor n_t = sqrt(sum g_t^2), g_t = (g_t c) / max(n_t, c)        (tf.clip_by_norm)
+ *   4a Keras route, global_clipnorm = c:  n = sqrt(sum g^2), g = g (c min(1/n, 1/c)); NaN for a non-finite n   (tf.clip_by_global_norm)
+ *   4b NIF_GT_GTCF, clipnorm = c:         g = (g c) / n where n >= c, else unchanged                            (gtcf.py:42-46)
+ *   5  NIF_GT_GTCF, clipvalue = c:        the clamp of stage 2, behind the norm stage                           (gtcf.py:47-48)
+ * Without NIF_GT_GTCF at most one of the three constants may be non-zero (Keras raises for more) ; with it global_clipnorm must be 0.
+ * Norms are those of the gradient as the stage finds it.  The loss slot g[P] is never touched.  Sums run in a fixed order without
+ * floating-point atomics: ranks that hold the same all-reduced gradient stay bit-identical.  One launch, two with a norm stage; an
+ * optimizer step with a transform set runs reduction, regulariser, transform and update as separate launches (no fused tail).
+ * nif_grad_read and nif_loss_and_grad return the UNtransformed gradient. */
+#define NIF_GT_CENTRALIZE 1
+#define NIF_GT_GTCF 2
+typedef struct {               /* 32 bytes; reserved fields and unknown flag bits must be zero, constants >= 0 (0 = off) */
+  int32_t flags;               /* NIF_GT_* bits */
+  float clipnorm, clipvalue, global_clipnorm;
+  int32_t reserved[4];
+} nif_grad_transform;
+/* context state, like the regulariser setters; NULL or an all-zero struct turns the transform off.  NIF_ERR_STATE inside a capture.
+ * A captured graph reads the constants at replay time; it is replayed only with a transform that needs no more launches than it
+ * recorded (NIF_ERR_STATE otherwise). */
+int nif_set_grad_transform(nif_ctx* ctx, const nif_grad_transform* t_or_null);
+/* runs the configured transform once on nif_grad_dev(), behind the deferred row reduction and the regulariser term: for callers with
+ * their own update (a following optimizer step of this library would transform again) */
+int nif_grad_transform_dev(nif_ctx* ctx);
+/* the norms of the last transform (what a Keras user logs as the gradient norm): per tensor (n = the layout's tensor count) and / or
+ * global, of the gradient in front of the norm stage -- behind centralisation and Keras' clipvalue.  NIF_ERR_STATE before any transform
+ * ran and inside a capture.  Synchronises. */
+int nif_grad_norms(nif_ctx* ctx, float* per_tensor_or_null, int32_t n, float* global_or_null);
 /* Low-magnitude pruning (tfmot.sparsity.keras 0.7.3 as nif_amd/sparsity.py restates it).  A segment is one pruned tensor: `size` floats
  * of the flat parameter vector from float `offset`; segments are given in increasing, non-overlapping order.
  *   nif_prune_config   registers n segments (n = 0: pruning off, its buffers freed); masks start at all ones, thresholds at 0

@@ -66,6 +66,14 @@ class nif_opt(C.Structure):
     ]
 
 
+GT_CENTRALIZE, GT_GTCF = 1, 2
+
+
+class nif_grad_transform(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("clipnorm", C.c_float), ("clipvalue", C.c_float), ("global_clipnorm", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 _CTX = C.c_void_p
@@ -129,6 +137,9 @@ SIGNATURES = {
     "nif_get_opt_slot": (C.c_int, [_CTX, C.c_int32, _VP, C.c_int64]),
     "nif_set_opt_slot": (C.c_int, [_CTX, C.c_int32, _VP, C.c_int64]),
     "nif_opt_scalars": (C.c_int, [C.POINTER(nif_opt), C.c_int64, C.POINTER(C.c_double)]),
+    "nif_set_grad_transform": (C.c_int, [_CTX, C.POINTER(nif_grad_transform)]),
+    "nif_grad_transform_dev": (C.c_int, [_CTX]),
+    "nif_grad_norms": (C.c_int, [_CTX, _VP, C.c_int32, _FP]),
     "nif_prune_config": (C.c_int, [_CTX, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "nif_prune_update": (C.c_int, [_CTX, C.POINTER(C.c_int64)]),
     "nif_prune_apply": (C.c_int, [_CTX]),

@@ -207,7 +207,7 @@ extern "C" int nif_destroy(nif_ctx* c) {
   for (hipEvent_t e : c->ev_chunk) hipEventDestroy(e);
   for (hipGraphExec_t ex : c->graphs) if (ex) (void)hipGraphExecDestroy(ex);
   if (c->opt_host) (void)hipHostFree(c->opt_host);
-  void* ptrs[] = {c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->sob2_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
+  void* ptrs[] = {c->gt_blk, c->gt_part, c->gt_norms, c->gt_dev, c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->sob2_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
                   c->DU, c->ZL, c->partial, c->loss_partial, c->dring, c->metric, c->tl, c->lWF, c->lWB, c->sWF4, c->sWB4, c->sWF4x, c->sWB4x, c->sWscale, c->sWF4h, c->sWB4h, c->ll_slots, c->ll_wpf, c->ll_wpb, c->stash_l, c->PHI, c->DPHI, c->DA, c->DZL, c->d_a, c->d_b, c->d_c, c->d_d};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->st) hipStreamDestroy(c->st);
@@ -2068,7 +2068,7 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
   // weights the previous replay left behind)
   c->packed = false; c->packed32 = false; c->packed_p32 = false;
   HIPCHK(hipStreamBeginCapture(c->st, hipStreamCaptureModeRelaxed));
-  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step; c->cap_kind = -1; c->cap_ams = false;
+  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step; c->cap_kind = -1; c->cap_ams = false; c->cap_gt = 0;
   return NIF_OK;
 }
 extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
@@ -2085,13 +2085,114 @@ extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) { (void)hipGetLastError(); return fail(NIF_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
   c->graphs.push_back(ex); c->graph_steps.push_back(c->cap_steps);
-  c->graph_kind.push_back(c->cap_kind); c->graph_ams.push_back(c->cap_ams ? 1 : 0);
+  c->graph_kind.push_back(c->cap_kind); c->graph_ams.push_back(c->cap_ams ? 1 : 0); c->graph_gt.push_back((char)c->cap_gt);
   *graph_id = (int32_t)c->graphs.size() - 1;
   return NIF_OK;
 }
 extern "C" int nif_graph_destroy(nif_ctx* c, int32_t graph_id) {
   if (!c || graph_id < 0 || graph_id >= (int32_t)c->graphs.size()) return fail(NIF_ERR_INVALID, "bad argument");
   if (c->graphs[graph_id]) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipGraphExecDestroy(c->graphs[graph_id]); c->graphs[graph_id] = nullptr; }
+  return NIF_OK;
+}
+
+// ---- gradient transform (include/nif_hip.h nif_set_grad_transform; k_gradtf.hip; reference nif/optimizers/gtcf.py:7-67) -------------
+static int gt_check(const nif_grad_transform* t) {
+  if (t->flags & ~(NIF_GT_CENTRALIZE | NIF_GT_GTCF)) return fail(NIF_ERR_INVALID, "nif_grad_transform: unknown flag bits");
+  if (t->reserved[0] || t->reserved[1] || t->reserved[2] || t->reserved[3]) return fail(NIF_ERR_INVALID, "nif_grad_transform: reserved fields must be zero");
+  if (!(t->clipnorm >= 0.f) || !(t->clipvalue >= 0.f) || !(t->global_clipnorm >= 0.f))
+    return fail(NIF_ERR_INVALID, "nif_grad_transform: clipnorm, clipvalue and global_clipnorm must be >= 0 (0 = off)");
+  const int n = (t->clipnorm > 0.f) + (t->clipvalue > 0.f) + (t->global_clipnorm > 0.f);
+  if (!(t->flags & NIF_GT_GTCF) && n > 1)
+    return fail(NIF_ERR_INVALID, "nif_grad_transform: only one of clipnorm, clipvalue and global_clipnorm (Keras route; NIF_GT_GTCF takes clipnorm and clipvalue)");
+  if ((t->flags & NIF_GT_GTCF) && t->global_clipnorm > 0.f)
+    return fail(NIF_ERR_INVALID, "nif_grad_transform: NIF_GT_GTCF has no global_clipnorm (its clipnorm is the global norm)");
+  return NIF_OK;
+}
+// the work blocks of the layout: 64 columns x all rows of a matrix, chunks of GT_VEC_CHUNK floats of a vector
+static std::vector<GtBlk> gt_blocks(const nif_ctx* c) {
+  std::vector<GtBlk> v;
+  for (size_t t = 0; t < c->layout.size(); ++t) {
+    const nif_tensor_desc& d = c->layout[t];
+    const int pb0 = (int)v.size();
+    GtBlk b; memset(&b, 0, sizeof(b));
+    b.tensor = (int)t; b.pb0 = pb0;
+    if (d.cols > 0) {
+      for (int c0 = 0; c0 < d.cols; c0 += 64) {
+        b.matrix = 1; b.base = (long)d.offset + c0; b.stride = d.cols; b.rows = d.rows; b.nc = d.cols - c0 < 64 ? d.cols - c0 : 64;
+        b.lim = (long)(d.rows - 1) * d.cols + b.nc;
+        v.push_back(b);
+      }
+    } else {
+      for (long e0 = 0; e0 < d.rows; e0 += GT_VEC_CHUNK) {
+        const long len = d.rows - e0 < GT_VEC_CHUNK ? d.rows - e0 : GT_VEC_CHUNK;
+        b.matrix = 0; b.base = (long)d.offset + e0; b.stride = 64; b.rows = (int)((len + 63) / 64); b.nc = 64; b.lim = len;
+        v.push_back(b);
+      }
+    }
+    for (size_t i = (size_t)pb0; i < v.size(); ++i) v[i].pbn = (int)v.size() - pb0;
+  }
+  return v;
+}
+static int gt_launches(const nif_ctx* c) { return c->gt_on ? (c->gt_norm ? 2 : 1) : 0; }
+extern "C" int nif_set_grad_transform(nif_ctx* c, const nif_grad_transform* t) {
+  nif_grad_transform z; memset(&z, 0, sizeof(z));
+  if (t) { const int rc = gt_check(t); if (rc) return rc; z = *t; }      // (the struct is judged first: checkable without a device)
+  if (!c) return fail(NIF_ERR_INVALID, "nif_set_grad_transform: null context");
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_set_grad_transform: not inside a graph capture");
+  const bool gtcf = (z.flags & NIF_GT_GTCF) != 0;
+  const bool on = (z.flags & NIF_GT_CENTRALIZE) || z.clipnorm > 0.f || z.clipvalue > 0.f || z.global_clipnorm > 0.f;
+  if (!on && !c->gt_dev) { c->gt = z; c->gt_on = false; c->gt_norm = false; return NIF_OK; }
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  HIPCHK(hipStreamSynchronize(c->st));      // (queued steps still read the device copy)
+  if (!c->gt_dev) {
+    const std::vector<GtBlk> blks = gt_blocks(c);
+    for (const GtBlk& b : blks)
+      if (b.base < 0 || b.base + b.lim > c->P) return fail(NIF_ERR_STATE, "internal: gradient-transform block outside the gradient");
+    HIPCHK(hipMalloc(&c->gt_blk, sizeof(GtBlk) * blks.size()));
+    HIPCHK(hipMalloc(&c->gt_part, sizeof(float) * blks.size()));
+    HIPCHK(hipMalloc(&c->gt_norms, sizeof(float) * (c->layout.size() + 1)));
+    HIPCHK(hipMalloc(&c->gt_dev, sizeof(GtDev)));
+    HIPCHK(hipMemcpy(c->gt_blk, blks.data(), sizeof(GtBlk) * blks.size(), hipMemcpyHostToDevice));
+    c->gt_nblk = (int)blks.size();
+  }
+  GtDev d; d.flags = z.flags; d.clipnorm = z.clipnorm; d.clipvalue = z.clipvalue; d.global_clipnorm = z.global_clipnorm;
+  HIPCHK(hipMemcpy(c->gt_dev, &d, sizeof(d), hipMemcpyHostToDevice));
+  c->gt = z; c->gt_on = on;
+  c->gt_norm = on && (gtcf ? z.clipnorm > 0.f : (z.clipnorm > 0.f || z.global_clipnorm > 0.f));
+  return NIF_OK;
+}
+// the configured transform on c->grad (complete: reduced, all-reduced, regulariser added); one launch, two with a norm stage
+static void gt_run(nif_ctx* c) {
+  launch_gt_reduce(c->grad, c->gt_blk, c->gt_nblk, c->gt_part, c->gt_dev, c->st);
+  if (c->gt_norm) launch_gt_apply(c->grad, c->gt_blk, c->gt_nblk, (int)c->layout.size(), c->gt_part, c->gt_norms, c->gt_dev, true, c->st);
+  if (c->capturing) c->cap_gt = gt_launches(c);      // (nothing has run yet: graph_replay marks the norms)
+  else c->gt_ran = c->gt_norm ? 2 : 1;
+}
+extern "C" int nif_grad_transform_dev(nif_ctx* c) {
+  if (!c) return fail(NIF_ERR_INVALID, "null");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  apply_reg(c);
+  if (c->gt_on) gt_run(c);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_grad_norms(nif_ctx* c, float* per_tensor, int32_t n, float* global) {
+  if (!c) return fail(NIF_ERR_INVALID, "null");
+  if (per_tensor && n != (int32_t)c->layout.size()) return fail(NIF_ERR_INVALID, "nif_grad_norms: n is the tensor count of nif_param_layout");
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_grad_norms: not inside a graph capture");
+  if (!c->gt_ran) return fail(NIF_ERR_STATE, "nif_grad_norms: no gradient transform has run on this context");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  if (c->gt_ran == 1) {      // the last transform had no norm stage: its partial sums are there, the norms are formed now
+    launch_gt_apply(c->grad, c->gt_blk, c->gt_nblk, (int)c->layout.size(), c->gt_part, c->gt_norms, c->gt_dev, false, c->st);
+    HIPCHK(hipGetLastError());
+    c->gt_ran = 2;
+  }
+  if (per_tensor) HIPCHK(hipMemcpyAsync(per_tensor, c->gt_norms, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->st));
+  if (global) HIPCHK(hipMemcpyAsync(global, c->gt_norms + c->layout.size(), sizeof(float), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
 
@@ -2136,7 +2237,8 @@ static void theta_stepped(nif_ctx* c) {
   c->packed = false; c->packed32 = false; c->packed_p32 = false;
   c->reg_applied = false;
 }
-// One optimizer step of any kind, after the all-reduce, in one of three forms: fused with the deferred row reduction (tail_can_defer);
+// One optimizer step of any kind, after the all-reduce, in one of three forms: fused with the deferred row reduction (tail_can_defer,
+// no gradient transform set);
 // inside a capture with the scalars from c->opt_dev at replay time (graph_replay refreshes it); else after the flushed reduction and the
 // regulariser term.  `who` names the entry point in the error messages.
 static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
@@ -2146,12 +2248,15 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
     return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
   HIPCHK(hipSetDevice(c->dev));
   if (ams) { const int rc = ensure_vhat(c); if (rc) return rc; }
-  const bool fused = c->tail_pending && !c->capturing && tail_can_defer(c);    // the step's row reduction and the update in ONE launch
+  // the step's row reduction and the update in ONE launch -- not with a gradient transform set: a norm needs every column of the
+  // gradient before any parameter moves
+  const bool fused = c->tail_pending && !c->capturing && !c->gt_on && tail_can_defer(c);
   if (fused) {
     c->tail_pending = false;
   } else {
     TAIL_FLUSH(c)
     apply_reg(c);
+    if (c->gt_on) gt_run(c);
   }
   c->step += 1;
   const OptDev d = opt_dev_of(opt, c->step - 1);
@@ -2188,6 +2293,8 @@ extern "C" int nif_opt_step_dev(nif_ctx* c, const nif_opt* opt) {
 // replays a captured graph with opt's hyper-parameters (its kind checked by the caller) and the context's iteration count
 static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const char* who) {
   if (c->capturing) return fail(NIF_ERR_STATE, std::string(who) + " while capturing");
+  if (gt_launches(c) > c->graph_gt[graph_id])
+    return fail(NIF_ERR_STATE, std::string(who) + ": the context's gradient transform needs launches this graph did not record (set it before the capture)");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
@@ -2195,6 +2302,7 @@ static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const 
   HIPCHK(hipMemcpyAsync(c->opt_dev, c->opt_host, sizeof(OptDev), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipGraphLaunch(c->graphs[graph_id], c->st));
   c->step += c->graph_steps[graph_id];
+  if (c->graph_gt[graph_id]) c->gt_ran = c->graph_gt[graph_id];
   theta_stepped(c);
   return NIF_OK;
 }

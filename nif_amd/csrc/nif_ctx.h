@@ -74,6 +74,13 @@ struct nif_ctx {
   std::vector<PruneSeg> prune_segs; long prune_nblk = 0, prune_lo = 0, prune_hi = 0;
   PruneSeg* prune_segs_dev = nullptr; unsigned char* prune_mask = nullptr; float* prune_thr = nullptr;
   unsigned* prune_hist = nullptr; PruneSel* prune_sel = nullptr;
+  // gradient transform (nif_set_grad_transform): the configured struct, whether any stage is on / a norm stage is on, the work-block
+  // table, one partial sum of squares per block, the norms [tensors | global], and the struct's device copy; all built at the first
+  // non-zero set.  gt_ran: 0 no transform has run, 1 the last one ran without a norm stage (norms not formed yet), 2 with.
+  // cap_gt / graph_gt: the launches a capture recorded (0 none, 1 k_gt_reduce, 2 both)
+  nif_grad_transform gt = {}; bool gt_on = false, gt_norm = false; int gt_ran = 0;
+  GtBlk* gt_blk = nullptr; int gt_nblk = 0; float* gt_part = nullptr; float* gt_norms = nullptr; GtDev* gt_dev = nullptr;
+  int cap_gt = 0; std::vector<char> graph_gt;
   bool ll_mlp_packed = false;        // last-layer class: the f32 planes of the 32-point MLP kernels are current
   int loss_kind = 0;                 // NIF_LOSS_* (nif_set_loss)
   float* sob2_acc = nullptr;         // [grad | loss] summed over the passes of a second-order Sobolev step (nif_sobolev2_loss_grad_dev)

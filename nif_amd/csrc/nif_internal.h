@@ -315,6 +315,17 @@ void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, i
                        long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st);
 void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
                     hipStream_t st);
+// the gradient transform in front of the update (k_gradtf.hip, nif_set_grad_transform).  GtDev: a nif_grad_transform in device memory,
+// read by the kernels of eager and captured steps alike.  GtBlk: one work block -- 64 columns of a matrix over all its rows, or a chunk
+// of a vector laid out as 64 columns: element (i, c) is g[base + i stride + c] for c < nc, i < rows, i stride + c < lim; the partial
+// sums of its tensor are part[pb0, pb0 + pbn)
+enum { GT_CENTRALIZE = 1, GT_GTCF = 2 };
+#define GT_VEC_CHUNK 4096
+struct GtDev { int flags; float clipnorm, clipvalue, global_clipnorm; };
+struct GtBlk { long base, lim; int stride, rows, nc, tensor, matrix, pb0, pbn, pad; };
+void launch_gt_reduce(float* g, const GtBlk* blks, int nblk, float* part, const GtDev* gd, hipStream_t st);
+void launch_gt_apply(float* g, const GtBlk* blks, int nblk, int ntensor, const float* part, float* norms, const GtDev* gd, bool write,
+                     hipStream_t st);
 // magnitude pruning (k_prune.hip, nif_prune_*): one segment = one pruned tensor, `size` floats of theta from `off`; its histogram /
 // mask-build blocks are [blk0, blk0 + ceil(size / PRUNE_CHUNK)) of a flattened grid.  k: keep the k largest |w| (1 <= k <= size)
 #define PRUNE_CHUNK 4096         // entries per histogram / mask block (256 threads x 16)

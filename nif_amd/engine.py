@@ -410,6 +410,36 @@ class Engine(object):
         values = _f32(values)
         check(self.lib.nif_set_opt_slot(self.ctx, int(slot), ptr(values), values.size))
 
+    # gradient transform in front of every optimizer step (include/nif_hip.h nif_set_grad_transform; k_gradtf.hip)
+    def set_grad_transform(self, spec=None, **kwargs):
+        """spec: None (off) or a dict / keywords of centralize, gtcf (bool), clipnorm, clipvalue, global_clipnorm (None or 0 = off).
+        Context state until set again: Model.fit sets it from its optimizer and clears it when it returns."""
+        spec = dict(spec or {}, **kwargs)
+        unknown = set(spec) - {"centralize", "gtcf", "clipnorm", "clipvalue", "global_clipnorm"}
+        if unknown:
+            raise TypeError("set_grad_transform(%s): unknown keyword" % ", ".join(sorted(unknown)))
+        if not spec:
+            check(self.lib.nif_set_grad_transform(self.ctx, None))
+            return
+        t = _lib.nif_grad_transform()
+        t.flags = (_lib.GT_CENTRALIZE if spec.get("centralize") else 0) | (_lib.GT_GTCF if spec.get("gtcf") else 0)
+        t.clipnorm = float(spec.get("clipnorm") or 0.0)
+        t.clipvalue = float(spec.get("clipvalue") or 0.0)
+        t.global_clipnorm = float(spec.get("global_clipnorm") or 0.0)
+        check(self.lib.nif_set_grad_transform(self.ctx, C.byref(t)))
+
+    def grad_transform_dev(self):
+        """the configured transform once on the [grad | loss] buffer (for callers with their own update)"""
+        check(self.lib.nif_grad_transform_dev(self.ctx))
+
+    def grad_norms(self):
+        """(per-tensor norms in layout order, global norm) of the last transform: the gradient in front of its norm stage"""
+        n = len(self.layout())
+        per = np.empty((n,), dtype=np.float32)
+        g = C.c_float()
+        check(self.lib.nif_grad_norms(self.ctx, ptr(per), n, C.byref(g)))
+        return per, float(g.value)
+
     # low-magnitude pruning (include/nif_hip.h nif_prune_*; nif_amd.sparsity drives these)
     def prune_config(self, offsets, sizes):
         """register the pruned tensors as segments of theta (float offsets, sizes); empty lists: pruning off"""

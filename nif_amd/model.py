@@ -14,7 +14,7 @@ from . import _lib
 from . import distributed as dist
 from .data import ShardBatches
 from .engine import Engine
-from .optimizers import Adam, get as get_optimizer
+from .optimizers import Adam, get as get_optimizer, grad_transform_of
 from .spec import Spec
 
 _global_rng = [np.random.default_rng()]
@@ -279,6 +279,8 @@ class Model(object):
         if self._metrics and self._n_tangents() != 0:
             raise NotImplementedError("compile(metrics=...) on the two-output model")
         new = get_optimizer(optimizer)
+        grad_transform_of(new)           # (a marker of centralized_gradients_for_optimizer on new.get_gradients, Adam's clip keywords:
+                                         # checked here, read again at the start of every fit())
         if new is not self.optimizer:
             self._fresh_slots = True     # Keras: a newly compiled optimizer starts with zero slots and iteration 0
         self.optimizer = new
@@ -389,6 +391,21 @@ class Model(object):
         if kinds and (isinstance(x, ShardBatches) or dist.get() is not None):
             raise NotImplementedError("compile(metrics=...): in-memory arrays on one GPU")
         self._push_losses(e, 1)                   # (raises here, not at first engine access, when the shape has no kernel for it)
+        # the optimizer's gradient transform (Adam's clip keywords, centralized_gradients_for_optimizer), read now and engine state for
+        # the length of this call: cleared in the `finally` below, like the loss terms (a later TFPLBFGS or another model on the
+        # shared engine steps without it)
+        grad_tf = grad_transform_of(self.optimizer)
+        if grad_tf is not None:
+            e.set_grad_transform(grad_tf)
+        try:
+            return self._fit(e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch,
+                             validation_data, steps_per_epoch)
+        finally:
+            if grad_tf is not None:
+                e.set_grad_transform(None)
+
+    def _fit(self, e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch, validation_data,
+             steps_per_epoch):
         self.stop_training = False
         is_adam = isinstance(self.optimizer, Adam)
         if getattr(self, "_fresh_slots", False):

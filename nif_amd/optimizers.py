@@ -8,12 +8,36 @@ import numpy as np
 from . import _lib
 
 
+_CLIP_KEYS = ("clipnorm", "clipvalue", "global_clipnorm")
+
+
+def _clip_constant(name, v):
+    """None (off) or a non-negative number, as Keras' optimizer base checks its clip keywords"""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (numbers.Real, np.floating, np.integer)):
+        raise TypeError("%s=%r: a number or None" % (name, v))
+    if float(v) < 0.0:
+        raise ValueError("%s cannot be less than 0. Received: %s=%r." % (name, name, v))
+    return float(v)
+
+
 class Adam(object):
-    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
+    """Keras-2.11 Adam.  clipnorm / clipvalue / global_clipnorm are Keras' gradient clipping (per tensor by norm, by value, by the
+    global norm), applied on the device in front of the update (k_gradtf.hip); at most one of them, as in Keras."""
+
+    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, **kwargs):
         if "lr" in kwargs:
             learning_rate = kwargs.pop("lr")
         self.learning_rate = float(learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+        self.clipnorm = _clip_constant("clipnorm", clipnorm)
+        self.clipvalue = _clip_constant("clipvalue", clipvalue)
+        self.global_clipnorm = _clip_constant("global_clipnorm", global_clipnorm)
+        if sum(v is not None for v in (self.clipnorm, self.clipvalue, self.global_clipnorm)) > 1:
+            raise ValueError("At most one of `clipnorm`, `clipvalue` and `global_clipnorm` can be set. Received: clipnorm=%r, "
+                             "clipvalue=%r, global_clipnorm=%r." % (clipnorm, clipvalue, global_clipnorm))
 
     # Keras exposes optimizer.lr / optimizer.learning_rate; LearningRateScheduler sets it
     @property
@@ -44,8 +68,10 @@ def _legacy_kwargs(cls, kwargs, learning_rate):
     if decay < 0.0:
         raise ValueError("decay cannot be less than 0. Received: decay=%r." % (decay,))
     if kwargs:
-        raise NotImplementedError("%s(%s): not built (clipping and the other keyword arguments of Keras' optimizer base are "
-                                  "out of scope)" % (cls, ", ".join(sorted(kwargs))))
+        clip = " -- clipping reaches %s through centralized_gradients_for_optimizer: set opt.clipnorm / opt.clipvalue as " \
+               "attributes and opt.get_gradients = centralized_gradients_for_optimizer(opt)" % cls if set(kwargs) & set(_CLIP_KEYS) else ""
+        raise NotImplementedError("%s(%s): not built (the clip keywords and the other keyword arguments of Keras' optimizer base "
+                                  "are not constructor arguments here)%s" % (cls, ", ".join(sorted(kwargs)), clip))
     return _number(cls, "learning_rate", learning_rate), decay
 
 
@@ -129,6 +155,60 @@ class L4Adam(object):
     def __init__(self, *args, **kwargs):
         raise NotImplementedError("L4Adam: the reference's implementation does not run (external_optimizers.py:148 new_var=None); "
                                   "use Adam, Lion or AdaBeliefOptimizer")
+
+
+class _CentralizedGradients(object):
+    """what centralized_gradients_for_optimizer returns: a marker Model.compile recognises on optimizer.get_gradients"""
+
+    def __init__(self, optimizer):
+        self.optimizer = optimizer
+
+    def __call__(self, loss=None, params=None):
+        raise NotImplementedError("centralized_gradients_for_optimizer(opt)(loss, params): there is no symbolic loss to differentiate "
+                                  "here -- assign the result to opt.get_gradients and compile the model with opt; the gradient is "
+                                  "centralised and clipped on the device in front of every update")
+
+
+def centralized_gradients_for_optimizer(optimizer):
+    """nif.optimizers.centralized_gradients_for_optimizer (reference nif/optimizers/gtcf.py:7-67; gradient centralisation, Yong et al.
+    2020).  Documented use, as in the reference:
+
+        opt = nif_amd.optimizers.Lion(1e-4)            # or Adam, AdaBeliefOptimizer
+        opt.clipnorm = 1.0                              # optional attributes, read at the start of every fit()
+        opt.get_gradients = centralized_gradients_for_optimizer(opt)
+        model.compile(optimizer=opt, loss="mse")
+
+    Every step's gradient then goes through what the reference function's body computes: each rank-2 gradient [in, out] loses its
+    mean over the `in` axis per output column (the body's `keep_dims` is TF1's spelling of `keepdims`); if `opt.clipnorm` exists
+    and is > 0 the whole gradient is scaled to that global norm where its norm is larger; if `opt.clipvalue` exists and is > 0 it
+    is clamped to [-clipvalue, clipvalue] behind that.  A kernel with ONE input row (latent_dim = 1's hypernetwork matrix, a first
+    layer with one input) is centralised to exactly zero and stops training, in the reference's formula as here.
+    Under the reference's pinned TensorFlow 2.11 the hook is inert: Keras' fit() never calls optimizer.get_gradients, so the
+    reference trains unchanged whether or not the function was used; what is built here is what its body computes.  The returned
+    object cannot be called (there is no symbolic loss): it is a marker."""
+    if not isinstance(optimizer, (Adam, Lion, AdaBeliefOptimizer)):
+        raise TypeError("centralized_gradients_for_optimizer(optimizer): an Adam, Lion or AdaBeliefOptimizer of nif_amd.optimizers")
+    return _CentralizedGradients(optimizer)
+
+
+def grad_transform_of(opt):
+    """the gradient transform an optimizer asks for, as Engine.set_grad_transform's dict, or None: the gtcf route when
+    opt.get_gradients carries centralized_gradients_for_optimizer's marker (clipnorm / clipvalue read as gtcf.py:42,47 does:
+    hasattr(...) and > 0), else Keras' route from Adam's clip keywords"""
+    def positive(name):
+        v = getattr(opt, name, None)
+        return float(v) if v is not None and float(v) > 0.0 else 0.0
+    if isinstance(getattr(opt, "get_gradients", None), _CentralizedGradients):
+        if getattr(opt, "global_clipnorm", None):
+            raise ValueError("centralized_gradients_for_optimizer reads clipnorm (its global norm) and clipvalue; global_clipnorm=%r "
+                             "is set as well" % (opt.global_clipnorm,))
+        return {"centralize": True, "gtcf": True, "clipnorm": positive("clipnorm"), "clipvalue": positive("clipvalue")}
+    if not isinstance(opt, Adam):
+        return None       # (Lion / AdaBeliefOptimizer take no clip keywords: attributes count on the gtcf route only)
+    spec = {k: positive(k) for k in _CLIP_KEYS}
+    if sum(1 for v in spec.values() if v) > 1:
+        raise ValueError("At most one of `clipnorm`, `clipvalue` and `global_clipnorm` can be set.")
+    return spec if any(spec.values()) else None
 
 
 def get(opt):
