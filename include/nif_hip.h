@@ -381,6 +381,23 @@ int nif_last_loss(nif_ctx* ctx, float* loss_out);
 /* read-out half of nif_loss_and_grad for a resident dataset (lbfgs.py:66-74 closure): adds the weight-regulariser term
  * once, copies loss and/or the flat gradient to the host, synchronises.  Either pointer may be NULL. */
 int nif_grad_read(nif_ctx* ctx, float* loss_out_or_null, float* grad_host_or_null);
+/* The L-BFGS closure in double precision (lbfgs.py:56-88 / lbfgs_V2.py:57-79; the reference's newer fine-tuner runs Keras in float64,
+ * lbfgs_V2.py:79).  A precision of the fine-tuner, NOT Keras' float64 policy: the model stays a float32 model, and a float64 master
+ * vector of its P parameters (same layout) lives next to the float32 one.  Forward pass, loss and the gradient with respect to every
+ * parameter run in double on the device (k_f64.hip: hidden products and the weight-gradient sums on v_mfma_f64_16x16x4_f64), the batch
+ * walked in chunks of 4096 points, every sum in a fixed order (two evaluations at one point are bit-identical).  Inputs [B, pi+si],
+ * targets [B, so], sample weights [B] and predictions [B, so] are DOUBLE device arrays.  The loss is nif_set_loss's kind, mean over the
+ * outputs, sample-weighted sum / B_global; no regulariser term, by definition (lbfgs.py:66-68 calls the loss function alone).
+ * Buffers are allocated at the first call and freed by nif_destroy; the float32 parameters, gradient buffer, optimizer slots and a
+ * deferred row reduction are not touched.  Built for class NIF and NIFMultiScale under policy float32: the last-layer class and the
+ * mixed policies return NIF_ERR_INVALID; inside nif_graph_begin / nif_graph_end NIF_ERR_STATE (not capturable); forward / loss_grad
+ * before nif_f64_set_params and grad_read before loss_grad NIF_ERR_STATE.  nif_f64_grad_read synchronises; either pointer may be NULL. */
+int nif_f64_set_params(nif_ctx* ctx, const double* host, int64_t n);
+int nif_f64_get_params(nif_ctx* ctx, double* host, int64_t n);
+int nif_f64_forward_dev(nif_ctx* ctx, const double* xin_dev, int64_t B, double* u_dev);
+int nif_f64_loss_grad_dev(nif_ctx* ctx, const double* xin_dev, const double* y_dev, const double* sw_dev_or_null, int64_t B_local,
+                          int64_t B_global);
+int nif_f64_grad_read(nif_ctx* ctx, double* loss_out_or_null, double* grad_host_or_null);
 /* A/B switches for measurement and tests (no reference counterpart).  "fp32_mfma" = 1: every product of the
  * ShapeNet on the f32-input MFMAs instead of the exact bf16 splits (default 0, or NIF_FP32_MFMA=1 in the environment);
  * "fuse_gw", "small_step", "fuse_tail" (default 1; NIF_FUSE_GW / NIF_SMALL_STEP / NIF_FUSE_TAIL = 0): the fused-gradient kernel, the

@@ -13,6 +13,7 @@ COMM_ID_BYTES = 128
 DT_F32, DT_F64, DT_I64 = 0, 1, 2
 POLICY_IDS = {"float32": 0, "mixed_bfloat16": 1, "mixed_float16": 2}
 OP_SUM, OP_MAX, OP_MIN = 0, 1, 2
+F64_CHUNK_POINTS = 4096      # points per chunk of the double-precision L-BFGS closure (k_f64.hip F64_CHUNK)
 
 PROF_NAMES = ["pack", "pnet_fwd", "snet", "pnet_bwd", "gw", "reduce", "adam", "given_w", "latent_to_w", "snet_fwd"]
 
@@ -169,6 +170,11 @@ SIGNATURES = {
     "nif_metric_read": (C.c_int, [_CTX, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
     "nif_last_loss": (C.c_int, [_CTX, _FP]),
     "nif_grad_read": (C.c_int, [_CTX, _FP, _VP]),
+    "nif_f64_set_params": (C.c_int, [_CTX, _VP, C.c_int64]),
+    "nif_f64_get_params": (C.c_int, [_CTX, _VP, C.c_int64]),
+    "nif_f64_forward_dev": (C.c_int, [_CTX, _VP, C.c_int64, _VP]),
+    "nif_f64_loss_grad_dev": (C.c_int, [_CTX, _VP, _VP, _VP, C.c_int64, C.c_int64]),
+    "nif_f64_grad_read": (C.c_int, [_CTX, C.POINTER(C.c_double), _VP]),
     "nif_set_option": (C.c_int, [_CTX, C.c_char_p, C.c_int32]),
     "nif_profile_enable": (C.c_int, [_CTX, C.c_int]),
     "nif_profile_read": (C.c_int, [_CTX, _FP, C.POINTER(C.c_int64), C.c_int, C.c_int]),

@@ -196,6 +196,7 @@ extern "C" int nif_destroy(nif_ctx* c) {
   if (!c) return NIF_OK;
   hipSetDevice(c->dev);
   if (c->st) hipStreamSynchronize(c->st);
+  nif_f64_release(c);
   if (c->small_idx) hipFree(c->small_idx);
   if (c->small_desc) hipFree(c->small_desc);
   if (c->comm) (void)nif_comm_destroy(c);
@@ -2498,6 +2499,29 @@ extern "C" int nif_grad_read(nif_ctx* c, float* loss, float* grad) {
   return NIF_OK;
 }
 
+// ---- the L-BFGS closure in double (k_f64.hip; reference nif/optimizers/lbfgs.py:56-88, lbfgs_V2.py:57-79) -------------------------------
+// A float64 master vector, [grad | loss] buffer and workspace of their own: theta, grad, the optimizer slots and a pending row reduction
+// of the float32 path are neither read nor written, so none of these calls flushes the tail.
+extern "C" int nif_f64_set_params(nif_ctx* c, const double* host, int64_t n) {
+  if (!c || !host) return fail(NIF_ERR_INVALID, "null");
+  return nif_f64_set_params_impl(c, host, n);
+}
+extern "C" int nif_f64_get_params(nif_ctx* c, double* host, int64_t n) {
+  if (!c || !host) return fail(NIF_ERR_INVALID, "null");
+  return nif_f64_get_params_impl(c, host, n);
+}
+extern "C" int nif_f64_forward_dev(nif_ctx* c, const double* xin, int64_t B, double* u) {
+  if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
+  return nif_f64_forward_dev_impl(c, xin, B, u);
+}
+extern "C" int nif_f64_loss_grad_dev(nif_ctx* c, const double* xin, const double* y, const double* sw, int64_t B, int64_t Bg) {
+  if (!c || !xin || !y || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
+  return nif_f64_loss_grad_dev_impl(c, xin, y, sw, B, Bg);
+}
+extern "C" int nif_f64_grad_read(nif_ctx* c, double* loss, double* grad) {
+  if (!c) return fail(NIF_ERR_INVALID, "null");
+  return nif_f64_grad_read_impl(c, loss, grad);
+}
 extern "C" int nif_last_loss(nif_ctx* c, float* loss) {
   if (!c || !loss) return fail(NIF_ERR_INVALID, "null");
   HIPCHK(hipSetDevice(c->dev));

@@ -18,8 +18,11 @@ static inline int fail(int code, const std::string& msg) { return nif_fail(code,
     }                                                                                             \
   } while (0)
 
+struct NifF64;      // state of the double-precision L-BFGS closure (k_f64.hip), allocated at its first use
+
 struct nif_ctx {
   nif_cfg cfg;
+  NifF64* f64 = nullptr;
   int dev = 0;
   hipStream_t st = nullptr;
   // derived sizes
@@ -141,4 +144,11 @@ int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* s
 // the deferred row reduction of the last plain step (nif_ctx::tail_pending), run before anything but the optimizer step touches
 // [grad | loss], the partial rows or the weights (nif_api.hip)
 int nif_tail_flush(nif_ctx* c);
+// the double-precision path behind include/nif_hip.h's nif_f64_* (k_f64.hip); nif_f64_release frees its buffers (nif_destroy)
+int nif_f64_set_params_impl(nif_ctx* c, const double* host, int64_t n);
+int nif_f64_get_params_impl(nif_ctx* c, double* host, int64_t n);
+int nif_f64_forward_dev_impl(nif_ctx* c, const double* xin, int64_t B, double* u);
+int nif_f64_loss_grad_dev_impl(nif_ctx* c, const double* xin, const double* y, const double* sw, int64_t B, int64_t Bg);
+int nif_f64_grad_read_impl(nif_ctx* c, double* loss, double* grad);
+void nif_f64_release(nif_ctx* c);
 #define TAIL_FLUSH(c_) { const int rct_ = nif_tail_flush(c_); if (rct_) return rct_; }

@@ -48,6 +48,35 @@ class DeviceArray(object):
             pass
 
 
+class DeviceArray64(object):
+    """A float64 device buffer owned by an Engine: inputs, targets, sample weights and predictions of the double-precision
+    L-BFGS closure (Engine.f64_*)."""
+
+    def __init__(self, engine, n_doubles):
+        self.engine = engine
+        self.n = int(n_doubles)
+        p = C.c_void_p()
+        check(engine.lib.nif_dev_alloc(engine.ctx, max(self.n, 1) * 8, C.byref(p)))
+        self.ptr = p.value
+
+    def at(self, double_offset):
+        return C.c_void_p(self.ptr + 8 * int(double_offset))
+
+    def upload(self, host, double_offset=0):
+        host = np.ascontiguousarray(host, dtype=np.float64)
+        assert host.size + double_offset <= self.n
+        check(self.engine.lib.nif_h2d(self.engine.ctx, self.at(double_offset), ptr(host), host.size * 8))
+
+    def download(self, n_doubles=None, double_offset=0):
+        n = self.n - double_offset if n_doubles is None else int(n_doubles)
+        out = np.empty((n,), dtype=np.float64)
+        check(self.engine.lib.nif_d2h(self.engine.ctx, ptr(out), self.at(double_offset), n * 8))
+        return out
+
+    free = DeviceArray.free
+    __del__ = DeviceArray.__del__
+
+
 class PinnedArray(object):
     """page-locked host staging buffer (hipHostMalloc through the C-ABI), exposed as a float32 NumPy view"""
 
@@ -521,6 +550,50 @@ class Engine(object):
         s, n = C.c_double(), C.c_double()
         check(self.lib.nif_metric_read(self.ctx, C.byref(s), C.byref(n), 1 if reset else 0))
         return float(s.value), float(n.value)
+
+    # ---- the L-BFGS closure in double precision (include/nif_hip.h nif_f64_*; k_f64.hip) -------------------------------------
+    # A precision of the fine-tuner, not a model policy: a float64 master vector next to the float32 parameters, and the loss and
+    # its gradient evaluated in double on float64 device arrays.  Nothing of the float32 state is touched.
+    def alloc_f64(self, n_doubles):
+        """float64 device buffer on this context's GPU"""
+        return DeviceArray64(self, n_doubles)
+
+    def f64_set_flat(self, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float64)
+        check(self.lib.nif_f64_set_params(self.ctx, ptr(flat), flat.size))
+
+    def f64_get_flat(self):
+        out = np.empty((self.n_params,), dtype=np.float64)
+        check(self.lib.nif_f64_get_params(self.ctx, ptr(out), out.size))
+        return out
+
+    def f64_forward(self, inputs):
+        """predictions [B, so] of the float64 master vector, float64"""
+        x = np.asarray(inputs, dtype=np.float64)
+        ncol = self.spec.pi_dim + self.spec.si_dim
+        if x.ndim != 2 or x.shape[1] < ncol:
+            raise ValueError("inputs: expected shape (batch, %d), got %s" % (ncol, x.shape))
+        x = np.ascontiguousarray(x[:, :ncol])
+        b, so = x.shape[0], self.spec.so_dim
+        if not b:
+            return np.empty((0, so), dtype=np.float64)
+        d_x, d_u = DeviceArray64(self, x.size), DeviceArray64(self, b * so)
+        try:
+            d_x.upload(x)
+            check(self.lib.nif_f64_forward_dev(self.ctx, d_x.at(0), b, d_u.at(0)))
+            return d_u.download().reshape(b, so)
+        finally:
+            d_x.free(); d_u.free()
+
+    def f64_loss_grad_dev(self, d_x, d_y, d_sw, b_local, b_global):
+        check(self.lib.nif_f64_loss_grad_dev(self.ctx, d_x, d_y, d_sw, int(b_local), int(b_global)))
+
+    def f64_grad_read(self):
+        """(loss, flat gradient) of the last f64_loss_grad_dev, both float64"""
+        g = np.empty((self.n_params,), dtype=np.float64)
+        loss = C.c_double()
+        check(self.lib.nif_f64_grad_read(self.ctx, C.byref(loss), ptr(g)))
+        return float(loss.value), g
 
     def set_option(self, key, value):
         check(self.lib.nif_set_option(self.ctx, key.encode(), int(value)))

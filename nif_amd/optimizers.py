@@ -398,11 +398,22 @@ class TFPLBFGS(object):
     on a dataset made resident in HBM once (`nif_loss_grad_dev` + `nif_grad_read`: per evaluation only the P parameters
     go up and P+1 floats come back).  The two-loop recursion and the Hager-Zhang line search (what
     tfp.optimizer.lbfgs_minimize uses; restated from the published algorithm, CG_DESCENT, Hager & Zhang 2005/2006:
-    approximate Wolfe conditions, bracketing by expansion, secant^2 + bisection updates) run on the host in float64."""
+    approximate Wolfe conditions, bracketing by expansion, secant^2 + bisection updates) run on the host in float64.
 
-    def __init__(self, model, loss_fun, inps, outs, display_epoch=1, sample_weight=None):
+    dtype="float64" (the reference's newer fine-tuner switches Keras to float64, lbfgs_V2.py:79) is a precision of the FINE-TUNER,
+    not Keras' float64 policy: the model stays a float32 model; the closure evaluates loss and gradient in double on the device
+    (nif_f64_*, k_f64.hip) at a float64 master vector that starts as the exact upcast of the model's parameters, receives every
+    trial point unrounded, survives between rounds (`position`), and is rounded into the model's float32 parameters after every
+    round.  Inputs, targets and sample weights travel as float64.  Built for class NIF and NIFMultiScale under policy float32."""
+
+    _F64_BUILT = "dtype='float64' is built for class NIF and NIFMultiScale under mixed_policy='float32'"
+
+    def __init__(self, model, loss_fun, inps, outs, display_epoch=1, sample_weight=None, dtype="float32"):
         import numpy as np
         self._np = np
+        if dtype not in ("float32", "float64"):
+            raise ValueError("TFPLBFGS / MSEClosure: dtype is 'float32' or 'float64', got %r" % (dtype,))
+        self.dtype = dtype
         if getattr(model, "_is_pruned", False):
             raise NotImplementedError("TFPLBFGS / LBFGSOptimizer on a pruned model (nif_amd.sparsity): strip_pruning(model) first")
         if getattr(model, "_order", 1) == 2:
@@ -421,6 +432,9 @@ class TFPLBFGS(object):
         self._loss = "mse" if name is None else ("mse", "mae", "huber", "log_cosh")[_lib.LOSS_IDS[name]]
         self.model = model
         e = model._engine
+        if dtype == "float64":
+            self._init_f64(e, inps, outs, sample_weight, display_epoch)
+            return
         x = e._inputs(inps)
         self._B = x.shape[0]
         y = e._targets(outs, self._B)
@@ -434,6 +448,82 @@ class TFPLBFGS(object):
         self.display_epoch = max(int(display_epoch), 1)
         self._losses = []
 
+    def _init_f64(self, e, inps, outs, sample_weight, display_epoch):
+        np = self._np
+        model = self.model
+        if hasattr(model, "_order"):
+            raise NotImplementedError("TFPLBFGS / MSEClosure(dtype='float64') on a Sobolev model is not built (%s)" % self._F64_BUILT)
+        if e.spec.kind == "NIFMultiScaleLastLayerParameterized":
+            raise NotImplementedError("TFPLBFGS / MSEClosure(dtype='float64') on NIFMultiScaleLastLayerParameterized is not built (%s)"
+                                      % self._F64_BUILT)
+        if e.spec.mixed_policy != "float32":
+            raise NotImplementedError("TFPLBFGS / MSEClosure(dtype='float64') on a model built under mixed_policy=%r is not built (%s)"
+                                      % (e.spec.mixed_policy, self._F64_BUILT))
+        ncol, so = e.spec.pi_dim + e.spec.si_dim, e.spec.so_dim
+        x = np.asarray(inps, dtype=np.float64)            # float64 arrays of the caller are NOT rounded to float32
+        if x.ndim != 2 or x.shape[1] < ncol:
+            raise ValueError("inputs: expected shape (batch, %d), got %s" % (ncol, x.shape))
+        x = np.ascontiguousarray(x[:, :ncol])
+        self._B = x.shape[0]
+        y = np.asarray(outs, dtype=np.float64)
+        if y.ndim == 1:
+            y = y[:, None]
+        if y.shape != (self._B, so):
+            raise ValueError("targets: expected shape (%d, %d), got %s" % (self._B, so, y.shape))
+        y = np.ascontiguousarray(y)
+        self._d_x, self._d_y = e.alloc_f64(x.size), e.alloc_f64(y.size)
+        self._d_x.upload(x); self._d_y.upload(y)
+        self._d_sw = None
+        if sample_weight is not None:
+            sw = np.ascontiguousarray(sample_weight, dtype=np.float64).reshape(-1)
+            if sw.shape != (self._B,):
+                raise ValueError("sample_weight: expected shape (%d,), got %s" % (self._B, sw.shape))
+            self._d_sw = e.alloc_f64(sw.size); self._d_sw.upload(sw)
+        self._master = e.get_flat().astype(np.float64)    # the exact upcast of the model's float32 parameters
+        e.f64_set_flat(self._master)
+        self.display_epoch = max(int(display_epoch), 1)
+        self._losses = []
+
+    @property
+    def position(self):
+        """the fine-tuner's parameter vector: dtype='float64' the float64 master vector (kept between rounds and minimize() calls),
+        else the model's float32 parameters"""
+        if self.dtype == "float64":
+            return self._master.copy()
+        return self.model._engine.get_flat()
+
+    def _commit(self, x):
+        """lbfgs.py:120 / lbfgs_V2.py:112 assign the result: dtype='float64' keeps x as the master vector and gives the model its
+        rounding, so that predict, save_weights and a later fit see the fine-tuned model"""
+        np = self._np
+        e = self.model._engine
+        if self.dtype == "float64":
+            self._master = np.array(x, dtype=np.float64)
+            e.f64_set_flat(self._master)
+        e.set_flat(x.astype(np.float32))
+
+    def _start(self):
+        np = self._np
+        return self._master.copy() if self.dtype == "float64" else self.model._engine.get_flat().astype(np.float64)
+
+    def _f64(self, theta):
+        """the closure in double: theta goes up unrounded, loss and gradient come back as float64"""
+        np = self._np
+        e = self.model._engine
+        e.f64_set_flat(np.ascontiguousarray(theta, dtype=np.float64))
+        if hasattr(e, "set_loss"):
+            e.set_loss(self._loss)            # (the double path has no regulariser term to switch off: the loss kind alone)
+        try:
+            e.f64_loss_grad_dev(self._d_x.at(0), self._d_y.at(0), self._d_sw.at(0) if self._d_sw is not None else None, self._B, self._B)
+            loss, g = e.f64_grad_read()
+        finally:
+            if hasattr(e, "set_loss"):
+                e.set_loss("mse")
+        self._losses.append(loss)
+        if len(self._losses) % self.display_epoch == 0:
+            print("Epoch: %d loss: %.8e" % (len(self._losses), loss))
+        return float(loss), g
+
     @property
     def history(self):
         """lbfgs.py:123-126"""
@@ -441,6 +531,8 @@ class TFPLBFGS(object):
 
     def _f(self, theta):
         """lbfgs.py:56-88: assign the parameters, loss and flat gradient; every call is counted and recorded"""
+        if getattr(self, "dtype", "float32") == "float64":
+            return self._f64(theta)
         np = self._np
         e = self.model._engine
         e.set_flat(theta.astype(np.float32))
@@ -457,12 +549,9 @@ class TFPLBFGS(object):
 
     def minimize(self, rounds=50, max_iter=50):
         """lbfgs.py:103-121: `rounds` independent lbfgs_minimize calls, each from the model's current variables"""
-        np = self._np
-        e = self.model._engine
         for _ in range(rounds):
-            x0 = e.get_flat().astype(np.float64)
-            x, _f = LBFGSMinimizer(self._f).run(x0, max_iter)
-            e.set_flat(x.astype(np.float32))      # lbfgs.py:120 assign_new_model_parameters(results.position)
+            x, _f = LBFGSMinimizer(self._f).run(self._start(), max_iter)
+            self._commit(x)                       # lbfgs.py:120 assign_new_model_parameters(results.position)
         return self.history
 
 
@@ -471,13 +560,13 @@ class MSEClosure(object):
     (lbfgs_V2.py:77-85: `loss_closure` = "the model's loss on the training table"): the model, its full-batch table and
     optional sample weights -- resident in HBM once; calling it returns the current loss like the reference's closure does."""
 
-    def __init__(self, model, x, y, sample_weight=None):
-        self._t = TFPLBFGS(model, "mse", x, y, display_epoch=1 << 62, sample_weight=sample_weight)
+    def __init__(self, model, x, y, sample_weight=None, dtype="float32"):
+        self._t = TFPLBFGS(model, "mse", x, y, display_epoch=1 << 62, sample_weight=sample_weight, dtype=dtype)
         self.model = model
+        self.dtype = dtype
 
     def __call__(self):
-        e = self.model._engine
-        return self._t._f(e.get_flat().astype(self._t._np.float64))[0]
+        return self._t._f(self._t._start())[0]
 
 
 class LBFGSOptimizer(object):
@@ -508,12 +597,14 @@ class LBFGSOptimizer(object):
         return self._loss
 
     def minimize(self):
-        import numpy as np
         t = self._c._t
-        e = self._c.model._engine
         mz = LBFGSMinimizer(t._f)
-        x0 = e.get_flat().astype(np.float64)
-        x, f, self._state, done = mz.run_resumable(x0, self.steps, self._state)
+        x, f, self._state, done = mz.run_resumable(t._start(), self.steps, self._state)
         self._it += done
         self._loss = float(f)
-        e.set_flat(x.astype(np.float32))           # lbfgs_V2.py:112 assign(results.position)
+        t._commit(x)                               # lbfgs_V2.py:112 assign(results.position)
+
+    @property
+    def position(self):
+        """the closure's parameter vector: a MSEClosure(dtype='float64') keeps its float64 master vector between minimize() calls"""
+        return self._c._t.position
