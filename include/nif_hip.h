@@ -245,7 +245,9 @@ int nif_sobolev_forward_dev(nif_ctx* ctx, const float* xin_dev, int64_t B, const
  * and nif_graph_end the device-side calls on this context are recorded instead of executed -- e.g. all batches of one epoch:
  * nif_loss_grad_dev / nif_sobolev_loss_grad_dev[_y], nif_adam_step_dev, nif_metric_accumulate; nif_graph_launch replays them in one
  * submission (pointers as recorded; Adam's hyper-parameters from `opt`, its iteration count continues from the context's).
- * Workspaces must have been sized by nif_reserve; contexts with a communicator attached are refused. */
+ * Workspaces must have been sized by nif_reserve; contexts with a communicator attached are refused.
+ * A replay rewrites [grad | loss]: a nif_metric_accumulate that was deferred behind an eager step (see there) is settled BEFORE the
+ * graph runs, with the loss of the step it was called for; the graph's own recorded accumulations follow it in the sum. */
 int nif_graph_begin(nif_ctx* ctx);
 int nif_graph_end(nif_ctx* ctx, int32_t* graph_id_out);
 int nif_graph_launch(nif_ctx* ctx, int32_t graph_id, const nif_adam* opt);
@@ -373,7 +375,10 @@ int nif_set_jac_regularizer(nif_ctx* ctx, float l1);
  * passes recompute it on the fly (k_actreg_*; latent_dim <= 64).  On the last-layer class pnet_out is the small [B, latent_dim]
  * tensor itself: one pass (k_ll_actreg). */
 int nif_set_activity_regularizer(nif_ctx* ctx, float l1, float l2);
-/* Keras' epoch loss metric without a host sync per batch: sum += weight * grad[P], count += weight (device side) */
+/* Keras' epoch loss metric without a host sync per batch: sum += weight * grad[P], count += weight (device side), with grad[P] as it
+ * stands at THIS call.  Behind a small-batch step the addition may wait for the next such step's launch; it is settled first by every
+ * call that rewrites grad[P] or reads the metric: nif_metric_read, a graph replay (nif_graph_launch[_opt]), nif_zero_grad, the
+ * regulariser term of an optimizer step / nif_grad_read / nif_grad_transform_dev, nif_comm_init_rank / _all, nif_comm_selftest. */
 int nif_metric_accumulate(nif_ctx* ctx, float weight);
 int nif_metric_read(nif_ctx* ctx, double* sum_out, double* count_out, int reset);
 /* reads grad[P] (the loss of the last nif_loss_grad_dev) */

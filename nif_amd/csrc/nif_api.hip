@@ -1458,10 +1458,18 @@ static int ensure_small_tables(nif_ctx* c, const PNetArgs& pa, const SNetArgs& s
   if (c->capturing) return fail(NIF_ERR_STATE, "small-batch step tables inside a graph capture (nif_graph_begin builds them)");
   std::vector<int> idx, desc;
   small_tables(pa, sa, idx, desc);
-  HIPCHK(hipMalloc(&c->small_idx, idx.size() * sizeof(int)));
-  HIPCHK(hipMalloc(&c->small_desc, desc.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(c->small_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(c->small_desc, desc.data(), desc.size() * sizeof(int), hipMemcpyHostToDevice));
+  // the context takes the tables only when both exist and are filled: a failure on the way leaves it without any (the next call tries again)
+  int *d_idx = nullptr, *d_desc = nullptr;
+  hipError_t e = hipMalloc(&d_idx, idx.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&d_desc, desc.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_desc, desc.data(), desc.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (d_idx) (void)hipFree(d_idx);
+    if (d_desc) (void)hipFree(d_desc);
+    HIPCHK(e);
+  }
+  c->small_idx = d_idx; c->small_desc = d_desc;
   return NIF_OK;
 }
 // r6: the row reduction of a plain step waits for its consumer when nothing else needs [grad | loss] first: the optimizer step runs it fused
@@ -1484,8 +1492,9 @@ static bool tail_can_defer(const nif_ctx* c) {
 }
 // a Keras loss-metric accumulation that nif_metric_accumulate left for the next k_small launch (r6: one launch less per small step):
 // everything that would change grad[P] or read the metric without such a launch runs it now
-static int metric_flush(nif_ctx* c) {
-  if (!c->metric_pending) return NIF_OK;
+int nif_metric_flush(nif_ctx* c) {
+  if (!c || !c->metric_pending) return NIF_OK;
+  HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   c->metric_pending = false;
   launch_metric(c->grad, c->P, c->metric_pending_w, c->metric, c->st);
@@ -1524,7 +1533,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
       return NIF_OK;
     }
   }
-  int rc = metric_flush(c); if (rc) return rc;
+  int rc = nif_metric_flush(c); if (rc) return rc;
   rc = ensure_packed(c); if (rc) return rc;
   const long ntiles = (B + 31) / 32;
   if (ns > 0) { rc = ensure_packed32(c); if (rc) return rc; }
@@ -1856,13 +1865,19 @@ static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const 
   return NIF_OK;
 }
 
-static void apply_reg(nif_ctx* c) {
-  if (c->reg_applied) return;
-  if ((c->reg_l1 != 0.f || c->reg_l2 != 0.f) && c->reg_hi > c->reg_lo)
-    launch_reg(c->theta, c->grad, c->reg_lo, c->reg_hi, c->P, c->reg_l1, c->reg_l2, c->st);
-  if ((c->sreg_l1 != 0.f || c->sreg_l2 != 0.f) && c->kind == NIF_KIND_LASTLAYER)
-    launch_reg(c->theta, c->grad, c->s_first_w, c->ll_bias, c->P, c->sreg_l1, c->sreg_l2, c->st);
+// The term is marked as applied only when one was added: with no regulariser set, a read of the gradient (nif_grad_read) must not keep a
+// regulariser that is set afterwards out of the update of the same gradient.  The term lands in grad[P] too: a loss-metric accumulation
+// that waits for the next k_small launch takes the loss as it stood at its call, so it runs first.
+static int apply_reg(nif_ctx* c) {
+  if (c->reg_applied) return NIF_OK;
+  const bool wreg = (c->reg_l1 != 0.f || c->reg_l2 != 0.f) && c->reg_hi > c->reg_lo;
+  const bool sreg = (c->sreg_l1 != 0.f || c->sreg_l2 != 0.f) && c->kind == NIF_KIND_LASTLAYER;
+  if (!wreg && !sreg) return NIF_OK;
+  { const int rc = nif_metric_flush(c); if (rc) return rc; }
+  if (wreg) launch_reg(c->theta, c->grad, c->reg_lo, c->reg_hi, c->P, c->reg_l1, c->reg_l2, c->st);
+  if (sreg) launch_reg(c->theta, c->grad, c->s_first_w, c->ll_bias, c->P, c->sreg_l1, c->sreg_l2, c->st);
   c->reg_applied = true;
+  return NIF_OK;
 }
 // cfg_shape_net["l1_reg" / "l2_reg"] of the last-layer class (nif/model.py:1028-1039, handed to every SIREN / SIREN_ResNet of the
 // shared ShapeNet at :1168-1211; siren.py:266-269, :393-398 add them for kernels AND biases): theta[s_first_w, ll_bias) -- first,
@@ -2017,7 +2032,7 @@ extern "C" int nif_metric_accumulate(nif_ctx* c, float weight) {
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   if (!c->metric) { HIPCHK(hipMalloc(&c->metric, 2 * sizeof(double))); HIPCHK(hipMemsetAsync(c->metric, 0, 2 * sizeof(double), c->st)); }
-  int rc = metric_flush(c); if (rc) return rc;
+  int rc = nif_metric_flush(c); if (rc) return rc;
   if (c->last_step_small && c->opt_small_step && !c->capturing && !c->comm) {     // behind a small step: rides in the next k_small launch (grad[P] is not
     c->metric_pending = true; c->metric_pending_w = weight;          // touched before that launch's row reduction; every other path flushes)
     return NIF_OK;
@@ -2031,7 +2046,7 @@ extern "C" int nif_metric_read(nif_ctx* c, double* sum, double* cnt, int reset) 
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   double h[2] = {0.0, 0.0};
-  { const int rcf = metric_flush(c); if (rcf) return rcf; }
+  { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }
   if (c->metric) {
     HIPCHK(hipMemcpyAsync(h, c->metric, 2 * sizeof(double), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -2053,7 +2068,7 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
   if (c->comm) return fail(NIF_ERR_STATE, "nif_graph_begin: not with a communicator attached (the all-reduce is not captured)");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  int rc = metric_flush(c); if (rc) return rc;
+  int rc = nif_metric_flush(c); if (rc) return rc;
   c->last_step_small = false;
   rc = ensure_packed(c); if (rc) return rc;
   if (c->kind != NIF_KIND_LASTLAYER) {      // (a captured small step must find its tables)
@@ -2076,6 +2091,7 @@ extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   if (!c || !graph_id) return fail(NIF_ERR_INVALID, "null");
   if (!c->capturing) return fail(NIF_ERR_STATE, "nif_graph_end without nif_graph_begin");
   c->capturing = false;
+  c->last_step_small = false;              // (set by the RECORDED small steps: no eager one ran, the next nif_metric_accumulate must not wait for a k_small launch)
   c->step = c->cap_step0;                  // nothing has run yet: the recorded steps count when the graph is launched
   c->packed = false; c->packed32 = false; c->packed_p32 = false;
   hipGraph_t g = nullptr;
@@ -2174,7 +2190,7 @@ extern "C" int nif_grad_transform_dev(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  apply_reg(c);
+  { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
   if (c->gt_on) gt_run(c);
   HIPCHK(hipGetLastError());
   return NIF_OK;
@@ -2256,7 +2272,7 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
     c->tail_pending = false;
   } else {
     TAIL_FLUSH(c)
-    apply_reg(c);
+    { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
     if (c->gt_on) gt_run(c);
   }
   c->step += 1;
@@ -2298,6 +2314,7 @@ static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const 
     return fail(NIF_ERR_STATE, std::string(who) + ": the context's gradient transform needs launches this graph did not record (set it before the capture)");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
+  { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }      // (the replay overwrites grad[P]: a deferred accumulation takes the loss of the step it was called for)
   HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
   *c->opt_host = opt_dev_of(opt, c->step);
   HIPCHK(hipMemcpyAsync(c->opt_dev, c->opt_host, sizeof(OptDev), hipMemcpyHostToDevice, c->st));
@@ -2360,7 +2377,7 @@ static int prune_enter(nif_ctx* c, bool need_config) {
   if (need_config && c->prune_segs.empty()) return fail(NIF_ERR_STATE, "pruning is not configured (nif_prune_config)");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  return metric_flush(c);
+  return nif_metric_flush(c);
 }
 extern "C" int nif_prune_config(nif_ctx* c, int32_t n, const int64_t* offsets, const int64_t* sizes) {
   if (!c || n < 0 || (n > 0 && (!offsets || !sizes))) return fail(NIF_ERR_INVALID, "bad argument");
@@ -2454,7 +2471,7 @@ extern "C" int nif_zero_grad(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  { const int rcf = metric_flush(c); if (rcf) return rcf; }      // (a deferred loss-metric accumulation reads grad[P]: before it is cleared)
+  { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }      // (a deferred loss-metric accumulation reads grad[P]: before it is cleared)
   c->last_step_small = false;
   HIPCHK(hipMemsetAsync(c->grad, 0, sizeof(float) * (size_t)(c->P + 1), c->st));
   c->reg_applied = false;
@@ -2492,7 +2509,7 @@ extern "C" int nif_grad_read(nif_ctx* c, float* loss, float* grad) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  apply_reg(c);
+  { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
   if (grad) HIPCHK(hipMemcpyAsync(grad, c->grad, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToHost, c->st));
   if (loss) HIPCHK(hipMemcpyAsync(loss, c->grad + c->P, sizeof(float), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -2553,7 +2570,7 @@ extern "C" int nif_loss_and_grad(nif_ctx* c, const float* xin, const float* y, c
   int rc = stage_batch(c, xin, y, sw, B); if (rc) return rc;
   rc = nif_loss_grad_dev(c, c->d_a, c->d_b, sw ? c->d_c : nullptr, B, B); if (rc) return rc;
   TAIL_FLUSH(c)
-  apply_reg(c);
+  { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
   if (grad) HIPCHK(hipMemcpyAsync(grad, c->grad, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToHost, c->st));
   if (loss) HIPCHK(hipMemcpyAsync(loss, c->grad + c->P, sizeof(float), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));

@@ -50,6 +50,7 @@ extern "C" int nif_comm_init_rank(nif_ctx* c, const void* id, int32_t rank, int3
   if (c->comm) return fail(NIF_ERR_STATE, "context already has a communicator");
   HIPCHK(hipSetDevice(c->dev));
   { const int rct = nif_tail_flush(c); if (rct) return rct; }      // (a deferred row reduction: the all-reduce reads [grad | loss])
+  { const int rcm = nif_metric_flush(c); if (rcm) return rcm; }    // (a deferred metric accumulation: with a communicator nothing defers, and the all-reduce rewrites grad[P])
   ncclUniqueId uid;
   memcpy(&uid, id, NIF_COMM_ID_BYTES);
   ncclComm_t comm = nullptr;
@@ -65,6 +66,7 @@ extern "C" int nif_comm_init_all(nif_ctx** ctxs, int32_t n) {
     if (!ctxs[i]) return fail(NIF_ERR_INVALID, "null context");
     if (ctxs[i]->comm) return fail(NIF_ERR_STATE, "context already has a communicator");
     { const int rct = nif_tail_flush(ctxs[i]); if (rct) return rct; }
+    { const int rcm = nif_metric_flush(ctxs[i]); if (rcm) return rcm; }
     devs[i] = ctxs[i]->dev;
     for (int j = 0; j < i; ++j)
       if (devs[j] == devs[i]) return fail(NIF_ERR_INVALID, "two contexts of one communicator on the same device");
@@ -136,6 +138,7 @@ extern "C" int nif_comm_selftest(nif_ctx* c, int32_t* ranks_seen) {
   if (!c->grad) return fail(NIF_ERR_STATE, "no gradient buffer");
   HIPCHK(hipSetDevice(c->dev));
   { const int rct = nif_tail_flush(c); if (rct) return rct; }
+  { const int rcm = nif_metric_flush(c); if (rcm) return rcm; }    // (the buffer is about to be filled and zeroed)
   const long n = c->P + 1;
   hipLaunchKernelGGL(k_fill_f32, dim3(64), dim3(256), 0, c->st, c->grad, n, (float)(c->comm_rank + 1));
   int rc = nif_allreduce_grad(c); if (rc) return rc;

@@ -127,7 +127,7 @@ struct ProfScope {
   nif_ctx* c; int id; hipEvent_t a = nullptr, b = nullptr;
   hipStream_t s;
   ProfScope(nif_ctx* c_, int id_, hipStream_t s_ = nullptr) : c(c_), id(id_), s(s_ ? s_ : c_->st) {
-    if (!c->prof_on) return;
+    if (!c->prof_on || c->capturing) return;      // (an event recorded into a capture is a graph node: it never holds a time, and reading it fails)
     auto get = [&]() { hipEvent_t e; if (!c->ev_pool.empty()) { e = c->ev_pool.back(); c->ev_pool.pop_back(); } else { (void)hipEventCreate(&e); } return e; };
     a = get(); b = get();
     (void)hipEventRecord(a, s);
@@ -144,6 +144,9 @@ int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* s
 // the deferred row reduction of the last plain step (nif_ctx::tail_pending), run before anything but the optimizer step touches
 // [grad | loss], the partial rows or the weights (nif_api.hip)
 int nif_tail_flush(nif_ctx* c);
+// a nif_metric_accumulate that waits for the next k_small launch (nif_ctx::metric_pending), run before anything else rewrites grad[P]
+// or reads the metric (nif_api.hip); runs the deferred row reduction first
+int nif_metric_flush(nif_ctx* c);
 // the double-precision path behind include/nif_hip.h's nif_f64_* (k_f64.hip); nif_f64_release frees its buffers (nif_destroy)
 int nif_f64_set_params_impl(nif_ctx* c, const double* host, int64_t n);
 int nif_f64_get_params_impl(nif_ctx* c, double* host, int64_t n);

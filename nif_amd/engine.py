@@ -224,6 +224,10 @@ class Engine(object):
             check(self.lib.nif_forward(self.ctx, ptr(x), x.shape[0], ptr(out)))
         return out
 
+    def forward_dev(self, d_x, b, d_u):
+        """predictions of device-resident rows [b, pi+si] into a device buffer [b, so] (nif_forward_dev); asynchronous"""
+        check(self.lib.nif_forward_dev(self.ctx, d_x, int(b), d_u))
+
     def p_to_lr(self, p):
         p = self._rows(p, self.spec.pi_dim, "parameter inputs")
         out = np.empty((p.shape[0], self.spec.pi_hidden), dtype=np.float32)
@@ -525,6 +529,23 @@ class Engine(object):
 
     def allreduce_grad(self):
         check(self.lib.nif_allreduce_grad(self.ctx))
+
+    # the communicator of this context (include/nif_hip.h "multi-GPU"; nif_amd.distributed.RcclComm carries the id between processes)
+    def comm_unique_id(self):
+        buf = C.create_string_buffer(_lib.COMM_ID_BYTES)
+        check(self.lib.nif_comm_unique_id(buf))
+        return buf.raw
+
+    def comm_init_rank(self, uid, rank, world):
+        check(self.lib.nif_comm_init_rank(self.ctx, C.create_string_buffer(uid, _lib.COMM_ID_BYTES), int(rank), int(world)))
+
+    def comm_selftest(self):
+        n = C.c_int32()
+        check(self.lib.nif_comm_selftest(self.ctx, C.byref(n)))
+        return int(n.value)
+
+    def comm_destroy(self):
+        check(self.lib.nif_comm_destroy(self.ctx))
 
     def set_regularizer(self, l1, l2, lo, hi):
         check(self.lib.nif_set_regularizer(self.ctx, float(l1), float(l2), int(lo), int(hi)))

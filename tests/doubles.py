@@ -229,3 +229,41 @@ def bench_double(points):
     spec = O.Spec("NIFMultiScale", bench.CFG_SHAPE, bench.CFG_PARAM)
     ws = O.init_weights(spec, np.random.default_rng(1))
     return OracleEngine(spec, ws), comm, (lambda engine, n: _HostArray(n))
+
+
+class DeferredMetricEngine(object):
+    """A context reduced to the loss slot, the metric and ONE deferred piece, with a planted order bug (tests/test_api_order.py, the
+    shrinker): metric_accumulate behind a step is deferred, and `replay` rewrites the loss slot WITHOUT settling it first -- the hole
+    nif_graph_launch had.  Every other call settles it."""
+
+    def __init__(self, planted_bug=True):
+        self.planted_bug = planted_bug
+        self.loss, self.metric, self.pending, self.theta = 0.0, [0.0, 0.0], None, 1.0
+
+    def _flush(self):
+        if self.pending is not None:
+            self.metric[0] += self.pending * self.loss; self.metric[1] += self.pending
+            self.pending = None
+
+    def step(self, scale):
+        self._flush()
+        self.loss = scale * self.theta
+
+    def metric_accumulate(self, weight):
+        self._flush()
+        self.pending = weight
+
+    def replay(self):
+        if not self.planted_bug:
+            self._flush()
+        self.loss = 3.0 * self.theta
+
+    def update(self):
+        self.theta *= 0.5
+
+    def metric_read(self, reset=True):
+        self._flush()
+        s, n = self.metric
+        if reset:
+            self.metric = [0.0, 0.0]
+        return s, n
