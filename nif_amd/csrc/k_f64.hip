@@ -24,6 +24,7 @@
 #include "nif_ctx.h"
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #define F64_CHUNK 4096      // points per chunk
@@ -47,8 +48,8 @@ struct F64Args {
 struct F64Job { const double* IN; const double* DA; const double* ZT; int nin, nout, K, wave0; MatRef W; double scale; };
 
 struct NifF64 {
-  double *theta = nullptr, *g = nullptr, *stash = nullptr, *part = nullptr;
-  F64Job* jobs = nullptr; int njobs = 0, job_waves = 0;
+  DevBuf<double> theta, g, stash, part;
+  DevBuf<F64Job> jobs; int njobs = 0, job_waves = 0;
   int S = F64_SEGS, seglen = F64_CHUNK / F64_SEGS; long pstride = 0;
   bool have_params = false, have_grad = false;
   F64Args a;
@@ -471,8 +472,8 @@ static MatRef f64_hyper(const nif_ctx* c, long slot, int ld, int nin, int nout) 
 
 static int f64_ensure(nif_ctx* c) {
   if (c->f64) return NIF_OK;
-  NifF64* f = new NifF64();
-  c->f64 = f;
+  std::unique_ptr<NifF64> own(new NifF64());      // joins the context after the last step that can fail
+  NifF64* f = own.get();
   F64Args& a = f->a;
   memset(&a, 0, sizeof(a));
   a.ncol = c->pi + c->si;
@@ -494,10 +495,10 @@ static int f64_ensure(nif_ctx* c) {
   f->pstride = (P + 1 + 15) / 16 * 16;
   const long rows = c->pi + nst + (long)(lst + 1) * nst + 3L * lst * nst + nst + 2L * lst * nst + 2L * nst + K + K + (long)nit * K + c->si + n +
                     (long)(nh + 1) * n + (long)nh * n + n + (long)nh * n + c->so + 3L * n + 1;
-  HIPCHK(hipMalloc(&f->theta, sizeof(double) * (size_t)P));
-  HIPCHK(hipMalloc(&f->g, sizeof(double) * (size_t)(P + 1)));
-  HIPCHK(hipMalloc(&f->stash, sizeof(double) * (size_t)rows * CH));
-  HIPCHK(hipMalloc(&f->part, sizeof(double) * (size_t)f->pstride * f->S));
+  int rc = f->theta.alloc(P); if (rc) return rc;
+  rc = f->g.alloc(P + 1); if (rc) return rc;
+  rc = f->stash.alloc(rows * CH); if (rc) return rc;
+  rc = f->part.alloc(f->pstride * f->S); if (rc) return rc;
   HIPCHK(hipMemsetAsync(f->stash, 0, sizeof(double) * (size_t)rows * CH, c->st));
   HIPCHK(hipMemsetAsync(f->part, 0, sizeof(double) * (size_t)f->pstride * f->S, c->st));
   HIPCHK(hipMemsetAsync(f->g, 0, sizeof(double) * (size_t)(P + 1), c->st));
@@ -532,20 +533,14 @@ static int f64_ensure(nif_ctx* c) {
   f64_add_job(jobs, waves, a.H + (long)nh * n * CH, a.GU, a.ZT, n, c->so, K, f64_hyper(c, f64_wl(a), c->so, n, c->so), 1.0);
   f64_add_job(jobs, waves, nullptr, a.GU, a.ZT, 1, c->so, K, f64_hyper(c, f64_bl(a), 0, 1, c->so), 1.0);
   f->njobs = (int)jobs.size(); f->job_waves = waves;
-  HIPCHK(hipMalloc(&f->jobs, sizeof(F64Job) * jobs.size()));
+  rc = f->jobs.alloc((long)jobs.size()); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(f->jobs, jobs.data(), sizeof(F64Job) * jobs.size(), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));      // (the host table goes out of scope)
+  c->f64 = own.release();
   return NIF_OK;
 }
 
-void nif_f64_release(nif_ctx* c) {
-  NifF64* f = c->f64;
-  if (!f) return;
-  void* ptrs[] = {f->theta, f->g, f->stash, f->part, f->jobs};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  delete f;
-  c->f64 = nullptr;
-}
+void nif_f64_release(nif_ctx* c) { delete c->f64; c->f64 = nullptr; }
 
 int nif_f64_set_params_impl(nif_ctx* c, const double* host, int64_t n) {
   int rc = f64_supported(c, "nif_f64_set_params"); if (rc) return rc;

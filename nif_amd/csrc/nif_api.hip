@@ -86,6 +86,51 @@ static int build_layout(nif_ctx* c) {
   return 0;
 }
 
+// the stream and every buffer whose size the configuration fixes
+static int create_buffers(nif_ctx* c) {
+  const int nh = c->nh, nm = c->nm;
+  HIPCHK(hipSetDevice(c->dev));
+  HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  const long pn = c->P + 2;   // [grad | loss | one scratch word of the two-level row reduction]
+  for (DevBuf<float>* b : {&c->theta, &c->grad, &c->m, &c->v}) { const int rc = b->alloc(pn); if (rc) return rc; }
+  for (float* b : {c->m.p, c->v.p, c->grad.p}) HIPCHK(hipMemset(b, 0, sizeof(float) * (size_t)pn));
+  int rc = NIF_OK;
+  const long pk_p = (long)(nm > 0 ? nm : 1) * c->NSTB * c->NSTB * 256;      // in f32x4
+  long pk_s = (long)(nh > 0 ? nh : 1) * (c->r + 1) * c->NB * c->NB * 256;
+  {
+    const long pk16 = (long)(nh > 0 ? nh : 1) * (c->r + 1) * snet3_plane_floats(c->n) / 4;
+    if (pk16 > pk_s) pk_s = pk16;
+  }
+  if (!rc) rc = c->pWF.alloc(pk_p);
+  if (!rc) rc = c->pWB.alloc(pk_p);
+  if (!rc) rc = c->sWF.alloc(pk_s);
+  if (!rc) rc = c->sWB.alloc(pk_s);
+  if (nh > 0 && !(snet3_nbl(c->n) & 1) && c->n <= 128) {
+    const int rr = c->kind == NIF_KIND_LASTLAYER ? 0 : c->r;   // last-layer class: shared dense weights, one plane
+    if (!rc) rc = c->sWF4.alloc((long)nh * snet4_fwd_elems(c->n, rr) * 2);
+    if (!rc) rc = c->sWB4.alloc((long)nh * snet4_bwd_elems(c->n, rr) * 2);
+    if (c->kind != NIF_KIND_NIF) {   // SIREN nets (r5): the exact-product half planes of k_snet4<.., PR = 3> / k_snet6 (class NIF keeps the bf16 splits)
+      if (!rc) rc = c->sWF4x.alloc((long)nh * snet4_bwd_elems(c->n, rr) * 2);
+      if (!rc) rc = c->sWB4x.alloc((long)nh * snet4_bwd_elems(c->n, rr) * 2);
+      if (!rc) rc = c->sWscale.alloc((long)nh * (rr + 1) * 2);
+    }
+    if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32) {     // the policy's compact plane set (k_snet4 / k_snet6<.., PR>), next to the exact splits
+      if (!rc) rc = c->sWF4h.alloc((long)nh * (snet4_fwd_elems(c->n, rr) / 3) * 2);
+      if (!rc) rc = c->sWB4h.alloc((long)nh * (snet4_bwd_elems(c->n, rr) / 2) * 2);
+    }
+    if (c->kind == NIF_KIND_LASTLAYER && !rc) rc = c->ll_wpf.alloc((long)snet4_phi_fwd_elems(c->n) * 2);
+    if (c->kind == NIF_KIND_LASTLAYER && !rc) rc = c->ll_wpb.alloc((long)snet4_phi_bwd_elems(c->n) * 2);
+  }
+  // slot-ordered copy of the dense ShapeNet parameters of the last-layer class (k_snet4<LL>, k_sob<LL>, k_jac on the r = 0 arguments)
+  if (c->kind == NIF_KIND_LASTLAYER && nh > 0 && c->n <= 128 && !rc)
+    rc = c->ll_slots.alloc((long)c->si * c->n + (long)nh * c->n * c->n + (long)c->n * c->so * c->r +
+                           c->n + (long)nh * c->n + c->so * c->r + c->so + c->r * c->r + 64);
+  const long pk_l = (long)(nh > 0 ? nh : 1) * c->NB * c->NB * 256;
+  if (!rc && c->kind == NIF_KIND_LASTLAYER) rc = c->lWF.alloc(pk_l);
+  if (!rc && c->kind == NIF_KIND_LASTLAYER) rc = c->lWB.alloc(pk_l);
+  return rc;
+}
+
 extern "C" int nif_create(const nif_cfg* cfg, int device_id, nif_ctx** out) {
   if (!cfg || !out) return fail(NIF_ERR_INVALID, "null argument");
   if (cfg->abi_version != NIF_ABI_VERSION) return fail(NIF_ERR_INVALID, "abi_version mismatch");
@@ -121,7 +166,8 @@ extern "C" int nif_create(const nif_cfg* cfg, int device_id, nif_ctx** out) {
     return fail(NIF_ERR_INVALID, "class NIF has no resblock / sine ParameterNet");
   if (cfg->p_resblock && cfg->kind == NIF_KIND_NIF) return fail(NIF_ERR_INVALID, "bad cfg");
 
-  nif_ctx* c = new nif_ctx();
+  std::unique_ptr<nif_ctx> own(new nif_ctx());      // (a failure below frees the stream and every buffer made so far: ~nif_ctx)
+  nif_ctx* c = own.get();
   c->cfg = *cfg;
   { const char* e = getenv("NIF_FP32_MFMA"); c->opt_fp32_mfma = e && e[0] == '1'; }
   { const char* e = getenv("NIF_FUSE_GW"); c->opt_fuse_gw = !(e && e[0] == '0'); }
@@ -140,78 +186,27 @@ extern "C" int nif_create(const nif_cfg* cfg, int device_id, nif_ctx** out) {
   if (c->kind == NIF_KIND_LASTLAYER) c->po = c->r;   // model.py:583-585
   c->RB = (c->r + 31) / 32;
   build_layout(c);
-  hipError_t e = hipSetDevice(device_id);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking);
-  const size_t pb = (size_t)(c->P + 2) * sizeof(float);   // [grad | loss | one scratch word of the two-level row reduction]
-  if (e == hipSuccess) e = hipMalloc(&c->theta, pb);
-  if (e == hipSuccess) e = hipMalloc(&c->grad, pb);
-  if (e == hipSuccess) e = hipMalloc(&c->m, pb);
-  if (e == hipSuccess) e = hipMalloc(&c->v, pb);
-  if (e == hipSuccess) e = hipMemset(c->m, 0, pb);
-  if (e == hipSuccess) e = hipMemset(c->v, 0, pb);
-  if (e == hipSuccess) e = hipMemset(c->grad, 0, pb);
-  const size_t pk_p = (size_t)(nm > 0 ? nm : 1) * c->NSTB * c->NSTB * 256 * sizeof(f32x4);
-  size_t pk_s = (size_t)(nh > 0 ? nh : 1) * (c->r + 1) * c->NB * c->NB * 256 * sizeof(f32x4);
-  {
-    const size_t pk16 = (size_t)(nh > 0 ? nh : 1) * (c->r + 1) * snet3_plane_floats(c->n) * sizeof(float);
-    if (pk16 > pk_s) pk_s = pk16;
-  }
-  if (e == hipSuccess) e = hipMalloc(&c->pWF, pk_p);
-  if (e == hipSuccess) e = hipMalloc(&c->pWB, pk_p);
-  if (e == hipSuccess) e = hipMalloc(&c->sWF, pk_s);
-  if (e == hipSuccess) e = hipMalloc(&c->sWB, pk_s);
-  if (nh > 0 && !(snet3_nbl(c->n) & 1) && c->n <= 128) {
-    const int rr = c->kind == NIF_KIND_LASTLAYER ? 0 : c->r;   // last-layer class: shared dense weights, one plane
-    if (e == hipSuccess) e = hipMalloc(&c->sWF4, (size_t)nh * snet4_fwd_elems(c->n, rr) * 2);
-    if (e == hipSuccess) e = hipMalloc(&c->sWB4, (size_t)nh * snet4_bwd_elems(c->n, rr) * 2);
-    if (c->kind != NIF_KIND_NIF) {   // SIREN nets (r5): the exact-product half planes of k_snet4<.., PR = 3> / k_snet6 (class NIF keeps the bf16 splits)
-      if (e == hipSuccess) e = hipMalloc(&c->sWF4x, (size_t)nh * snet4_bwd_elems(c->n, rr) * 2);
-      if (e == hipSuccess) e = hipMalloc(&c->sWB4x, (size_t)nh * snet4_bwd_elems(c->n, rr) * 2);
-      if (e == hipSuccess) e = hipMalloc(&c->sWscale, sizeof(float) * (size_t)nh * (rr + 1) * 2);
-    }
-    if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32) {     // the policy's compact plane set (k_snet4 / k_snet6<.., PR>), next to the exact splits
-      if (e == hipSuccess) e = hipMalloc(&c->sWF4h, (size_t)nh * (snet4_fwd_elems(c->n, rr) / 3) * 2);
-      if (e == hipSuccess) e = hipMalloc(&c->sWB4h, (size_t)nh * (snet4_bwd_elems(c->n, rr) / 2) * 2);
-    }
-    if (c->kind == NIF_KIND_LASTLAYER && e == hipSuccess) e = hipMalloc(&c->ll_wpf, (size_t)snet4_phi_fwd_elems(c->n) * 2);
-    if (c->kind == NIF_KIND_LASTLAYER && e == hipSuccess) e = hipMalloc(&c->ll_wpb, (size_t)snet4_phi_bwd_elems(c->n) * 2);
-  }
-  // slot-ordered copy of the dense ShapeNet parameters of the last-layer class (k_snet4<LL>, k_sob<LL>, k_jac on the r = 0 arguments)
-  if (c->kind == NIF_KIND_LASTLAYER && nh > 0 && c->n <= 128 && e == hipSuccess)
-    e = hipMalloc(&c->ll_slots, sizeof(float) * (size_t)((long)c->si * c->n + (long)nh * c->n * c->n + (long)c->n * c->so * c->r +
-                                                           c->n + (long)nh * c->n + c->so * c->r + c->so + c->r * c->r + 64));
-  const size_t pk_l = (size_t)(nh > 0 ? nh : 1) * c->NB * c->NB * 256 * sizeof(f32x4);
-  if (e == hipSuccess && c->kind == NIF_KIND_LASTLAYER) e = hipMalloc(&c->lWF, pk_l);
-  if (e == hipSuccess && c->kind == NIF_KIND_LASTLAYER) e = hipMalloc(&c->lWB, pk_l);
-  if (e != hipSuccess) {
-    std::string msg = std::string("nif_create: ") + hipGetErrorString(e);
-    delete c;
-    return fail(NIF_ERR_HIP, msg);
-  }
-  *out = c;
+  c->pstride = (c->P + 1 + 63) / 64 * 64;
+  if (create_buffers(c) != NIF_OK) return fail(NIF_ERR_HIP, "nif_create: " + g_err);
+  *out = own.release();
   return NIF_OK;
 }
 
+nif_ctx::~nif_ctx() {
+  (void)hipSetDevice(dev);
+  nif_f64_release(this);
+  if (comm) (void)nif_comm_destroy(this);
+  for (hipStream_t s : {st2, st_copy, st}) if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+  for (hipEvent_t e : {ev_copied[0], ev_copied[1], ev_consumed[0], ev_consumed[1], ev_start, ev_done, t0, t1}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+  for (const Rec& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+  for (hipGraphExec_t ex : graphs) if (ex) (void)hipGraphExecDestroy(ex);
+}
 extern "C" int nif_destroy(nif_ctx* c) {
   if (!c) return NIF_OK;
   hipSetDevice(c->dev);
   if (c->st) hipStreamSynchronize(c->st);
-  nif_f64_release(c);
-  if (c->small_idx) hipFree(c->small_idx);
-  if (c->small_desc) hipFree(c->small_desc);
-  if (c->comm) (void)nif_comm_destroy(c);
-  if (c->st2) { hipStreamSynchronize(c->st2); hipStreamDestroy(c->st2); }
-  if (c->st_copy) { hipStreamSynchronize(c->st_copy); hipStreamDestroy(c->st_copy); }
-  for (int s_ = 0; s_ < 2; ++s_) { if (c->ev_copied[s_]) hipEventDestroy(c->ev_copied[s_]); if (c->ev_consumed[s_]) hipEventDestroy(c->ev_consumed[s_]); }
-  if (c->ev_start) hipEventDestroy(c->ev_start);
-  if (c->ev_done) hipEventDestroy(c->ev_done);
-  for (hipEvent_t e : c->ev_chunk) hipEventDestroy(e);
-  for (hipGraphExec_t ex : c->graphs) if (ex) (void)hipGraphExecDestroy(ex);
-  if (c->opt_host) (void)hipHostFree(c->opt_host);
-  void* ptrs[] = {c->gt_blk, c->gt_part, c->gt_norms, c->gt_dev, c->opt_dev, c->vhat, c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel, c->sob_acc, c->sob2_acc, c->comm_scratch, c->chunk_grad, c->act_part, c->act_loss, c->jac_mu, c->jac_tmp, c->zt_par, c->dzt_par, c->dat_par, c->ztl_par, c->theta, c->grad, c->m, c->v, c->pWF, c->pWB, c->sWF, c->sWB, c->stash_s, c->stash_p, c->Z, c->DZ,
-                  c->DU, c->ZL, c->partial, c->loss_partial, c->dring, c->metric, c->tl, c->lWF, c->lWB, c->sWF4, c->sWB4, c->sWF4x, c->sWB4x, c->sWscale, c->sWF4h, c->sWB4h, c->ll_slots, c->ll_wpf, c->ll_wpb, c->stash_l, c->PHI, c->DPHI, c->DA, c->DZL, c->d_a, c->d_b, c->d_c, c->d_d};
-  for (void* p : ptrs) if (p) hipFree(p);
-  if (c->st) hipStreamDestroy(c->st);
   delete c;
   return NIF_OK;
 }
@@ -384,35 +379,28 @@ extern "C" void* nif_params_dev(nif_ctx* c) { return c ? (void*)c->theta : nullp
 // ------------------------------------------------------------------------------------------
 // internal orchestration
 // ------------------------------------------------------------------------------------------
-static int grow(float** p, long* cap, long need) {
-  if (need <= *cap) return NIF_OK;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  HIPCHK(hipMalloc(p, sizeof(float) * (size_t)need));
-  *cap = need;
-  return NIF_OK;
-}
-
-static int ensure_capacity(nif_ctx* c, long B, bool train) {
+// Partial gradient rows and loss partials of a training step over B points: all a k_small step needs of ensure_capacity.
+// One loss partial per workgroup of the fused kernel: the 16-point-tile kernels launch up to ceil(2*ntiles/4) workgroups (k_snet3/4,
+// k_sob), k_ll_out ntiles/8, k_snet ntiles/4 (r6: k_small one per 16 points = 2 ntiles)
+static int ensure_rows(nif_ctx* c, long B) {
   const long ntiles = (B + 31) / 32;
-  const long pts = ntiles * 32;
+  const int rc = c->loss_partial.reserve(c, 2 * ntiles + 1); if (rc) return rc;
+  return c->partial.reserve(c, 256 * c->pstride);
+}
+// Point workspaces for B points and, for a training step, the stashes and ensure_rows.  c->cap describes all of them: a failure on the
+// way leaves none and cap = 0, so the next call builds them again.
+static int ensure_capacity(nif_ctx* c, long B, bool train) {
+  const long pts = (B + 31) / 32 * 32;
   if (pts > c->cap || (train && !c->stash_s)) {
-    HIPCHK(hipStreamSynchronize(c->st));
     const long newcap = pts > c->cap ? pts : c->cap;
     const bool ll = c->kind == NIF_KIND_LASTLAYER;
-    float** ws[] = {&c->Z, &c->DZ, &c->DU, &c->ZL, &c->PHI, &c->DPHI, &c->DA, &c->DZL};
+    DevBuf<float>* ws[] = {&c->Z, &c->DZ, &c->DU, &c->ZL, &c->PHI, &c->DPHI, &c->DA, &c->DZL};
     const long wsz[] = {(long)c->r * newcap, (long)c->r * newcap, (long)c->so * newcap, (long)32 * c->RB * newcap,
                         (long)c->r * c->so * newcap, (long)c->r * c->so * newcap, (long)c->r * newcap, (long)c->r * newcap};
-    if (newcap > c->cap)
-      for (int i = 0; i < (ll ? 8 : 4); ++i) {
-        if (*ws[i]) HIPCHK(hipFree(*ws[i]));
-        *ws[i] = nullptr;
-        HIPCHK(hipMalloc(ws[i], sizeof(float) * (size_t)wsz[i]));
-      }
-    if (train) {
-      if (c->stash_s) HIPCHK(hipFree(c->stash_s));
-      if (c->stash_p) HIPCHK(hipFree(c->stash_p));
-      c->stash_s = c->stash_p = nullptr;
+    int rc = NIF_OK;
+    for (int i = 0; i < (ll ? 8 : 4) && !rc; ++i) rc = ws[i]->reserve(c, wsz[i]);
+    if (!rc && newcap > c->cap) { rc = c->stash_s.release(c); if (!rc) rc = c->stash_p.release(c); }      // (their slot strides follow cap)
+    if (!rc && train) {
       c->slot_s = (long)c->NB * 32 * newcap;
       c->slot_p = (long)c->NSTB * 32 * newcap;
       // r6 (fuzz case 606/16): k_snet6 keeps its private h ring in this buffer -- [workgroups][8 waves][nh][64 features][16 points],
@@ -422,35 +410,20 @@ static int ensure_capacity(nif_ctx* c, long B, bool train) {
       long s_floats = c->slot_s * 2 * (c->nh + 1);
       const long ring6 = snet6_ring_floats(newcap, c->nh);
       if (ring6 > s_floats) s_floats = ring6;
-      HIPCHK(hipMalloc(&c->stash_s, sizeof(float) * (size_t)s_floats));
-      HIPCHK(hipMalloc(&c->stash_p, sizeof(float) * (size_t)(c->slot_p * (2 * c->nm + 2))));
-      if (c->NB * 32 > ((c->n + 15) / 16) * 16)    // 65..96 (and 33..48) units: the rows the fused kernels never write must read as zero
-        HIPCHK(hipMemsetAsync(c->stash_s, 0, sizeof(float) * (size_t)s_floats, c->st));
-    } else if (newcap > c->cap && c->stash_s) {
-      HIPCHK(hipFree(c->stash_s)); HIPCHK(hipFree(c->stash_p));
-      c->stash_s = c->stash_p = nullptr;
+      rc = c->stash_s.reserve(c, s_floats);
+      if (!rc) rc = c->stash_p.reserve(c, c->slot_p * (2 * c->nm + 2));
+      if (!rc && c->NB * 32 > ((c->n + 15) / 16) * 16)    // 65..96 (and 33..48) units: the rows the fused kernels never write must read as zero
+        rc = hipMemsetAsync(c->stash_s, 0, sizeof(float) * (size_t)s_floats, c->st) == hipSuccess ? NIF_OK : fail(NIF_ERR_HIP, "hipMemsetAsync(stash_s)");
+    }
+    if (rc) {
+      for (DevBuf<float>* b : ws) b->drop();
+      c->stash_s.drop(); c->stash_p.drop();
+      c->cap = 0;
+      return rc;
     }
     c->cap = newcap;
   }
-  if (train) {
-    // one loss partial per workgroup of the fused kernel: the 16-point-tile kernels launch up to ceil(2*ntiles/4)
-    // workgroups (k_snet3/4, k_sob), k_ll_out ntiles/8, k_snet ntiles/4
-    // (r6: k_small one per 16 points = 2 ntiles)
-    const long nblk = 2 * ntiles + 1;
-    if (nblk > c->nloss_cap) {
-      HIPCHK(hipStreamSynchronize(c->st));
-      if (c->loss_partial) HIPCHK(hipFree(c->loss_partial));
-      c->loss_partial = nullptr;
-      HIPCHK(hipMalloc(&c->loss_partial, sizeof(float) * (size_t)nblk));
-      c->nloss_cap = nblk;
-    }
-    if (!c->partial) {
-      c->rows_cap = 256;
-      c->pstride = (c->P + 1 + 63) / 64 * 64;
-      HIPCHK(hipMalloc(&c->partial, sizeof(float) * (size_t)c->rows_cap * c->pstride));
-    }
-  }
-  return NIF_OK;
+  return train ? ensure_rows(c, B) : NIF_OK;
 }
 
 static MatRef dense_ref(long w_off, int nin, int nout) { MatRef m; m.r = 0; m.base_k = 0; m.kstride = 0; m.base_last = w_off; m.ld = nout; m.nin = nin; m.nout = nout; return m; }
@@ -458,6 +431,17 @@ static MatRef vec_ref(long b_off, int nout) { MatRef m; m.r = 0; m.base_k = 0; m
 static MatRef hyper_ref(const nif_ctx* c, long slot, int ld, int nin, int nout) {
   MatRef m; m.r = c->r; m.base_k = c->last_w + slot; m.kstride = c->po; m.base_last = c->last_b + slot; m.ld = ld; m.nin = nin; m.nout = nout; return m;
 }
+
+// matrix j of an MLP's hidden stack (pairs (w, w2) per layer with resblocks) -> offsets of its kernel and bias in theta
+static void mlp_mat(bool res, const long* w, const long* b, const long* w2, const long* b2, int j, long* w_off, long* b_off) {
+  const int i = res ? j / 2 : j;
+  const bool second = res && (j & 1);
+  *w_off = second ? w2[i] : w[i]; *b_off = second ? b2[i] : b[i];
+}
+static void pnet_mat(const nif_ctx* c, int j, long* w_off, long* b_off) { mlp_mat(c->cfg.p_resblock, c->hid_w, c->hid_b, c->hid_w2, c->hid_b2, j, w_off, b_off); }
+static void snet_mat(const nif_ctx* c, int j, long* w_off, long* b_off) { mlp_mat(c->cfg.s_resblock, c->s_hid_w, c->s_hid_b, c->s_hid_w2, c->s_hid_b2, j, w_off, b_off); }
+// the mixed policy's MFMA operand form: 0 exact bf16 splits (float32), 1 bf16 planes, 2 f16 planes
+static int policy_prec(const nif_ctx* c) { return c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? 1 : (c->cfg.mixed_policy == NIF_POLICY_MIXED_F16 ? 2 : 0); }
 
 static void fill_pnet(const nif_ctx* c, PNetArgs& a, const float* xin, long B) {
   memset(&a, 0, sizeof(a));
@@ -479,13 +463,9 @@ static void fill_pnet(const nif_ctx* c, PNetArgs& a, const float* xin, long B) {
 static void ensure_ll_mlp_planes(nif_ctx* c) {
   if (c->ll_mlp_packed) return;
   const long plane_l = (long)c->NB * c->NB * 256;
-  for (int i = 0; i < c->L; ++i) {
-    if (!c->cfg.s_resblock) {
-      launch_pack(c->theta, dense_ref(c->s_hid_w[i], c->n, c->n), c->NB, c->NB, c->lWF + i * plane_l, c->lWB + i * plane_l, c->st);
-    } else {
-      launch_pack(c->theta, dense_ref(c->s_hid_w[i], c->n, c->n), c->NB, c->NB, c->lWF + (2 * i) * plane_l, c->lWB + (2 * i) * plane_l, c->st);
-      launch_pack(c->theta, dense_ref(c->s_hid_w2[i], c->n, c->n), c->NB, c->NB, c->lWF + (2 * i + 1) * plane_l, c->lWB + (2 * i + 1) * plane_l, c->st);
-    }
+  for (int j = 0; j < c->nh; ++j) {
+    long w_off, b_off; snet_mat(c, j, &w_off, &b_off);
+    launch_pack(c->theta, dense_ref(w_off, c->n, c->n), c->NB, c->NB, c->lWF + j * plane_l, c->lWB + j * plane_l, c->st);
   }
   c->ll_mlp_packed = true;
 }
@@ -518,7 +498,7 @@ static void fill_snet_ll(const nif_ctx* c, SNetArgs& a, const float* xin, int nc
   a.DU = c->DU; a.DZ = nullptr; a.dring = c->dring;
   a.ll = 1; a.rl = c->r; a.so_u = c->so; a.DPHI = c->DPHI; a.DA_ll = c->DA; a.DZL = c->DZL;
   a.WPF = c->ll_wpf; a.WPB = c->ll_wpb;
-  a.prec = c->opt_fp32_mfma ? 0 : (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? 1 : (c->cfg.mixed_policy == NIF_POLICY_MIXED_F16 ? 2 : 0));     // (k_snet4<LL> only; k_sob / k_jac stay exact)
+  a.prec = c->opt_fp32_mfma ? 0 : policy_prec(c);     // (k_snet4<LL> only; k_sob / k_jac stay exact)
   a.WF4h = c->sWF4h; a.WB4h = c->sWB4h;
   a.WF4x = c->sWF4x; a.WB4x = c->sWB4x; a.wscale = c->sWscale;
   a.nsm = snet4_nsm_ll(c->si, sop, c->nh, c->n, c->so, c->r);
@@ -537,7 +517,7 @@ static void fill_snet(const nif_ctx* c, SNetArgs& a, const float* xin, int ncol,
   a.nsm = snet3_nsm(c->si, c->so, c->nh, c->n);
   a.WF4 = c->use_snet4 ? c->sWF4 : nullptr; a.WB4 = c->use_snet4 ? c->sWB4 : nullptr;   // packed only then
   a.WF4x = c->use_snet4 ? c->sWF4x : nullptr; a.WB4x = c->use_snet4 ? c->sWB4x : nullptr; a.wscale = c->sWscale;
-  a.prec = c->opt_fp32_mfma ? 0 : (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? 1 : (c->cfg.mixed_policy == NIF_POLICY_MIXED_F16 ? 2 : 0));
+  a.prec = c->opt_fp32_mfma ? 0 : policy_prec(c);
   if (!c->use_snet4) a.prec = a.prec == 2 ? 0 : a.prec;      // (no k_snet4 for this shape: the policy runs on the exact kernels)
   a.WF4h = c->use_snet4 ? c->sWF4h : nullptr; a.WB4h = c->use_snet4 ? c->sWB4h : nullptr;
   a.dring = c->dring;
@@ -569,13 +549,9 @@ static int ensure_packed_p32(nif_ctx* c) {
   if (c->packed_p32) return NIF_OK;
   ProfScope ps_(c, NIF_PROF_PACK);
   const long plane_p = (long)c->NSTB * c->NSTB * 256;
-  for (int i = 0; i < c->lst; ++i) {
-    if (!c->cfg.p_resblock) {
-      launch_pack(c->theta, dense_ref(c->hid_w[i], c->nst, c->nst), c->NSTB, c->NSTB, c->pWF + i * plane_p, c->pWB + i * plane_p, c->st);
-    } else {
-      launch_pack(c->theta, dense_ref(c->hid_w[i], c->nst, c->nst), c->NSTB, c->NSTB, c->pWF + (2 * i) * plane_p, c->pWB + (2 * i) * plane_p, c->st);
-      launch_pack(c->theta, dense_ref(c->hid_w2[i], c->nst, c->nst), c->NSTB, c->NSTB, c->pWF + (2 * i + 1) * plane_p, c->pWB + (2 * i + 1) * plane_p, c->st);
-    }
+  for (int j = 0; j < c->nm; ++j) {
+    long w_off, b_off; pnet_mat(c, j, &w_off, &b_off);
+    launch_pack(c->theta, dense_ref(w_off, c->nst, c->nst), c->NSTB, c->NSTB, c->pWF + j * plane_p, c->pWB + j * plane_p, c->st);
   }
   HIPCHK(hipGetLastError());
   c->packed_p32 = true;
@@ -604,9 +580,7 @@ static int ensure_packed(nif_ctx* c) {
       seg(c->s_bott_w, s_wl, (long)n * sop);
       seg(c->s_first_b, s_b1, n);
       for (int j = 0; j < nh; ++j) {
-        long w_off, b_off;
-        if (!c->cfg.s_resblock) { w_off = c->s_hid_w[j]; b_off = c->s_hid_b[j]; }
-        else { const int i = j / 2; w_off = (j & 1) ? c->s_hid_w2[i] : c->s_hid_w[i]; b_off = (j & 1) ? c->s_hid_b2[i] : c->s_hid_b[i]; }
+        long w_off, b_off; snet_mat(c, j, &w_off, &b_off);
         seg(b_off, s_bh + (long)j * n, n);
         if (c->use_ll4 && c->sWF4x)       // (r5: split groups + half planes + their scales in one launch)
           launch_pack16b_dual(c->theta, dense_ref(w_off, n, n), 0, 1, snet3_nbl(n),
@@ -620,7 +594,7 @@ static int ensure_packed(nif_ctx* c) {
         if (c->use_ll4 && c->sWF4h)
           launch_pack16b(c->theta, dense_ref(w_off, n, n), snet3_nbl(n),
                          (char*)c->sWF4h + (size_t)j * (snet4_fwd_elems(n, 0) / 3) * 2, (char*)c->sWB4h + (size_t)j * (snet4_bwd_elems(n, 0) / 2) * 2,
-                         c->cfg.s_omega0, c->st, c->cfg.mixed_policy == NIF_POLICY_MIXED_F16 ? 2 : 1);
+                         c->cfg.s_omega0, c->st, policy_prec(c));
       }
       seg(c->s_bott_b, s_bl, sop);
       seg(c->ll_bias, s_bl + sop, c->so);
@@ -651,7 +625,7 @@ static int ensure_packed(nif_ctx* c) {
   if (c->use_snet4 && c->nh > 0 && c->sWF4h)
     launch_pack16b_batch(c->theta, hyper_ref(c, (long)c->si * c->n, c->n, c->n, c->n), (long)c->n * c->n, c->nh, snet3_nbl(c->n),
                          c->sWF4h, c->sWB4h, snet4_fwd_elems(c->n, c->r) / 3, snet4_bwd_elems(c->n, c->r) / 2, probe.omega, c->st,
-                         c->cfg.mixed_policy == NIF_POLICY_MIXED_F16 ? 2 : 1);
+                         policy_prec(c));
   HIPCHK(hipGetLastError());
   c->packed = true;
   if (!c->use_snet4) return ensure_packed32(c);
@@ -694,9 +668,9 @@ extern "C" int nif_forward_dev(nif_ctx* c, const float* xin, int64_t B, float* u
   return NIF_OK;
 }
 
-static int stage(nif_ctx* c, float** buf, long* cap, const float* host, long n) {
-  int rc = grow(buf, cap, n); if (rc) return rc;
-  if (host) HIPCHK(hipMemcpyAsync(*buf, host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->st));
+static int stage(nif_ctx* c, DevBuf<float>& buf, const float* host, long n) {
+  int rc = buf.reserve(c, n); if (rc) return rc;
+  if (host) HIPCHK(hipMemcpyAsync(buf, host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->st));
   return NIF_OK;
 }
 
@@ -705,8 +679,8 @@ extern "C" int nif_forward(nif_ctx* c, const float* xin, int64_t B, float* u) {
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));
-  int rc = stage(c, &c->d_a, &c->cap_a, xin, B * (c->pi + c->si)); if (rc) return rc;
-  rc = stage(c, &c->d_d, &c->cap_d, nullptr, B * c->so); if (rc) return rc;
+  int rc = stage(c, c->d_a, xin, B * (c->pi + c->si)); if (rc) return rc;
+  rc = stage(c, c->d_d, nullptr, B * c->so); if (rc) return rc;
   rc = nif_forward_dev(c, c->d_a, B, c->d_d); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(u, c->d_d, sizeof(float) * (size_t)(B * c->so), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -732,12 +706,12 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
   rc = ensure_capacity(c, B, false); if (rc) return rc;
   const long ntiles = (B + 31) / 32;
   const int ncol = c->pi + c->si;
-  rc = stage(c, &c->d_a, &c->cap_a, xin, B * ncol); if (rc) return rc;
-  rc = stage(c, &c->d_d, &c->cap_d, nullptr, B * c->so); if (rc) return rc;
-  rc = stage(c, &c->d_b, &c->cap_b, nullptr, B * c->so * nx); if (rc) return rc;
+  rc = stage(c, c->d_a, xin, B * ncol); if (rc) return rc;
+  rc = stage(c, c->d_d, nullptr, B * c->so); if (rc) return rc;
+  rc = stage(c, c->d_b, nullptr, B * c->so * nx); if (rc) return rc;
   // tangent buffers: dz/dp for up to 3 parameter seeds (and d phi / dx for the last-layer class)
   const long zd_sz = ntiles * 32 * (long)c->r * (ll ? c->so : 1);
-  rc = grow(&c->d_c, &c->cap_c, 3 * zd_sz); if (rc) return rc;
+  rc = c->d_c.reserve(c, 3 * zd_sz); if (rc) return rc;
   PNetArgs pa; fill_pnet(c, pa, c->d_a, B);
   if (ll) {
     // u = Dot(phi(x), a(p)) + bias: coordinate columns move phi, parameter columns move a
@@ -813,9 +787,8 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
     if (!pjac_supported(pa))
       return fail(NIF_ERR_INVALID, "HessianLayer on parameter columns: ParameterNets of up to 128 units");
     const long need_zt = (long)c->pi * blk, need_dd = (long)np_ * np_ * blk;
-    if (need_zt > c->zt_par_cap || need_dd > c->dzt_par_cap) HIPCHK(hipStreamSynchronize(c->st));
-    if (need_zt > c->zt_par_cap) { rc = grow(&c->zt_par, &c->zt_par_cap, need_zt); if (rc) return rc; }
-    if (need_dd > c->dzt_par_cap) { rc = grow(&c->dzt_par, &c->dzt_par_cap, need_dd); if (rc) return rc; }
+    rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
+    rc = c->dzt_par.reserve(c, need_dd); if (rc) return rc;
     launch_pjac_fwd(pa, c->zt_par, c->st);
   }
   auto zt_of = [&](int col) -> const float* { return c->zt_par + (long)col * blk; };
@@ -825,9 +798,9 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
     // the r = 0 case of the same kernel with so * latent_dim outputs), the parameters only move a = latent last_w + last_b
     const int rl = c->r, sop = c->so * c->r;
     const int nxc = xc.empty() ? 1 : (int)xc.size();
-    rc = stage(c, &c->d_d, &c->cap_d, nullptr, B * sop); if (rc) return rc;
-    rc = stage(c, &c->d_b, &c->cap_b, nullptr, B * sop * nxc); if (rc) return rc;
-    rc = stage(c, &c->d_c, &c->cap_c, nullptr, B * sop * nxc * nxc); if (rc) return rc;
+    rc = stage(c, c->d_d, nullptr, B * sop); if (rc) return rc;
+    rc = stage(c, c->d_b, nullptr, B * sop * nxc); if (rc) return rc;
+    rc = stage(c, c->d_c, nullptr, B * sop * nxc * nxc); if (rc) return rc;
     SNetArgs sa; rc = fill_snet_ll_sob(c, sa, xin_dev, B, true); if (rc) return rc;
     if (xc.empty()) { sa.u_out = c->d_d; launch_hess(sa, 0, 0, 0, 0, 1, c->d_b, c->d_c, c->st); }     // phi alone
     for (size_t j = 0; j < xc.size(); ++j)
@@ -840,11 +813,11 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
     float* ap = nullptr;
     if (nvec > 0) {
       const long need = (long)nvec * blk + 64;        // + the source offsets (as raw bytes behind the vectors)
-      if (need > c->jac_mu_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->jac_mu, &c->jac_mu_cap, need); if (rc) return rc; }
+      rc = c->jac_mu.reserve(c, need); if (rc) return rc;
       ap = c->jac_mu;
       for (int j = 0; j < np_; ++j)
         for (int k = j; k < np_; ++k) launch_pjac2(pa, x_idx[xp[j]], x_idx[xp[k]], zdd_of(j, k), c->st);
-      // source of vector v: z'_j inside zt_par, z''_jk inside dzt_par -- addressed relative to zt_par (both are hipMalloc'ed floats)
+      // source of vector v: z'_j inside zt_par, z''_jk inside dzt_par -- addressed relative to zt_par (both are device arrays of floats)
       std::vector<long> off(nvec, 0);
       for (int j = 0; j < np_; ++j) off[j] = (long)(zt_of(x_idx[xp[j]]) - c->zt_par);
       for (int j = 0; j < np_; ++j)
@@ -867,8 +840,8 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
   }
   rc = ensure_packed32(c); if (rc) return rc;
   if (!c->jac_ok) return fail(NIF_ERR_INVALID, "HessianLayer: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
-  rc = stage(c, &c->d_b, &c->cap_b, nullptr, B * c->so * nx); if (rc) return rc;
-  rc = stage(c, &c->d_c, &c->cap_c, nullptr, B * c->so * nx * nx); if (rc) return rc;
+  rc = stage(c, c->d_b, nullptr, B * c->so * nx); if (rc) return rc;
+  rc = stage(c, c->d_c, nullptr, B * c->so * nx * nx); if (rc) return rc;
   SNetArgs sa; fill_snet(c, sa, xin_dev, ncol, c->pi, B);
   std::vector<int> ppos(nx, -1);                    // position among the parameter columns of x_idx
   for (int j = 0; j < np_; ++j) ppos[xp[j]] = j;
@@ -910,10 +883,10 @@ extern "C" int nif_hessian(nif_ctx* c, const float* xin, int64_t B, const int32_
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));
-  rc = stage(c, &c->d_a, &c->cap_a, xin, B * (c->pi + c->si)); if (rc) return rc;
+  rc = stage(c, c->d_a, xin, B * (c->pi + c->si)); if (rc) return rc;
   const size_t n_y = (size_t)B * c->so, n_d = (size_t)B * ny * nx, n_h = n_d * nx;
-  float* out = nullptr;
-  HIPCHK(hipMalloc(&out, sizeof(float) * (n_y + n_d + n_h)));
+  DevBuf<float> out;      // this call's own device copy of the three outputs
+  rc = out.alloc((long)(n_y + n_d + n_h)); if (rc) return rc;
   rc = hessian_core(c, c->d_a, B, y_idx, ny, x_idx, nx, out, out + n_y, out + n_y + n_d);
   if (rc == NIF_OK) {
     hipError_t e = hipMemcpyAsync(y_out, out, sizeof(float) * n_y, hipMemcpyDeviceToHost, c->st);
@@ -922,7 +895,6 @@ extern "C" int nif_hessian(nif_ctx* c, const float* xin, int64_t B, const int32_
     if (e == hipSuccess) e = hipStreamSynchronize(c->st);
     if (e != hipSuccess) rc = fail(NIF_ERR_HIP, hipGetErrorString(e));
   } else (void)hipStreamSynchronize(c->st);
-  (void)hipFree(out);
   return rc;
 }
 
@@ -933,8 +905,8 @@ extern "C" int nif_pnet_latent(nif_ctx* c, const float* p, int64_t B, float* lr)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_capacity(c, B, false); if (rc) return rc;
-  rc = stage(c, &c->d_a, &c->cap_a, p, B * c->pi); if (rc) return rc;
-  rc = stage(c, &c->d_d, &c->cap_d, nullptr, B * c->r); if (rc) return rc;
+  rc = stage(c, c->d_a, p, B * c->pi); if (rc) return rc;
+  rc = stage(c, c->d_d, nullptr, B * c->r); if (rc) return rc;
   PNetArgs pa; fill_pnet(c, pa, c->d_a, B);
   pa.ncol = c->pi;
   launch_pnet(pa, c->NSTB, false, c->st);
@@ -953,8 +925,8 @@ extern "C" int nif_x_to_phi(nif_ctx* c, const float* x, int64_t B, float* phi) {
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_capacity(c, B, false); if (rc) return rc;
-  rc = stage(c, &c->d_a, &c->cap_a, x, B * c->si); if (rc) return rc;
-  rc = stage(c, &c->d_d, &c->cap_d, nullptr, B * c->so * c->r); if (rc) return rc;
+  rc = stage(c, c->d_a, x, B * c->si); if (rc) return rc;
+  rc = stage(c, c->d_d, nullptr, B * c->so * c->r); if (rc) return rc;
   ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, c->d_a, c->si, 0, B);
   launch_pnet(ma, c->NB, false, c->st);
   launch_tiles_to_rows(c->PHI, B, c->so * c->r, c->d_d, c->st);
@@ -980,8 +952,8 @@ extern "C" int nif_latent_to_w(nif_ctx* c, const float* lr, int64_t B, float* w)
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));
-  int rc = stage(c, &c->d_a, &c->cap_a, lr, B * c->r); if (rc) return rc;
-  rc = stage(c, &c->d_b, &c->cap_b, nullptr, B * c->po); if (rc) return rc;
+  int rc = stage(c, c->d_a, lr, B * c->r); if (rc) return rc;
+  rc = stage(c, c->d_b, nullptr, B * c->po); if (rc) return rc;
   rc = nif_latent_to_w_dev(c, c->d_a, B, c->d_b); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(w, c->d_b, sizeof(float) * (size_t)(B * c->po), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -1015,9 +987,9 @@ extern "C" int nif_shapenet_given_w(nif_ctx* c, const float* x, const float* w, 
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));
-  int rc = stage(c, &c->d_a, &c->cap_a, x, B * c->si); if (rc) return rc;
-  rc = stage(c, &c->d_b, &c->cap_b, w, B * c->po); if (rc) return rc;   // po == r for the last-layer class
-  rc = stage(c, &c->d_d, &c->cap_d, nullptr, B * c->so); if (rc) return rc;
+  int rc = stage(c, c->d_a, x, B * c->si); if (rc) return rc;
+  rc = stage(c, c->d_b, w, B * c->po); if (rc) return rc;   // po == r for the last-layer class
+  rc = stage(c, c->d_d, nullptr, B * c->so); if (rc) return rc;
   rc = nif_shapenet_given_w_dev(c, c->d_a, c->d_b, B, c->d_d); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(u, c->d_d, sizeof(float) * (size_t)(B * c->so), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -1037,9 +1009,7 @@ static int fill_snet_ll_sob(nif_ctx* c, SNetArgs& sa, const float* xin, long B, 
     const long plane_s = snet3_plane_floats(c->n) / 4;
     if (!c->ll_packed32) {
       for (int j = 0; j < c->nh; ++j) {
-        long w_off;
-        if (!c->cfg.s_resblock) w_off = c->s_hid_w[j];
-        else { const int i = j / 2; w_off = (j & 1) ? c->s_hid_w2[i] : c->s_hid_w[i]; }
+        long w_off, b_off; snet_mat(c, j, &w_off, &b_off);
         launch_pack16(c->theta, dense_ref(w_off, c->n, c->n), NBL, c->sWF + (long)j * plane_s, c->sWB + (long)j * plane_s, c->st);
       }
       c->ll_packed32 = true;
@@ -1074,17 +1044,16 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     nloss = launch_sob(sa, true, nsc, sp->seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spq);
     if (nloss < 0) return fail(NIF_ERR_INVALID, "Sobolev step: the kernel's working set of this shape does not fit the 160 KB LDS of a CU");
     const long need = (long)nloss * 4 * sob_ring_floats_per_wave(c->n, c->nh);
-    if (need > c->dring_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->dring, &c->dring_cap, need); if (rc) return rc; }
+    rc = c->dring.reserve(c, need); if (rc) return rc;
     SobPar spar{};
     for (int d = 0; d < 3; ++d) { spar.par[d] = -1; spar.gcol[d] = sp->gcol[d]; }
     spar.gstride = sp->gstride; spar.nx_all = sp->nx_all; spar.ny = sp->ny; spar.no_primal = sp->no_primal; spar.ymask = sp->ymask;
     spar.hess = sp->hess;
     if (nhead > 0) {     // parameter columns: heads of the epilogue (z' = dz/dp sits in c->zt_par, loss_grad_core)
       const long need_a = 3 * ntiles * 32 * c->r, need_l = 3 * ntiles * 32 * 32 * c->RB;
-      if (need_a > c->dat_par_cap || need_l > c->ztl_par_cap) HIPCHK(hipStreamSynchronize(c->st));
-      if (need_a > c->dat_par_cap) { rc = grow(&c->dat_par, &c->dat_par_cap, need_a); if (rc) return rc; }
-      if (need_l > c->ztl_par_cap) {
-        rc = grow(&c->ztl_par, &c->ztl_par_cap, need_l); if (rc) return rc;
+      rc = c->dat_par.reserve(c, need_a); if (rc) return rc;
+      if (need_l > c->ztl_par.n) {
+        rc = c->ztl_par.reserve(c, need_l); if (rc) return rc;
         HIPCHK(hipMemsetAsync(c->ztl_par, 0, sizeof(float) * (size_t)need_l, c->st));     // the padding rows stay zero
       }
       spar.npar = nhead; spar.ZT = c->zt_par; spar.DZT = c->dzt_par; spar.DAT = c->dat_par; spar.ZTL = c->ztl_par;
@@ -1108,10 +1077,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     }
     nloss = launch_snet4(sa, true, true, c->st);
     const long need = (long)nloss * 4 * snet3_ring_floats_per_wave(c->n, c->nh);
-    if (need > c->dring_cap) {
-      HIPCHK(hipStreamSynchronize(c->st));
-      int rc = grow(&c->dring, &c->dring_cap, need); if (rc) return rc;
-    }
+    int rc = c->dring.reserve(c, need); if (rc) return rc;
     sa.dring = c->dring;
     ProfScope p_(c, NIF_PROF_SNET);
     if (launch_snet4(sa, true, false, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no k_snet4 form for this net (SIREN planes not packed as half pairs)");
@@ -1124,12 +1090,12 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   int n_act = 0;
   if (act_on(c)) {    // + c/Bg phi'(a) into dL/da and dL/dlatent, before their consumers; the loss term joins after the row reduction
     const long nlp = (B + 255) / 256;
-    if (nlp > c->act_loss_cap) { HIPCHK(hipStreamSynchronize(c->st)); int rc = grow(&c->act_loss, &c->act_loss_cap, nlp); if (rc) return rc; }
+    int rc = c->act_loss.reserve(c, nlp); if (rc) return rc;
     const bool l1 = c->act_l2 == 0.f;
     n_act = launch_ll_actreg(c->Z, c->theta + c->last_w, c->r, B, (l1 ? c->act_l1 : c->act_l2) / (float)Bg, l1, c->DA, c->DZL, c->act_loss, c->st);
   }
   int rows = (int)((ntiles + 3) / 4);
-  if (rows > c->rows_cap) rows = c->rows_cap;
+  if (rows > c->rows_cap()) rows = c->rows_cap();
   if (rows < 1) rows = 1;
   { ProfScope p_(c, NIF_PROF_PNET_BWD);
     if (fused_p) launch_pnet_bwg(pa, c->partial, c->pstride, rows, c->st);
@@ -1157,9 +1123,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     launch_gw_first(g, c->NB, rows, c->st);
     for (int mi = 0; mi < nms; ++mi) {
       sbase(g); g.IN = sST + (long)mi * c->slot_s; g.DA = sST + (long)(nms + 2 + mi) * c->slot_s; g.scale = ma.omega;
-      long w_off, b_off;
-      if (!c->cfg.s_resblock) { w_off = c->s_hid_w[mi]; b_off = c->s_hid_b[mi]; }
-      else { const int i = mi / 2; w_off = (mi & 1) ? c->s_hid_w2[i] : c->s_hid_w[i]; b_off = (mi & 1) ? c->s_hid_b2[i] : c->s_hid_b[i]; }
+      long w_off, b_off; snet_mat(c, mi, &w_off, &b_off);
       g.W = dense_ref(w_off, c->n, c->n); g.Bv = vec_ref(b_off, c->n);
       g.da_bf16 = ll_dab ? 1 : 0;
       g.in_ph16 = ll_ph ? 1 : 0;
@@ -1179,9 +1143,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     launch_gw_first(g, c->NSTB, rows, c->st);
     for (int mi = 0; mi < c->nm; ++mi) {
       base(g); g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.scale = pa.omega;
-      long w_off, b_off;
-      if (!c->cfg.p_resblock) { w_off = c->hid_w[mi]; b_off = c->hid_b[mi]; }
-      else { const int i = mi / 2; w_off = (mi & 1) ? c->hid_w2[i] : c->hid_w[i]; b_off = (mi & 1) ? c->hid_b2[i] : c->hid_b[i]; }
+      long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
       g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
       launch_gw_mfma(g, c->NSTB, c->NSTB, rows, c->st);
     }
@@ -1202,7 +1164,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   if (nhead > 0) {
     // the heads' share of the r x r layer: dL/dlast_w += z'^T dL/da' (a' = z' last_w has no bias), the same reduction as the
     // main one with (z', dL/da') as the operand pair; then the (primal, tangent) ParameterNet for dL/dz' (jac_reg_pass, given mu)
-    if (!c->jac_tmp) HIPCHK(hipMalloc(&c->jac_tmp, sizeof(float) * (size_t)(c->P + 2)));
+    if (!c->jac_tmp) { const int rca = c->jac_tmp.alloc(c->P + 2); if (rca) return rca; }
     int mu_blk[16];
   for (int q = 0; q < 16; ++q) mu_blk[q] = -1;
     const long rr = (long)c->r * c->r;
@@ -1224,7 +1186,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
 }
 
 // Workspace sizing of the fused ShapeNet kernel the step will launch (no launch): number of workgroups (= loss partials),
-// the act'(a) ring, the optional edge-gradient partials.  Grows buffers when needed (stream sync + hipMalloc): call
+// the act'(a) ring, the optional edge-gradient partials.  Grows buffers when needed (stream sync + device allocation): call
 // nif_reserve() once up front to keep that out of the timed steps.
 static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nloss, const int* par_of = nullptr, bool hess = false) {
   int rc;
@@ -1236,19 +1198,13 @@ static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nl
     if (nblk < 0)
       return fail(NIF_ERR_INVALID, "Sobolev step: the kernel's working set of this shape (units, latent_dim, parameter columns) does not fit the 160 KB LDS of a CU");
     const long need = (long)nblk * 4 * sob_ring_floats_per_wave(c->n, c->nh);
-    if (need > c->dring_cap) {
-      HIPCHK(hipStreamSynchronize(c->st));
-      rc = grow(&c->dring, &c->dring_cap, need); if (rc) return rc;
-    }
+    rc = c->dring.reserve(c, need); if (rc) return rc;
     *nloss = nblk;
   } else if (c->use_snet3 || c->use_snet4) {
     int waves = 4;
     const int nblk = c->use_snet4 ? launch_snet4(sa, true, true, c->st) : launch_snet3(sa, true, true, &waves, c->st);
     const long need = (long)nblk * waves * snet3_ring_floats_per_wave(c->n, c->nh);
-    if (need > c->dring_cap) {
-      HIPCHK(hipStreamSynchronize(c->st));
-      rc = grow(&c->dring, &c->dring_cap, need); if (rc) return rc;
-    }
+    rc = c->dring.reserve(c, need); if (rc) return rc;
     *nloss = nblk;
   }
   sa.dring = c->dring;
@@ -1257,7 +1213,7 @@ static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nl
 
 static int rows_for(const nif_ctx* c, long ntiles) {
   int rows = (int)((ntiles + 3) / 4);
-  if (rows > c->rows_cap) rows = c->rows_cap;
+  if (rows > c->rows_cap()) rows = c->rows_cap();
   return rows < 1 ? 1 : rows;
 }
 
@@ -1282,14 +1238,7 @@ static int ensure_pipe(nif_ctx* c, int nchunk) {
     HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     c->ev_chunk.push_back(e);
   }
-  if (nchunk > c->chunk_cap) {
-    HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipStreamSynchronize(c->st2));
-    if (c->chunk_grad) HIPCHK(hipFree(c->chunk_grad));
-    c->chunk_grad = nullptr; c->chunk_cap = 0;
-    HIPCHK(hipMalloc(&c->chunk_grad, sizeof(float) * (size_t)nchunk * c->pstride));
-    c->chunk_cap = nchunk;
-  }
-  return NIF_OK;
+  return c->chunk_grad.reserve(c, (long)nchunk * c->pstride);
 }
 
 // Forward + adjoint + weight-gradient partial rows of the points [off, off + Bc) of a batch (NIF / NIFMultiScale).
@@ -1368,7 +1317,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   }
   if (act_on(c)) {   // + c/Bg sum phi'(out) M^(k) into dL/dz, before the ParameterNet adjoint consumes it; its loss partials
     const long nlp = (B + 255) / 256;
-    if (nlp > c->act_loss_cap) { HIPCHK(hipStreamSynchronize(sa_st)); rc = grow(&c->act_loss, &c->act_loss_cap, nlp); if (rc) return rc; }
+    rc = c->act_loss.reserve(c, nlp); if (rc) return rc;
     const bool l1 = c->act_l2 == 0.f;
     launch_actreg_points(l1, c->theta, c->last_w, c->last_b, c->r, c->po, sa.Z, B, (l1 ? c->act_l1 : c->act_l2) / (float)Bg, sa.DZ,
                          c->act_loss, sa_st);
@@ -1437,9 +1386,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   launch_gw_first(g, c->NSTB, rows, pb_st);
   for (int mi = 0; mi < c->nm; ++mi) {
     base(g); g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.r = 0; g.scale = om_p;
-    long w_off, b_off;
-    if (!c->cfg.p_resblock) { w_off = c->hid_w[mi]; b_off = c->hid_b[mi]; }
-    else { const int i = mi / 2; w_off = (mi & 1) ? c->hid_w2[i] : c->hid_w[i]; b_off = (mi & 1) ? c->hid_b2[i] : c->hid_b[i]; }
+    long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
     g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
     launch_gw_mfma(g, c->NSTB, c->NSTB, rows, pb_st);
   }
@@ -1459,17 +1406,12 @@ static int ensure_small_tables(nif_ctx* c, const PNetArgs& pa, const SNetArgs& s
   std::vector<int> idx, desc;
   small_tables(pa, sa, idx, desc);
   // the context takes the tables only when both exist and are filled: a failure on the way leaves it without any (the next call tries again)
-  int *d_idx = nullptr, *d_desc = nullptr;
-  hipError_t e = hipMalloc(&d_idx, idx.size() * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&d_desc, desc.size() * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_desc, desc.data(), desc.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (d_idx) (void)hipFree(d_idx);
-    if (d_desc) (void)hipFree(d_desc);
-    HIPCHK(e);
-  }
-  c->small_idx = d_idx; c->small_desc = d_desc;
+  DevBuf<int> d_idx, d_desc;
+  int rc = d_idx.alloc((long)idx.size()); if (rc) return rc;
+  rc = d_desc.alloc((long)desc.size()); if (rc) return rc;
+  HIPCHK(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_desc, desc.data(), desc.size() * sizeof(int), hipMemcpyHostToDevice));
+  c->small_idx = std::move(d_idx); c->small_desc = std::move(d_desc);
   return NIF_OK;
 }
 // r6: the row reduction of a plain step waits for its consumer when nothing else needs [grad | loss] first: the optimizer step runs it fused
@@ -1513,10 +1455,10 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
     PNetArgs pa; fill_pnet(c, pa, xin, B);
     SNetArgs sa; fill_snet(c, sa, xin, c->pi + c->si, c->pi, B);
     if (small_supported(pa, sa) && small_rows(B) <= 256) {
-      int rc = ensure_capacity(c, ((B + 31) / 32) * 32, true); if (rc) return rc;      // (first call: allocates the partial rows, rows_cap = 256)
+      int rc = ensure_rows(c, B); if (rc) return rc;      // (no point workspaces, no stashes: k_small keeps everything on chip)
       const int rows = small_rows(B);
-      if (rows > c->rows_cap) return fail(NIF_ERR_STATE, "internal: partial-row buffer too small for the small-batch step");
-      if (rows > c->nloss_cap) return fail(NIF_ERR_STATE, "internal: loss partial buffer too small for the small-batch step");
+      if (rows > c->rows_cap()) return fail(NIF_ERR_STATE, "internal: partial-row buffer too small for the small-batch step");
+      if (rows > c->loss_partial.n) return fail(NIF_ERR_STATE, "internal: loss partial buffer too small for the small-batch step");
       c->reg_applied = false;
       sa.y = y; sa.sw = sw; sa.loss_partial = c->loss_partial; sa.inv_bg = 1.0f / (float)Bg;
       rc = ensure_small_tables(c, pa, sa); if (rc) return rc;
@@ -1548,9 +1490,8 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
     if (!pjac_supported(pa))
       return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
     const long need_zt = (long)c->pi * ntiles * 32 * c->r, need_dzt = 3 * ntiles * 32 * c->r;
-    if (need_zt > c->zt_par_cap || need_dzt > c->dzt_par_cap) HIPCHK(hipStreamSynchronize(c->st));
-    if (need_zt > c->zt_par_cap) { rc = grow(&c->zt_par, &c->zt_par_cap, need_zt); if (rc) return rc; }
-    if (need_dzt > c->dzt_par_cap) { rc = grow(&c->dzt_par, &c->dzt_par_cap, need_dzt); if (rc) return rc; }
+    rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
+    rc = c->dzt_par.reserve(c, need_dzt); if (rc) return rc;
     launch_pjac_fwd(pa, c->zt_par, c->st);
   }
   c->reg_applied = false;
@@ -1582,7 +1523,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
     launch_reduce(c->partial, c->pstride, rows, c->loss_partial, nloss, c->grad, c->P, c->st);
     if (act_on(c)) {   // the plane side of the activity regulariser and its loss, on top of the reduced gradient
       const long need = (long)NIF_ACT_SLABS * (c->r + 1) * c->po;
-      if (need > c->act_part_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->act_part, &c->act_part_cap, need); if (rc) return rc; }
+      rc = c->act_part.reserve(c, need); if (rc) return rc;
       const bool l1 = c->act_l2 == 0.f;
       launch_actreg_planes(l1, c->theta, c->last_w, c->last_b, c->r, c->po, c->Z, B, NIF_ACT_SLABS, c->act_part, c->st);
       launch_actreg_apply(c->act_part, NIF_ACT_SLABS, c->r, c->po, (l1 ? c->act_l1 : c->act_l2) / (float)Bg, c->last_w, c->last_b,
@@ -1597,7 +1538,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
   rc = ensure_pipe(c, nchunk); if (rc) return rc;
   HIPCHK(hipEventRecord(c->ev_start, c->st));             // stream B starts behind whatever st has queued (packing, Adam)
   HIPCHK(hipStreamWaitEvent(c->st2, c->ev_start, 0));
-  const long lp_stride = c->nloss_cap / nchunk;            // loss partials of chunk i at i * lp_stride
+  const long lp_stride = c->loss_partial.n / nchunk;            // loss partials of chunk i at i * lp_stride
   for (int i = 0; i < nchunk; ++i) {
     const long off = (long)i * chunk;
     const long Bc = B - off < chunk ? B - off : chunk;
@@ -1627,7 +1568,7 @@ extern "C" int nif_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, c
 }
 
 // Size every workspace of a training step over up to B_max points (n_tangents Sobolev seeds, 0 = plain step) now, so
-// that no hipMalloc / stream synchronisation happens inside a later (timed) step.
+// that no device allocation / stream synchronisation happens inside a later (timed) step.
 extern "C" int nif_reserve(nif_ctx* c, int64_t B_max, int32_t n_tangents) {
   if (!c || B_max <= 0 || n_tangents < 0 || n_tangents > 16) return fail(NIF_ERR_INVALID, "bad argument");
   if (n_tangents > 3) n_tangents = 3;      // (more x_index columns run as passes over groups of three)
@@ -1641,7 +1582,7 @@ extern "C" int nif_reserve(nif_ctx* c, int64_t B_max, int32_t n_tangents) {
       SNetArgs sa; fill_snet_ll(c, sa, nullptr, c->pi + c->si, c->pi, B_max);
       const int nblk = launch_snet4(sa, true, true, c->st);
       const long need = (long)nblk * 4 * snet3_ring_floats_per_wave(c->n, c->nh);
-      if (need > c->dring_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->dring, &c->dring_cap, need); if (rc) return rc; }
+      rc = c->dring.reserve(c, need); if (rc) return rc;
     }
     return NIF_OK;
   }
@@ -1728,7 +1669,7 @@ extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const f
   TAIL_FLUSH(c)
   const int gs = sob_cols_per_pass(c, x_idx, nx);
   const int ngroups = (nx + gs - 1) / gs;
-  if (ngroups > 1 && !c->sob_acc) HIPCHK(hipMalloc(&c->sob_acc, sizeof(float) * (size_t)(c->P + 1)));
+  if (ngroups > 1 && !c->sob_acc) { rc = c->sob_acc.alloc(c->P + 1); if (rc) return rc; }
   const float jac_l1 = c->jac_l1, act_l1 = c->act_l1, act_l2 = c->act_l2;
   for (int k = 0; k < ngroups; ++k) {
     const int g0 = gs * k, ng = nx - g0 < gs ? nx - g0 : gs;
@@ -1776,7 +1717,7 @@ extern "C" int nif_sobolev2_loss_grad_dev(nif_ctx* c, const float* xin, const fl
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   rc = nif_sobolev_loss_grad_dev_y(c, xin, y, dydx, sw, B, Bg, x_idx, nx, y_idx, ny, w_jac); if (rc) return rc;
-  if (!c->sob2_acc) HIPCHK(hipMalloc(&c->sob2_acc, sizeof(float) * (size_t)(c->P + 1)));
+  if (!c->sob2_acc) { rc = c->sob2_acc.alloc(c->P + 1); if (rc) return rc; }
   HIPCHK(hipMemcpyAsync(c->sob2_acc, c->grad, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
   const float jac_l1 = c->jac_l1, act_l1 = c->act_l1, act_l2 = c->act_l2;
   c->jac_l1 = 0.f; c->act_l1 = 0.f; c->act_l2 = 0.f;      // the regularisation losses belong to pass 0
@@ -1836,7 +1777,7 @@ static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const 
       if (!pjac_supported(pa))
         return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
       const long need_zt = (long)c->pi * ((B + 31) / 32) * 32 * c->r;
-      if (need_zt > c->zt_par_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->zt_par, &c->zt_par_cap, need_zt); if (rc) return rc; }
+      rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
       launch_pjac_fwd(pa, c->zt_par, c->st);
       spar.npar = sp.ns - sp.nsc; spar.ZT = c->zt_par;
       for (int e = 0; e < spar.npar; ++e) { spar.parc[e] = sp.par[sp.nsc + e]; spar.pcol[e] = sp.gcol[sp.nsc + e]; }
@@ -1853,7 +1794,7 @@ static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const 
     if (!pjac_supported(pa))
       return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
     const long need_zt = (long)c->pi * ((B + 31) / 32) * 32 * c->r;
-    if (need_zt > c->zt_par_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->zt_par, &c->zt_par_cap, need_zt); if (rc) return rc; }
+    rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
     launch_pjac_fwd(pa, c->zt_par, c->st);
     spar.ZT = c->zt_par;
   }
@@ -1914,10 +1855,10 @@ static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int
   const long ntiles = (B + 31) / 32;
   int rc = ensure_capacity(c, ntiles * 32 * (1 + ndmax), true); if (rc) return rc;
   const long need_mu = (long)(1 + ndmax) * ntiles * 32 * c->r;
-  if (need_mu > c->jac_mu_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->jac_mu, &c->jac_mu_cap, need_mu); if (rc) return rc; }
-  if (!c->jac_tmp) HIPCHK(hipMalloc(&c->jac_tmp, sizeof(float) * (size_t)(c->P + 2)));
+  rc = c->jac_mu.reserve(c, need_mu); if (rc) return rc;
+  if (!c->jac_tmp) { const int rca = c->jac_tmp.alloc(c->P + 2); if (rca) return rca; }
   const long nlp = (B + 127) / 128;
-  if (nlp > c->act_loss_cap) { HIPCHK(hipStreamSynchronize(c->st)); rc = grow(&c->act_loss, &c->act_loss_cap, nlp); if (rc) return rc; }
+  rc = c->act_loss.reserve(c, nlp); if (rc) return rc;
   PNetArgs pa; fill_pnet(c, pa, xin, B);
   const float coef = c->jac_l1 / ((float)Bg * (float)c->r * (float)pi);
   // r4: passes over groups of parameter columns (k_pjac carries pjac_group() tangents): loss and gradient are sums over the
@@ -1943,9 +1884,7 @@ static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int
     launch_gw_first(g, c->NSTB, rows, c->st);
     for (int mi = 0; mi < c->nm; ++mi) {
       base(g); g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.scale = pa.omega;
-      long w_off, b_off;
-      if (!c->cfg.p_resblock) { w_off = c->hid_w[mi]; b_off = c->hid_b[mi]; }
-      else { const int i = mi / 2; w_off = (mi & 1) ? c->hid_w2[i] : c->hid_w[i]; b_off = (mi & 1) ? c->hid_b2[i] : c->hid_b[i]; }
+      long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
       g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
       launch_gw_mfma(g, c->NSTB, c->NSTB, rows, c->st);
     }
@@ -1970,7 +1909,7 @@ static int sob_par_pass(nif_ctx* c, const float* xin, long B, long Bg, const Sob
   const long ntiles = (B + 31) / 32;
   const int ncol = c->pi + c->si;
   const int rows = rows_for(c, ntiles);
-  if (!c->jac_tmp) HIPCHK(hipMalloc(&c->jac_tmp, sizeof(float) * (size_t)(c->P + 2)));
+  if (!c->jac_tmp) { const int rca = c->jac_tmp.alloc(c->P + 2); if (rca) return rca; }
   const long blk_s = ntiles * 1024 * c->NB;                 // floats of one block of tiles in a ShapeNet stash slot
   float* sIN = sa.stash; float* sDA = sa.stash + (long)(c->nh + 1) * c->slot_s;
   const long kcols = (long)c->r * c->po;                     // the hyper kernel [r][po] = columns last_w .. last_w + r*po
@@ -2027,11 +1966,19 @@ extern "C" int nif_set_activity_regularizer(nif_ctx* c, float l1, float l2) {
   c->act_l1 = l2 != 0.f ? 0.f : l1; c->act_l2 = l2;
   return NIF_OK;
 }
+static int ensure_metric(nif_ctx* c) {
+  if (c->metric) return NIF_OK;
+  DevBuf<double> m;
+  const int rc = m.alloc(2); if (rc) return rc;
+  HIPCHK(hipMemsetAsync(m, 0, 2 * sizeof(double), c->st));
+  c->metric = std::move(m);
+  return NIF_OK;
+}
 extern "C" int nif_metric_accumulate(nif_ctx* c, float weight) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  if (!c->metric) { HIPCHK(hipMalloc(&c->metric, 2 * sizeof(double))); HIPCHK(hipMemsetAsync(c->metric, 0, 2 * sizeof(double), c->st)); }
+  { const int rcm = ensure_metric(c); if (rcm) return rcm; }
   int rc = nif_metric_flush(c); if (rc) return rc;
   if (c->last_step_small && c->opt_small_step && !c->capturing && !c->comm) {     // behind a small step: rides in the next k_small launch (grad[P] is not
     c->metric_pending = true; c->metric_pending_w = weight;          // touched before that launch's row reduction; every other path flushes)
@@ -2076,9 +2023,9 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
     SNetArgs sa; fill_snet(c, sa, nullptr, c->pi + c->si, c->pi, 32);
     if (small_supported(pa, sa)) { rc = ensure_small_tables(c, pa, sa); if (rc) return rc; }
   }
-  if (!c->metric) { HIPCHK(hipMalloc(&c->metric, 2 * sizeof(double))); HIPCHK(hipMemsetAsync(c->metric, 0, 2 * sizeof(double), c->st)); }
-  if (!c->opt_dev) HIPCHK(hipMalloc(&c->opt_dev, sizeof(OptDev)));
-  if (!c->opt_host) HIPCHK(hipHostMalloc(&c->opt_host, sizeof(OptDev)));
+  { const int rcm = ensure_metric(c); if (rcm) return rcm; }
+  if (!c->opt_dev) { rc = c->opt_dev.alloc(1); if (rc) return rc; }
+  if (!c->opt_host) { rc = c->opt_host.alloc(1); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(c->st));
   // (ensure_packed above did every first-use initialisation eagerly; the RECORDED sequence must start with the packing of whatever
   // weights the previous replay left behind)
@@ -2162,19 +2109,22 @@ extern "C" int nif_set_grad_transform(nif_ctx* c, const nif_grad_transform* t) {
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));      // (queued steps still read the device copy)
+  GtDev d; d.flags = z.flags; d.clipnorm = z.clipnorm; d.clipvalue = z.clipvalue; d.global_clipnorm = z.global_clipnorm;
   if (!c->gt_dev) {
     const std::vector<GtBlk> blks = gt_blocks(c);
     for (const GtBlk& b : blks)
       if (b.base < 0 || b.base + b.lim > c->P) return fail(NIF_ERR_STATE, "internal: gradient-transform block outside the gradient");
-    HIPCHK(hipMalloc(&c->gt_blk, sizeof(GtBlk) * blks.size()));
-    HIPCHK(hipMalloc(&c->gt_part, sizeof(float) * blks.size()));
-    HIPCHK(hipMalloc(&c->gt_norms, sizeof(float) * (c->layout.size() + 1)));
-    HIPCHK(hipMalloc(&c->gt_dev, sizeof(GtDev)));
-    HIPCHK(hipMemcpy(c->gt_blk, blks.data(), sizeof(GtBlk) * blks.size(), hipMemcpyHostToDevice));
+    // gt_dev != null says that all four exist and the block table is filled: they join the context together, after the last step that can fail
+    DevBuf<GtBlk> blk; DevBuf<float> part, norms; DevBuf<GtDev> dev;
+    int rc = blk.alloc((long)blks.size()); if (rc) return rc;
+    rc = part.alloc((long)blks.size()); if (rc) return rc;
+    rc = norms.alloc((long)c->layout.size() + 1); if (rc) return rc;
+    rc = dev.alloc(1); if (rc) return rc;
+    HIPCHK(hipMemcpy(blk, blks.data(), sizeof(GtBlk) * blks.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dev, &d, sizeof(d), hipMemcpyHostToDevice));
+    c->gt_blk = std::move(blk); c->gt_part = std::move(part); c->gt_norms = std::move(norms); c->gt_dev = std::move(dev);
     c->gt_nblk = (int)blks.size();
-  }
-  GtDev d; d.flags = z.flags; d.clipnorm = z.clipnorm; d.clipvalue = z.clipvalue; d.global_clipnorm = z.global_clipnorm;
-  HIPCHK(hipMemcpy(c->gt_dev, &d, sizeof(d), hipMemcpyHostToDevice));
+  } else HIPCHK(hipMemcpy(c->gt_dev, &d, sizeof(d), hipMemcpyHostToDevice));
   c->gt = z; c->gt_on = on;
   c->gt_norm = on && (gtcf ? z.clipnorm > 0.f : (z.clipnorm > 0.f || z.global_clipnorm > 0.f));
   return NIF_OK;
@@ -2236,8 +2186,10 @@ static bool opt_ams(const nif_opt* o) { return o->kind == NIF_OPT_ADABELIEF && (
 static int ensure_vhat(nif_ctx* c) {
   if (c->vhat) return NIF_OK;
   if (c->capturing) return fail(NIF_ERR_STATE, "AMSGrad's vhat slot does not exist yet: run one eager step or nif_set_opt_slot(2, ...) before the capture");
-  HIPCHK(hipMalloc(&c->vhat, sizeof(float) * (size_t)c->P));
-  HIPCHK(hipMemsetAsync(c->vhat, 0, sizeof(float) * (size_t)c->P, c->st));
+  DevBuf<float> vh;
+  const int rc = vh.alloc(c->P); if (rc) return rc;
+  HIPCHK(hipMemsetAsync(vh, 0, sizeof(float) * (size_t)c->P, c->st));
+  c->vhat = std::move(vh);
   return NIF_OK;
 }
 extern "C" int nif_opt_scalars(const nif_opt* o, int64_t t, double* out) {
@@ -2366,9 +2318,7 @@ extern "C" int nif_set_opt_slot(nif_ctx* c, int32_t slot, const float* host, int
 
 // ---- low-magnitude pruning (include/nif_hip.h nif_prune_*; k_prune.hip) -----------------------------------------------------------
 static void prune_free(nif_ctx* c) {
-  void* ptrs[] = {c->prune_segs_dev, c->prune_mask, c->prune_thr, c->prune_hist, c->prune_sel};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  c->prune_segs_dev = nullptr; c->prune_mask = nullptr; c->prune_thr = nullptr; c->prune_hist = nullptr; c->prune_sel = nullptr;
+  c->prune_segs_dev.drop(); c->prune_mask.drop(); c->prune_thr.drop(); c->prune_hist.drop(); c->prune_sel.drop();
   c->prune_segs.clear(); c->prune_nblk = 0; c->prune_lo = 0; c->prune_hi = 0;
 }
 // what every nif_prune_* call does first: no capture, the deferred row reduction and loss-metric accumulation run now
@@ -2395,16 +2345,20 @@ extern "C" int nif_prune_config(nif_ctx* c, int32_t n, const int64_t* offsets, c
   HIPCHK(hipStreamSynchronize(c->st));      // (queued work may still read the buffers freed here)
   prune_free(c);
   if (n == 0) return NIF_OK;
-  HIPCHK(hipMalloc(&c->prune_segs_dev, sizeof(PruneSeg) * (size_t)n));
-  HIPCHK(hipMalloc(&c->prune_mask, (size_t)c->P + 16));
-  HIPCHK(hipMalloc(&c->prune_thr, sizeof(float) * (size_t)n));
-  HIPCHK(hipMalloc(&c->prune_hist, sizeof(unsigned) * PRUNE_BINS * (size_t)n));
-  HIPCHK(hipMalloc(&c->prune_sel, sizeof(PruneSel) * (size_t)n));
-  HIPCHK(hipMemcpy(c->prune_segs_dev, segs.data(), sizeof(PruneSeg) * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(c->prune_mask, 1, (size_t)c->P + 16, c->st));
-  HIPCHK(hipMemsetAsync(c->prune_thr, 0, sizeof(float) * (size_t)n, c->st));
-  HIPCHK(hipMemsetAsync(c->prune_hist, 0, sizeof(unsigned) * PRUNE_BINS * (size_t)n, c->st));
+  // the five tables join the context together, after the last step that can fail: until then pruning stays unconfigured
+  DevBuf<PruneSeg> segs_dev; DevBuf<unsigned char> mask; DevBuf<float> thr; DevBuf<unsigned> hist; DevBuf<PruneSel> sel;
+  rc = segs_dev.alloc(n); if (rc) return rc;
+  rc = mask.alloc(c->P + 16); if (rc) return rc;
+  rc = thr.alloc(n); if (rc) return rc;
+  rc = hist.alloc((long)PRUNE_BINS * n); if (rc) return rc;
+  rc = sel.alloc(n); if (rc) return rc;
+  HIPCHK(hipMemcpy(segs_dev, segs.data(), sizeof(PruneSeg) * (size_t)n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(mask, 1, (size_t)c->P + 16, c->st));
+  HIPCHK(hipMemsetAsync(thr, 0, sizeof(float) * (size_t)n, c->st));
+  HIPCHK(hipMemsetAsync(hist, 0, sizeof(unsigned) * PRUNE_BINS * (size_t)n, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
+  c->prune_segs_dev = std::move(segs_dev); c->prune_mask = std::move(mask); c->prune_thr = std::move(thr);
+  c->prune_hist = std::move(hist); c->prune_sel = std::move(sel);
   c->prune_segs = segs; c->prune_nblk = nblk; c->prune_lo = segs.front().off; c->prune_hi = end;
   return NIF_OK;
 }
@@ -2550,9 +2504,9 @@ extern "C" int nif_last_loss(nif_ctx* c, float* loss) {
 
 static int stage_batch(nif_ctx* c, const float* xin, const float* y, const float* sw, long B) {
   HIPCHK(hipStreamSynchronize(c->st));
-  int rc = stage(c, &c->d_a, &c->cap_a, xin, B * (c->pi + c->si)); if (rc) return rc;
-  rc = stage(c, &c->d_b, &c->cap_b, y, B * c->so); if (rc) return rc;
-  if (sw) { rc = stage(c, &c->d_c, &c->cap_c, sw, B); if (rc) return rc; }
+  int rc = stage(c, c->d_a, xin, B * (c->pi + c->si)); if (rc) return rc;
+  rc = stage(c, c->d_b, y, B * c->so); if (rc) return rc;
+  if (sw) { rc = stage(c, c->d_c, sw, B); if (rc) return rc; }
   return NIF_OK;
 }
 int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, float** dx, float** dy, float** dsw) {
@@ -2627,8 +2581,10 @@ extern "C" int nif_debug_timeline(nif_ctx* c, int64_t* out, int32_t n_pairs) {
   TAIL_FLUSH(c)
   HIPCHK(hipStreamSynchronize(c->st));
   if (!c->tl) {
-    HIPCHK(hipMalloc(&c->tl, 4096 * sizeof(long long)));
-    HIPCHK(hipMemset(c->tl, 0, 4096 * sizeof(long long)));
+    DevBuf<long long> tl;
+    const int rc = tl.alloc(4096); if (rc) return rc;
+    HIPCHK(hipMemset(tl, 0, 4096 * sizeof(long long)));
+    c->tl = std::move(tl);
     return NIF_OK;   // first call arms the buffer
   }
   if (out && n_pairs > 0) HIPCHK(hipMemcpy(out, c->tl, sizeof(long long) * 2 * n_pairs, hipMemcpyDeviceToHost));

@@ -38,10 +38,11 @@ extern "C" int nif_comm_unique_id(void* id_out) {
 }
 
 static int comm_scratch(nif_ctx* c) {
-  if (!c->comm_scratch) {
-    HIPCHK(hipMalloc(&c->comm_scratch, 64));
-    HIPCHK(hipMemsetAsync(c->comm_scratch, 0, 64, c->st));
-  }
+  if (c->comm_scratch) return NIF_OK;
+  DevBuf<float> s;
+  const int rc = s.alloc(16); if (rc) return rc;
+  HIPCHK(hipMemsetAsync(s, 0, 64, c->st));
+  c->comm_scratch = std::move(s);
   return NIF_OK;
 }
 

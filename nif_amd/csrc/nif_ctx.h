@@ -18,6 +18,36 @@ static inline int fail(int code, const std::string& msg) { return nif_fail(code,
     }                                                                                             \
   } while (0)
 
+struct nif_ctx;
+// The one owner of a device allocation (Pinned: of a pinned host block): move-only, frees in its destructor, converts to T* so that
+// launch arguments read as with a raw pointer.  n is the element count it was allocated with -- the capacity; there is no second field.
+// Exact sizes, no geometric growth, contents not kept.  After a failed allocation the buffer is empty (p null, n 0): the call can be repeated.
+template <class T, bool Pinned = false>
+struct DevBuf {
+  T* p = nullptr; long n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { drop(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  ~DevBuf() { drop(); }
+  operator T*() const { return p; }
+  void drop() {      // no stream synchronisation of its own: for buffers nothing queued can read (locals, teardown, after a failure)
+    if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; n = 0;
+  }
+  int alloc(long count) {      // a fresh block of exactly `count` elements for a buffer that is empty (first use, set-up built into locals)
+    drop();
+    T* q = nullptr;
+    if (Pinned) HIPCHK(hipHostMalloc(&q, sizeof(T) * (size_t)count));
+    else HIPCHK(hipMalloc(&q, sizeof(T) * (size_t)count));
+    p = q; n = count;
+    return NIF_OK;
+  }
+  int release(nif_ctx* c);                 // the context's streams drained, then freed
+  int reserve(nif_ctx* c, long count);     // nothing (no synchronisation either) when count <= n; else release + alloc
+};
+
 struct NifF64;      // state of the double-precision L-BFGS closure (k_f64.hip), allocated at its first use
 
 struct nif_ctx {
@@ -37,59 +67,61 @@ struct nif_ctx {
   long s_bott_w = 0, s_bott_b = 0, ll_bias = 0;
   int RB = 1;   // ZL rows per tile = 32*RB
   // device state
-  float *theta = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr;
+  DevBuf<float> theta, grad, m, v;
   long step = 0;
   bool have_params = false, packed = false, packed32 = false, packed_p32 = false, use_snet3 = false, use_snet4 = false;
   bool jac_ok = false;        // JacobianLayer / HessianLayer kernels take this shape (jac_supported)
-  void *sWF4 = nullptr, *sWB4 = nullptr;   // bf16-split planes of the hidden hyper-matrices (k_snet4)
-  void *sWF4x = nullptr, *sWB4x = nullptr; // k_snet6 (r5): exact-product HALF (hi, lo) planes of the hidden hyper-matrices (k_pack16b mode 3)
-  float* sWscale = nullptr;                //   and their powers of two [matrix][plane]
-  void *sWF4h = nullptr, *sWB4h = nullptr; // the policies' compact plane set (one bf16 / half plane per block: k_snet4 / k_snet6<.., PR>)
+  DevBuf<char> sWF4, sWB4;   // bf16-split planes of the hidden hyper-matrices (k_snet4)
+  DevBuf<char> sWF4x, sWB4x; // k_snet6 (r5): exact-product HALF (hi, lo) planes of the hidden hyper-matrices (k_pack16b mode 3)
+  DevBuf<float> sWscale;                   //   and their powers of two [matrix][plane]
+  DevBuf<char> sWF4h, sWB4h; // the policies' compact plane set (one bf16 / half plane per block: k_snet4 / k_snet6<.., PR>)
   bool use_ll4 = false;                    // last-layer class: dense ShapeNet on k_snet4
-  float* ll_slots = nullptr;               // its parameters in k_snet4's slot order (launch_ll_slots)
-  void *ll_wpf = nullptr, *ll_wpb = nullptr;   // phi layer as bf16-split MFMA operands (launch_pack_phi)
-  f32x4 *pWF = nullptr, *pWB = nullptr, *sWF = nullptr, *sWB = nullptr, *lWF = nullptr, *lWB = nullptr;
-  // workspaces (capacity in points)
+  DevBuf<float> ll_slots;                  // its parameters in k_snet4's slot order (launch_ll_slots)
+  DevBuf<char> ll_wpf, ll_wpb;   // phi layer as bf16-split MFMA operands (launch_pack_phi)
+  DevBuf<f32x4> pWF, pWB, sWF, sWB, lWF, lWB;
+  // workspaces: cap is the capacity in points of the point workspaces (Z .. DZL) and, where they exist, of the stashes (their slot
+  // strides derive from it); every other buffer's capacity is its own n
   long cap = 0;
-  float *stash_s = nullptr, *stash_p = nullptr, *Z = nullptr, *DZ = nullptr, *DU = nullptr, *ZL = nullptr;
+  DevBuf<float> stash_s, stash_p, Z, DZ, DU, ZL;
   long slot_s = 0, slot_p = 0;
-  float* partial = nullptr; int rows_cap = 0; long pstride = 0;
-  float* loss_partial = nullptr; long nloss_cap = 0;
-  float* dring = nullptr; long dring_cap = 0;
-  long long* tl = nullptr;   // timeline stamps (measurement builds)
+  DevBuf<float> partial; long pstride = 0;     // [rows_cap()][pstride] partial gradient | loss rows; pstride is fixed by P (nif_create)
+  int rows_cap() const { return (int)(partial.n / pstride); }
+  DevBuf<float> loss_partial;
+  DevBuf<float> dring;
+  DevBuf<long long> tl;      // timeline stamps (measurement builds)
   float reg_l1 = 0.f, reg_l2 = 0.f; long reg_lo = 0, reg_hi = 0; bool reg_applied = false;
   float sreg_l1 = 0.f, sreg_l2 = 0.f;   // last-layer class: cfg_shape_net l1_reg / l2_reg over the shared ShapeNet's kernels and biases [s_first_w, ll_bias)
-  double* metric = nullptr;  // device {sum, count}
+  DevBuf<double> metric;     // device {sum, count}
   // activity regulariser of the ParameterNet output (nif_set_activity_regularizer): L2 wins over L1 like in the reference
   bool ll_packed32 = false;     // last-layer class under k_sob at n > 96: f32-input MFMA planes of the shared hidden matrices in sWF / sWB
-  float* zt_par = nullptr; long zt_par_cap = 0; float* dzt_par = nullptr; long dzt_par_cap = 0;
-  float* dat_par = nullptr; long dat_par_cap = 0; float* ztl_par = nullptr; long ztl_par_cap = 0;   // last-layer class: dL/da', z' in latent-row layout   // Sobolev with parameter seeds: dz/dp, dL/d(dz/dp)
-  float jac_l1 = 0.f; float* jac_mu = nullptr; long jac_mu_cap = 0; float* jac_tmp = nullptr;   // latent Jacobian regulariser (k_pjac)
+  DevBuf<float> zt_par, dzt_par;
+  DevBuf<float> dat_par, ztl_par;   // last-layer class: dL/da', z' in latent-row layout   // Sobolev with parameter seeds: dz/dp, dL/d(dz/dp)
+  float jac_l1 = 0.f; DevBuf<float> jac_mu, jac_tmp;   // latent Jacobian regulariser (k_pjac)
   // captured training steps (nif_graph_*): hipGraph executables, the steps each one carries, the device-side optimizer state (and its
   // pinned staging copy), and the optimizer kind / amsgrad flag each capture recorded (-1: no update step) -- a graph is replayed only
   // with the kind it holds
   std::vector<hipGraphExec_t> graphs; std::vector<int> graph_steps; bool capturing = false; int cap_steps = 0; long cap_step0 = 0;
-  OptDev* opt_dev = nullptr; OptDev* opt_host = nullptr;
-  float* vhat = nullptr;       // AdaBelief's amsgrad slot, allocated on first use
+  DevBuf<OptDev> opt_dev; DevBuf<OptDev, true> opt_host;
+  DevBuf<float> vhat;          // AdaBelief's amsgrad slot, allocated on first use
   int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
   // magnitude pruning (nif_prune_*): the segment table (host copy: the k of the last update), its span [prune_lo, prune_hi), a byte mask
   // over the whole of theta (1 outside the segments), the thresholds and the select's histograms / per-segment state
   std::vector<PruneSeg> prune_segs; long prune_nblk = 0, prune_lo = 0, prune_hi = 0;
-  PruneSeg* prune_segs_dev = nullptr; unsigned char* prune_mask = nullptr; float* prune_thr = nullptr;
-  unsigned* prune_hist = nullptr; PruneSel* prune_sel = nullptr;
+  DevBuf<PruneSeg> prune_segs_dev; DevBuf<unsigned char> prune_mask; DevBuf<float> prune_thr;
+  DevBuf<unsigned> prune_hist; DevBuf<PruneSel> prune_sel;
   // gradient transform (nif_set_grad_transform): the configured struct, whether any stage is on / a norm stage is on, the work-block
   // table, one partial sum of squares per block, the norms [tensors | global], and the struct's device copy; all built at the first
   // non-zero set.  gt_ran: 0 no transform has run, 1 the last one ran without a norm stage (norms not formed yet), 2 with.
   // cap_gt / graph_gt: the launches a capture recorded (0 none, 1 k_gt_reduce, 2 both)
   nif_grad_transform gt = {}; bool gt_on = false, gt_norm = false; int gt_ran = 0;
-  GtBlk* gt_blk = nullptr; int gt_nblk = 0; float* gt_part = nullptr; float* gt_norms = nullptr; GtDev* gt_dev = nullptr;
+  DevBuf<GtBlk> gt_blk; int gt_nblk = 0; DevBuf<float> gt_part, gt_norms; DevBuf<GtDev> gt_dev;
   int cap_gt = 0; std::vector<char> graph_gt;
   bool ll_mlp_packed = false;        // last-layer class: the f32 planes of the 32-point MLP kernels are current
   int loss_kind = 0;                 // NIF_LOSS_* (nif_set_loss)
-  float* sob2_acc = nullptr;         // [grad | loss] summed over the passes of a second-order Sobolev step (nif_sobolev2_loss_grad_dev)
-  float* sob_acc = nullptr;          // [grad | loss] summed over the column groups of a Sobolev step with more than three x_index columns
-  float act_l1 = 0.f, act_l2 = 0.f; float* act_part = nullptr; long act_part_cap = 0; float* act_loss = nullptr; long act_loss_cap = 0;
-  float *stash_l = nullptr, *PHI = nullptr, *DPHI = nullptr, *DA = nullptr, *DZL = nullptr; long slot_l = 0;
+  DevBuf<float> sob2_acc;            // [grad | loss] summed over the passes of a second-order Sobolev step (nif_sobolev2_loss_grad_dev)
+  DevBuf<float> sob_acc;             // [grad | loss] summed over the column groups of a Sobolev step with more than three x_index columns
+  float act_l1 = 0.f, act_l2 = 0.f; DevBuf<float> act_part, act_loss;
+  DevBuf<float> PHI, DPHI, DA, DZL;
   // profiling: (group id, start, stop) event triples recorded on st
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;
@@ -99,20 +131,19 @@ struct nif_ctx {
   long prof_cnt[NIF_PROF_N] = {0};
   hipEvent_t t0 = nullptr, t1 = nullptr;
   // staging for the host-pointer API
-  float *d_a = nullptr, *d_b = nullptr, *d_c = nullptr, *d_d = nullptr;
-  long cap_a = 0, cap_b = 0, cap_c = 0, cap_d = 0;
+  DevBuf<float> d_a, d_b, d_c, d_d;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
-  float* comm_scratch = nullptr;   // 64 B device scratch for barrier()
+  DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()
   // two-stream chunk pipeline of the training step (nif_api.hip: loss_grad_core)
   hipStream_t st2 = nullptr; hipEvent_t ev_start = nullptr, ev_done = nullptr; std::vector<hipEvent_t> ev_chunk;
-  float* chunk_grad = nullptr; int chunk_cap = 0;      // [chunks][pstride]: per-chunk gradient | loss rows
+  DevBuf<float> chunk_grad;                            // [chunks][pstride]: per-chunk gradient | loss rows
   bool opt_side_pnet = false;                          // whole-batch step: ParameterNet adjoint on st2 next to the gradient reductions
   long opt_pipe_chunk = -1; int opt_pipe_wgs = 512;    // points per chunk (-1 default, 0 off); fused-kernel workgroups per chunk
   // shard streaming (nif_h2d_async): a copy stream and, per staging slot, 'copy landed' / 'slot consumed' events
   hipStream_t st_copy = nullptr; hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
   bool opt_fp32_mfma = false;      // nif_set_option("fp32_mfma"): A/B switch, default from NIF_FP32_MFMA
-  int* small_idx = nullptr; int* small_desc = nullptr;     // k_small's tables (offsets only), built at the first small step
+  DevBuf<int> small_idx, small_desc;                       // k_small's tables (offsets only), built at the first small step
   bool metric_pending = false; float metric_pending_w = 0.f;   // a nif_metric_accumulate deferred into the next k_small launch
   bool last_step_small = false;
   // r6: the row reduction of a plain step may wait for its consumer -- the optimizer step then runs it fused with the update (one launch
@@ -120,7 +151,22 @@ struct nif_ctx {
   bool tail_pending = false; int tail_rows = 0, tail_nloss = 0; bool opt_fuse_tail = true;
   bool opt_small_step = true;      // nif_set_option("small_step"): batches <= NIF_SMALL_MAX_B points of a net k_small takes run on it (one launch for loss + gradient); default from NIF_SMALL_STEP
   bool opt_fuse_gw = true;         // nif_set_option("fuse_gw"): ShapeNet weight gradients inside the training kernel (k_snet6) where it has the shape; default from NIF_FUSE_GW
+  nif_ctx() = default;
+  nif_ctx(const nif_ctx&) = delete;
+  ~nif_ctx();      // streams, events, graph executables, the communicator and the float64 state; then the buffers free themselves (nif_api.hip)
 };
+
+template <class T, bool Pinned> int DevBuf<T, Pinned>::release(nif_ctx* c) {
+  HIPCHK(hipStreamSynchronize(c->st));
+  if (c->st2) HIPCHK(hipStreamSynchronize(c->st2));
+  drop();
+  return NIF_OK;
+}
+template <class T, bool Pinned> int DevBuf<T, Pinned>::reserve(nif_ctx* c, long count) {
+  if (count <= n) return NIF_OK;
+  const int rc = release(c); if (rc) return rc;
+  return alloc(count);
+}
 
 // RAII-ish helper: records an event pair around a kernel group when profiling is on
 struct ProfScope {
@@ -147,7 +193,7 @@ int nif_tail_flush(nif_ctx* c);
 // a nif_metric_accumulate that waits for the next k_small launch (nif_ctx::metric_pending), run before anything else rewrites grad[P]
 // or reads the metric (nif_api.hip); runs the deferred row reduction first
 int nif_metric_flush(nif_ctx* c);
-// the double-precision path behind include/nif_hip.h's nif_f64_* (k_f64.hip); nif_f64_release frees its buffers (nif_destroy)
+// the double-precision path behind include/nif_hip.h's nif_f64_* (k_f64.hip); nif_f64_release deletes its state (~nif_ctx)
 int nif_f64_set_params_impl(nif_ctx* c, const double* host, int64_t n);
 int nif_f64_get_params_impl(nif_ctx* c, double* host, int64_t n);
 int nif_f64_forward_dev_impl(nif_ctx* c, const double* xin, int64_t B, double* u);
