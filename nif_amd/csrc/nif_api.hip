@@ -15,6 +15,19 @@
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
 static inline bool act_on(const nif_ctx* c) { return c->act_l1 != 0.f || c->act_l2 != 0.f; }
+// Scope of the passes of a multi-pass step that run without jac_reg and the activity regulariser (their losses belong to the first
+// pass): the coefficients are zero inside and back on every way out
+struct RegsOff {
+  nif_ctx* c; float jac_l1, act_l1, act_l2;
+  RegsOff(nif_ctx* c_, bool on) : c(on ? c_ : nullptr) {
+    if (!c) return;
+    jac_l1 = c->jac_l1; act_l1 = c->act_l1; act_l2 = c->act_l2;
+    c->jac_l1 = 0.f; c->act_l1 = 0.f; c->act_l2 = 0.f;
+  }
+  ~RegsOff() { if (c) { c->jac_l1 = jac_l1; c->act_l1 = act_l1; c->act_l2 = act_l2; } }
+  RegsOff(const RegsOff&) = delete;
+  RegsOff& operator=(const RegsOff&) = delete;
+};
 static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int* mu_blk = nullptr);
 // Sobolev streams of one x_index: coordinate seeds first, then the parameter seeds (their pseudo-tiles trail the stashes, so
 // that the first-layer reduction simply stops in front of them); gcol = the x_index position (column of dydx) of each stream
@@ -431,6 +444,17 @@ static MatRef vec_ref(long b_off, int nout) { MatRef m; m.r = 0; m.base_k = 0; m
 static MatRef hyper_ref(const nif_ctx* c, long slot, int ld, int nin, int nout) {
   MatRef m; m.r = c->r; m.base_k = c->last_w + slot; m.kstride = c->po; m.base_last = c->last_b + slot; m.ld = ld; m.nin = nin; m.nout = nout; return m;
 }
+// Hyper-slot layout of one row of the [r][po] hyper kernel (and of the hyper bias): the ShapeNet's kernels first (si x n), hidden j
+// (n x n each), last (n x so), then its biases in the same order.  Layer l: 0 = first, 1 + j = hidden matrix j, nh + 1 = last.  The
+// host side's one statement of it (the kernels' prologues derive the same offsets from SNetArgs)
+static long hyper_wslot(const nif_ctx* c, int l) { return l == 0 ? 0 : (long)c->si * c->n + (long)(l - 1) * c->n * c->n; }
+static long hyper_bslot(const nif_ctx* c, int l) { return hyper_wslot(c, c->nh + 1) + (long)c->n * c->so + (long)l * c->n; }
+// ... and the layers as operands of the weight-gradient reductions
+static MatRef hyper_w(const nif_ctx* c, int l) {
+  const int nin = l == 0 ? c->si : c->n, nout = l == c->nh + 1 ? c->so : c->n;
+  return hyper_ref(c, hyper_wslot(c, l), nout, nin, nout);
+}
+static MatRef hyper_b(const nif_ctx* c, int l) { return hyper_ref(c, hyper_bslot(c, l), 0, 1, l == c->nh + 1 ? c->so : c->n); }
 
 // matrix j of an MLP's hidden stack (pairs (w, w2) per layer with resblocks) -> offsets of its kernel and bias in theta
 static void mlp_mat(bool res, const long* w, const long* b, const long* w2, const long* b2, int j, long* w_off, long* b_off) {
@@ -532,11 +556,10 @@ static int ensure_packed32(nif_ctx* c) {
   const bool fmt16 = c->use_snet3 || c->jac_ok;     // 16-point-tile plane format (k_snet3, k_jac, k_sob) / 32-point (k_snet)
   const long plane_s = fmt16 ? snet3_plane_floats(c->n) / 4 : (long)c->NB * c->NB * 256;
   for (int j = 0; j < c->nh; ++j) {
-    const long slot = (long)c->si * c->n + (long)j * c->n * c->n;
     f32x4* wf = c->sWF + (long)j * (c->r + 1) * plane_s;
     f32x4* wb = c->sWB + (long)j * (c->r + 1) * plane_s;
-    if (fmt16) launch_pack16(c->theta, hyper_ref(c, slot, c->n, c->n, c->n), snet3_nbl(c->n), wf, wb, c->st);
-    else launch_pack(c->theta, hyper_ref(c, slot, c->n, c->n, c->n), c->NB, c->NB, wf, wb, c->st);
+    if (fmt16) launch_pack16(c->theta, hyper_w(c, 1 + j), snet3_nbl(c->n), wf, wb, c->st);
+    else launch_pack(c->theta, hyper_w(c, 1 + j), c->NB, c->NB, wf, wb, c->st);
   }
   HIPCHK(hipGetLastError());
   c->packed32 = true;
@@ -616,14 +639,14 @@ static int ensure_packed(nif_ctx* c) {
   c->use_snet4 = c->sWF4 && !fp32_only && snet4_supported(probe);
   c->packed32 = false;
   if (c->use_snet4 && c->nh > 0 && c->sWF4x)   // all hidden hyper-matrices (n^2 slots apart): split groups, half planes and their scales in ONE launch (r5)
-    launch_pack16b_dual(c->theta, hyper_ref(c, (long)c->si * c->n, c->n, c->n, c->n), (long)c->n * c->n, c->nh, snet3_nbl(c->n),
+    launch_pack16b_dual(c->theta, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, snet3_nbl(c->n),
                         c->sWF4, c->sWB4, snet4_fwd_elems(c->n, c->r), snet4_bwd_elems(c->n, c->r),
                         c->sWF4x, c->sWB4x, snet4_bwd_elems(c->n, c->r), snet4_bwd_elems(c->n, c->r), probe.omega, c->sWscale, c->st);
   else if (c->use_snet4 && c->nh > 0)
-    launch_pack16b_batch(c->theta, hyper_ref(c, (long)c->si * c->n, c->n, c->n, c->n), (long)c->n * c->n, c->nh, snet3_nbl(c->n),
+    launch_pack16b_batch(c->theta, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, snet3_nbl(c->n),
                          c->sWF4, c->sWB4, snet4_fwd_elems(c->n, c->r), snet4_bwd_elems(c->n, c->r), probe.omega, c->st);
   if (c->use_snet4 && c->nh > 0 && c->sWF4h)
-    launch_pack16b_batch(c->theta, hyper_ref(c, (long)c->si * c->n, c->n, c->n, c->n), (long)c->n * c->n, c->nh, snet3_nbl(c->n),
+    launch_pack16b_batch(c->theta, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, snet3_nbl(c->n),
                          c->sWF4h, c->sWB4h, snet4_fwd_elems(c->n, c->r) / 3, snet4_bwd_elems(c->n, c->r) / 2, probe.omega, c->st,
                          policy_prec(c));
   HIPCHK(hipGetLastError());
@@ -996,6 +1019,102 @@ extern "C" int nif_shapenet_given_w(nif_ctx* c, const float* x, const float* w, 
   return NIF_OK;
 }
 
+// ---- training step: the pieces every class and pass shares -------------------------------------------
+static int rows_for(const nif_ctx* c, long ntiles) {
+  int rows = (int)((ntiles + 3) / 4);
+  if (rows > c->rows_cap()) rows = c->rows_cap();
+  return rows < 1 ? 1 : rows;
+}
+// NIF_PNET_STASH=1 forces the ParameterNet adjoint through its HBM stash (A/B runs, tests); default: small ParameterNets keep no stash,
+// the adjoint kernel recomputes the forward pass and reduces the weight gradients itself (k_pnetbw.hip)
+static bool pnet_force_stash() {
+  static const bool on = [] { const char* e = getenv("NIF_PNET_STASH"); return e && e[0] == '1'; }();
+  return on;
+}
+static int ensure_jac_tmp(nif_ctx* c) { return c->jac_tmp ? NIF_OK : c->jac_tmp.alloc(c->P + 2); }
+// block of c->dzt_par that holds dL/dz' of each parameter column (jac_reg_pass, given mu); -1: none
+struct MuBlk { int blk[16]; MuBlk() { for (int& b : blk) b = -1; } };
+// The SobPar of a plan, as every launch_sob call (query or launch) starts from it; a site adds only what is its own: the last-layer
+// class sets par = -1 and its head fields, the hypernetwork classes ZT / DZT
+static SobPar sob_par_of(const SobPlan& sp) {
+  SobPar q{};
+  for (int d = 0; d < 3; ++d) { q.par[d] = sp.par[d]; q.gcol[d] = sp.gcol[d]; }
+  q.gstride = sp.gstride; q.nx_all = sp.nx_all; q.ny = sp.ny; q.no_primal = sp.no_primal; q.ymask = sp.ymask; q.hess = sp.hess;
+  return q;
+}
+// z' = dz/dp of every parameter column into c->zt_par (k_pjac, forward mode), in front of the ShapeNet; train: + room for the
+// dL/dz' of up to three streams
+static int ensure_zt_par(nif_ctx* c, const PNetArgs& pa, long ntiles, bool train) {
+  if (!pjac_supported(pa))
+    return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
+  int rc = c->zt_par.reserve(c, (long)c->pi * ntiles * 32 * c->r); if (rc) return rc;
+  if (train) { rc = c->dzt_par.reserve(c, 3 * ntiles * 32 * c->r); if (rc) return rc; }
+  launch_pjac_fwd(pa, c->zt_par, c->st);
+  return NIF_OK;
+}
+// Workgroups (= loss partials) of the last-layer class's k_snet4<LL> step, and its act'(a) ring
+static int ll4_plan(nif_ctx* c, SNetArgs& sa, int* nloss) {
+  *nloss = launch_snet4(sa, true, true, c->st);
+  const int rc = c->dring.reserve(c, (long)*nloss * 4 * snet3_ring_floats_per_wave(c->n, c->nh)); if (rc) return rc;
+  sa.dring = c->dring;
+  return NIF_OK;
+}
+
+// Weight-gradient reductions into partial rows.  Every GwArgs of a step starts from gw_base; gw_add_tangents makes the reduction run
+// over n blocks of tangent pseudo-tiles behind the real tiles as well (Sobolev streams, the z' tangents of jac_reg_pass).  The two
+// stacks below are the one statement of the reduction sequence of the ParameterNet and of the hypernetwork ShapeNet
+static GwArgs gw_base(const nif_ctx* c, long ntiles, long B, float* partial) {
+  GwArgs q;
+  memset(&q, 0, sizeof(q));
+  q.ntiles = ntiles; q.B = B; q.partial = partial; q.pstride = c->pstride; q.has_bias = 1; q.scale = 1.0f;
+  return q;
+}
+static void gw_add_tangents(GwArgs& q, int n, const int* seeds) {
+  q.zt_mod = q.ntiles; q.bias_ntiles = q.ntiles; q.ntiles *= 1 + n;
+  for (int d = 0; d < 3; ++d) q.seed[d] = (seeds && d < n) ? seeds[d] : 0;
+}
+// ParameterNet: first layer, hidden matrices, bottleneck -- from the stash slots at pST, SM = dL/d(bottleneck output)
+static void gw_pnet_stack(const nif_ctx* c, const GwArgs& base, const float* xin, const float* pST, const float* SM, float omega, int rows,
+                          hipStream_t st) {
+  GwArgs g = base;
+  g.DA = pST + (long)(c->nm + 1) * c->slot_p; g.xin = xin; g.ncol = c->pi + c->si; g.col0 = 0; g.nd = c->pi; g.scale = omega;
+  g.W = dense_ref(c->first_w, c->pi, c->nst); g.Bv = vec_ref(c->first_b, c->nst);
+  launch_gw_first(g, c->NSTB, rows, st);
+  for (int mi = 0; mi < c->nm; ++mi) {
+    g = base; g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.scale = omega;
+    long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
+    g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
+    launch_gw_mfma(g, c->NSTB, c->NSTB, rows, st);
+  }
+  g = base; g.IN = pST + (long)c->nm * c->slot_p; g.SM = SM; g.nc = c->r;
+  g.W = dense_ref(c->bott_w, c->nst, c->r); g.Bv = vec_ref(c->bott_b, c->r);
+  launch_gw_out(g, c->NSTB, rows, st);
+}
+// Hypernetwork ShapeNet: first layer, hidden matrices, last layer -- the stashes and DU of sa, block blk of their tiles as the dL/da
+// side (0: the step's own tiles and pseudo-tiles; 1 + d: stream d alone, sob_par_pass), Z in the latent's place; base carries the
+// tangent pseudo-tiles (zt_mod = the real tiles), the first layer runs over first_ntiles of them.  < 0: launch_gw_mfma's refusal
+static int gw_hyper_snet_stack(const nif_ctx* c, const GwArgs& base, const SNetArgs& sa, const float* xin, const float* Z, long blk,
+                               long first_ntiles, bool da_bf16, bool in_ph16, int rows, hipStream_t st) {
+  const float* sIN = sa.stash;
+  const float* sDA = sa.stash + (long)(c->nh + 1) * c->slot_s + blk * base.zt_mod * 1024 * c->NB;
+  GwArgs g = base;
+  g.DA = sDA; g.xin = xin; g.ncol = c->pi + c->si; g.col0 = c->pi; g.nd = c->si; g.Z = Z; g.r = c->r; g.scale = sa.omega;
+  g.W = hyper_w(c, 0); g.Bv = hyper_b(c, 0);
+  g.ntiles = first_ntiles;
+  launch_gw_first(g, c->NB, rows, st);
+  for (int j = 0; j < c->nh; ++j) {
+    g = base; g.IN = sIN + (long)j * c->slot_s; g.DA = sDA + (long)(j + 1) * c->slot_s; g.Z = Z; g.r = c->r; g.scale = sa.omega;
+    g.da_bf16 = da_bf16 ? 1 : 0;
+    g.in_ph16 = in_ph16 ? 1 : 0;
+    g.W = hyper_w(c, 1 + j); g.Bv = hyper_b(c, 1 + j);
+    if (launch_gw_mfma(g, c->NB, c->NB, rows, st) < 0) return -1;
+  }
+  g = base; g.IN = sIN + (long)c->nh * c->slot_s; g.SM = sa.DU + blk * base.zt_mod * c->so * 32; g.nc = c->so; g.Z = Z; g.r = c->r;
+  g.W = hyper_w(c, c->nh + 1); g.Bv = hyper_b(c, c->nh + 1);
+  launch_gw_out(g, c->NB, rows, st);
+  return 0;
+}
+
 // ---- last-layer-parameterised class: loss and gradient ---------------------------------------------
 // SNetArgs of the last-layer class for k_sob (Sobolev step / its predict): k_snet4's arguments for that class plus, beyond the
 // widths whose bf16 planes fit the LDS (n > 96), the f32-input MFMA planes of the shared hidden matrices, packed on demand
@@ -1029,8 +1148,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, c->pi, B);
   LLArgs la; fill_ll(c, la, B);
   la.y = y; la.sw = sw; la.inv_bg = 1.0f / (float)Bg;
-  static const bool force_stash_ll = [] { const char* e = getenv("NIF_PNET_STASH"); return e && e[0] == '1'; }();
-  const bool fused_p = !force_stash_ll && pnet_bwg_supported(pa);
+  const bool fused_p = !pnet_force_stash() && pnet_bwg_supported(pa);
   if (!fused_p) { const int rcp = ensure_packed_p32(c); if (rcp) return rcp; }
   { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, !fused_p, c->st); }
   int nloss = (int)((ntiles * 32 + 255) / 256);
@@ -1038,17 +1156,12 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   if (ns > 0) {   // Sobolev: primal + tangents + their adjoint on k_sob<.., LL>; stashes and DPHI hold (1 + ns) blocks of tiles
     SNetArgs sa; int rc = fill_snet_ll_sob(c, sa, xin, B); if (rc) return rc;
     sa.y = y; sa.sw = sw; sa.loss_partial = c->loss_partial; sa.inv_bg = 1.0f / (float)Bg;
-    SobPar spq{};
-    for (int d = 0; d < 3; ++d) spq.par[d] = -1;
-    spq.hess = sp->hess;
-    nloss = launch_sob(sa, true, nsc, sp->seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spq);
+    SobPar spar = sob_par_of(*sp);
+    for (int d = 0; d < 3; ++d) spar.par[d] = -1;       // (parameter columns are heads of the epilogue here, not streams)
+    nloss = launch_sob(sa, true, nsc, sp->seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spar);
     if (nloss < 0) return fail(NIF_ERR_INVALID, "Sobolev step: the kernel's working set of this shape does not fit the 160 KB LDS of a CU");
     const long need = (long)nloss * 4 * sob_ring_floats_per_wave(c->n, c->nh);
     rc = c->dring.reserve(c, need); if (rc) return rc;
-    SobPar spar{};
-    for (int d = 0; d < 3; ++d) { spar.par[d] = -1; spar.gcol[d] = sp->gcol[d]; }
-    spar.gstride = sp->gstride; spar.nx_all = sp->nx_all; spar.ny = sp->ny; spar.no_primal = sp->no_primal; spar.ymask = sp->ymask;
-    spar.hess = sp->hess;
     if (nhead > 0) {     // parameter columns: heads of the epilogue (z' = dz/dp sits in c->zt_par, loss_grad_core)
       const long need_a = 3 * ntiles * 32 * c->r, need_l = 3 * ntiles * 32 * 32 * c->RB;
       rc = c->dat_par.reserve(c, need_a); if (rc) return rc;
@@ -1075,10 +1188,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
       ll_ph = snet4_writes_h_ph16(sa);
       if (ll_ph != (sa.h_ph16 != 0)) return fail(NIF_ERR_STATE, "internal: layer-input stash format of producer and plan disagree");
     }
-    nloss = launch_snet4(sa, true, true, c->st);
-    const long need = (long)nloss * 4 * snet3_ring_floats_per_wave(c->n, c->nh);
-    int rc = c->dring.reserve(c, need); if (rc) return rc;
-    sa.dring = c->dring;
+    int rc = ll4_plan(c, sa, &nloss); if (rc) return rc;
     ProfScope p_(c, NIF_PROF_SNET);
     if (launch_snet4(sa, true, false, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no k_snet4 form for this net (SIREN planes not packed as half pairs)");
   } else {
@@ -1094,64 +1204,40 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     const bool l1 = c->act_l2 == 0.f;
     n_act = launch_ll_actreg(c->Z, c->theta + c->last_w, c->r, B, (l1 ? c->act_l1 : c->act_l2) / (float)Bg, l1, c->DA, c->DZL, c->act_loss, c->st);
   }
-  int rows = (int)((ntiles + 3) / 4);
-  if (rows > c->rows_cap()) rows = c->rows_cap();
-  if (rows < 1) rows = 1;
+  const int rows = rows_for(c, ntiles);
   { ProfScope p_(c, NIF_PROF_PNET_BWD);
     if (fused_p) launch_pnet_bwg(pa, c->partial, c->pstride, rows, c->st);
     else launch_pnet_bwd(pa, c->NSTB, c->st); }
   {
     ProfScope p_(c, NIF_PROF_GW);
-    GwArgs g;
-    auto base = [&](GwArgs& q) {
-      memset(&q, 0, sizeof(q));
-      q.ntiles = ntiles; q.B = B; q.partial = c->partial; q.pstride = c->pstride; q.has_bias = 1; q.scale = 1.0f; q.r = 0;
-    };
+    const GwArgs base = gw_base(c, ntiles, B, c->partial);
+    GwArgs sbase = base;            // Sobolev: the ShapeNet reductions also run over the tangent pseudo-tiles
+    if (nsc > 0) gw_add_tangents(sbase, nsc, sp->seeds);
     const int nms = c->nh;  // hidden matrices of the ShapeNet (2L with resblocks)
     float* sST = c->stash_s;
-    auto sbase = [&](GwArgs& q) {   // Sobolev: the ShapeNet reductions also run over the tangent pseudo-tiles
-      base(q);
-      if (nsc > 0) {
-        q.ntiles = ntiles * (1 + nsc); q.zt_mod = ntiles; q.bias_ntiles = ntiles;
-        for (int d = 0; d < 3; ++d) q.seed[d] = d < nsc ? sp->seeds[d] : 0;
-      }
-    };
     // ShapeNet (dense SIREN): first, hidden matrices, bottleneck (n -> r*so), last_layer_bias
-    sbase(g); g.DA = sST + (long)(nms + 1) * c->slot_s; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.scale = ma.omega;
+    GwArgs g = sbase;
+    g.DA = sST + (long)(nms + 1) * c->slot_s; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.scale = ma.omega;
     if (ns > 0 && sp->hess) g.ntiles = ntiles * 3;      // (the second-order stream has no first-layer input: a'' = 0 there)
     g.W = dense_ref(c->s_first_w, c->si, c->n); g.Bv = vec_ref(c->s_first_b, c->n);
     launch_gw_first(g, c->NB, rows, c->st);
     for (int mi = 0; mi < nms; ++mi) {
-      sbase(g); g.IN = sST + (long)mi * c->slot_s; g.DA = sST + (long)(nms + 2 + mi) * c->slot_s; g.scale = ma.omega;
+      g = sbase; g.IN = sST + (long)mi * c->slot_s; g.DA = sST + (long)(nms + 2 + mi) * c->slot_s; g.scale = ma.omega;
       long w_off, b_off; snet_mat(c, mi, &w_off, &b_off);
       g.W = dense_ref(w_off, c->n, c->n); g.Bv = vec_ref(b_off, c->n);
       g.da_bf16 = ll_dab ? 1 : 0;
       g.in_ph16 = ll_ph ? 1 : 0;
       if (launch_gw_mfma(g, c->NB, c->NB, rows, c->st) < 0) return fail(NIF_ERR_STATE, "internal: bf16 dL/da stash rows without a reader of that form");
     }
-    sbase(g); g.IN = sST + (long)nms * c->slot_s; g.SM = c->DPHI; g.nc = c->r * c->so;
+    g = sbase; g.IN = sST + (long)nms * c->slot_s; g.SM = c->DPHI; g.nc = c->r * c->so;
     g.W = dense_ref(c->s_bott_w, c->n, c->r * c->so); g.Bv = vec_ref(c->s_bott_b, c->r * c->so);
     launch_gw_out(g, c->NB, rows, c->st);
-    base(g); g.IN = sST + (long)nms * c->slot_s; g.SM = c->DU; g.nc = c->so;   // only the bias part: W.nin = 0
+    g = base; g.IN = sST + (long)nms * c->slot_s; g.SM = c->DU; g.nc = c->so;   // only the bias part: W.nin = 0
     g.W = dense_ref(0, 0, c->so); g.Bv = vec_ref(c->ll_bias, c->so);
     launch_gw_out(g, c->NB, rows, c->st);
     // ParameterNet: first, hidden matrices, bottleneck, last (r x r)
-    float* pST = c->stash_p;
-    if (!fused_p) {
-    base(g); g.DA = pST + (long)(c->nm + 1) * c->slot_p; g.xin = xin; g.ncol = ncol; g.col0 = 0; g.nd = c->pi; g.scale = pa.omega;
-    g.W = dense_ref(c->first_w, c->pi, c->nst); g.Bv = vec_ref(c->first_b, c->nst);
-    launch_gw_first(g, c->NSTB, rows, c->st);
-    for (int mi = 0; mi < c->nm; ++mi) {
-      base(g); g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.scale = pa.omega;
-      long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
-      g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
-      launch_gw_mfma(g, c->NSTB, c->NSTB, rows, c->st);
-    }
-    base(g); g.IN = pST + (long)c->nm * c->slot_p; g.SM = c->DZL; g.nc = c->r;
-    g.W = dense_ref(c->bott_w, c->nst, c->r); g.Bv = vec_ref(c->bott_b, c->r);
-    launch_gw_out(g, c->NSTB, rows, c->st);
-    }
-    base(g); g.IN = c->ZL; g.SM = c->DA; g.nc = c->r;   // latent (padded rows) x dL/da
+    if (!fused_p) gw_pnet_stack(c, base, xin, c->stash_p, c->DZL, pa.omega, rows, c->st);
+    g = base; g.IN = c->ZL; g.SM = c->DA; g.nc = c->r;   // latent (padded rows) x dL/da
     g.W = dense_ref(c->last_w, c->r, c->r); g.Bv = vec_ref(c->last_b, c->r);
     launch_gw_out(g, c->RB, rows, c->st);
   }
@@ -1164,14 +1250,12 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   if (nhead > 0) {
     // the heads' share of the r x r layer: dL/dlast_w += z'^T dL/da' (a' = z' last_w has no bias), the same reduction as the
     // main one with (z', dL/da') as the operand pair; then the (primal, tangent) ParameterNet for dL/dz' (jac_reg_pass, given mu)
-    if (!c->jac_tmp) { const int rca = c->jac_tmp.alloc(c->P + 2); if (rca) return rca; }
-    int mu_blk[16];
-  for (int q = 0; q < 16; ++q) mu_blk[q] = -1;
+    { const int rca = ensure_jac_tmp(c); if (rca) return rca; }
+    MuBlk mu;
     const long rr = (long)c->r * c->r;
     for (int e = 0; e < nhead; ++e) {
-      mu_blk[sp->par[nsc + e]] = e;
-      GwArgs g; memset(&g, 0, sizeof(g));
-      g.ntiles = ntiles; g.B = B; g.partial = c->partial; g.pstride = c->pstride; g.has_bias = 1; g.scale = 1.0f; g.r = 0;
+      mu.blk[sp->par[nsc + e]] = e;
+      GwArgs g = gw_base(c, ntiles, B, c->partial);
       g.IN = c->ztl_par + (long)e * ntiles * 32 * 32 * c->RB; g.SM = c->dat_par + (long)e * ntiles * 32 * c->r; g.nc = c->r;
       g.W = dense_ref(c->last_w, c->r, c->r); g.Bv = vec_ref(c->last_b, c->r);     // (the bias columns are not taken over)
       launch_gw_out(g, c->RB, rows, c->st);
@@ -1179,7 +1263,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
       launch_axpy_cols(c->grad + c->last_w, c->jac_tmp, rr, c->P - c->last_w, c->st);
     }
     HIPCHK(hipGetLastError());
-    return jac_reg_pass(c, xin, B, Bg, mu_blk);
+    return jac_reg_pass(c, xin, B, Bg, mu.blk);
   }
   HIPCHK(hipGetLastError());
   return NIF_OK;
@@ -1188,13 +1272,12 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
 // Workspace sizing of the fused ShapeNet kernel the step will launch (no launch): number of workgroups (= loss partials),
 // the act'(a) ring, the optional edge-gradient partials.  Grows buffers when needed (stream sync + device allocation): call
 // nif_reserve() once up front to keep that out of the timed steps.
-static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nloss, const int* par_of = nullptr, bool hess = false) {
+static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nloss, const SobPlan* sp = nullptr) {
   int rc;
   if (ns > 0) {
-    SobPar spq{};     // (the parameter streams' extra per-wave LDS counts)
-    for (int d = 0; d < 3; ++d) spq.par[d] = par_of ? par_of[d] : -1;
-    spq.hess = hess ? 1 : 0;
-    const int nblk = launch_sob(sa, true, ns, seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spq);
+    SobPar spq{};     // (the parameter streams' extra per-wave LDS counts; no plan: first-order coordinate streams, as launch_sob takes no SobPar)
+    if (sp) spq = sob_par_of(*sp);
+    const int nblk = launch_sob(sa, true, ns, seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, sp ? &spq : nullptr);
     if (nblk < 0)
       return fail(NIF_ERR_INVALID, "Sobolev step: the kernel's working set of this shape (units, latent_dim, parameter columns) does not fit the 160 KB LDS of a CU");
     const long need = (long)nblk * 4 * sob_ring_floats_per_wave(c->n, c->nh);
@@ -1209,12 +1292,6 @@ static int snet_plan(nif_ctx* c, SNetArgs& sa, int ns, const int* seeds, int* nl
   }
   sa.dring = c->dring;
   return NIF_OK;
-}
-
-static int rows_for(const nif_ctx* c, long ntiles) {
-  int rows = (int)((ntiles + 3) / 4);
-  if (rows > c->rows_cap()) rows = c->rows_cap();
-  return rows < 1 ? 1 : rows;
 }
 
 // chunk size (points) of the two-stream pipeline, 0 = off.  nif_set_option("pipe_chunk", points) / NIF_PIPE_CHUNK;
@@ -1260,10 +1337,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   PNetArgs pa; fill_pnet(c, pa, xin, B);
   pa.Z = c->Z + t0 * 32 * c->r; pa.DZ = c->DZ + t0 * 32 * c->r;
   if (pa.stash) pa.stash += t0 * 32 * 32 * c->NSTB;
-  // small ParameterNets: no stash -- the adjoint kernel recomputes the forward pass and reduces the weight
-  // gradients itself (k_pnetbw.hip).  NIF_PNET_STASH=1 forces the stash path (A/B runs, tests)
-  static const bool force_stash = [] { const char* e = getenv("NIF_PNET_STASH"); return e && e[0] == '1'; }();
-  const bool fused_p = !force_stash && pnet_bwg_supported(pa);
+  const bool fused_p = !pnet_force_stash() && pnet_bwg_supported(pa);
   if (!fused_p) { const int rcp = ensure_packed_p32(c); if (rcp) return rcp; }
   { ProfScope p_(c, NIF_PROF_PNET_FWD, sa_st); launch_pnet(pa, c->NSTB, !fused_p, sa_st); }
   SNetArgs sa; fill_snet(c, sa, xin, ncol, c->pi, B);
@@ -1272,7 +1346,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   sa.y = y; sa.sw = sw; sa.u_out = nullptr; sa.loss_partial = loss_partial; sa.inv_bg = 1.0f / (float)Bg;
   if (!whole) sa.wg_cap = c->opt_pipe_wgs;        // leave room on every CU for the reductions of the previous chunk
   int nloss = (int)((ntiles + 3) / 4);
-  rc = snet_plan(c, sa, ns, seeds, &nloss, sp ? sp->par : nullptr, sp && sp->hess); if (rc) return rc;
+  rc = snet_plan(c, sa, ns, seeds, &nloss, sp); if (rc) return rc;
   // plain SIREN step on the bf16-split kernel: every ShapeNet weight gradient inside the training kernel (k_snet6) -- its workgroups
   // are the partial-gradient rows, so the row count of this step has to be the kernel's grid
   const bool fused_gw = ns == 0 && whole && c->use_snet4 && c->opt_fuse_gw && snet6_supported(sa) &&
@@ -1298,17 +1372,10 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
   {
     ProfScope p_(c, NIF_PROF_SNET, sa_st);
     if (ns > 0) {
-      SobPar spar{}; const SobPar* sparp = nullptr;
-      if (sp) { spar.gstride = sp->gstride; spar.nx_all = sp->nx_all; spar.ny = sp->ny; spar.no_primal = sp->no_primal; spar.ymask = sp->ymask;
-                spar.hess = sp->hess; }
-      if (sp && sp->any_par) {
-        for (int d = 0; d < 3; ++d) { spar.par[d] = sp->par[d]; spar.gcol[d] = sp->gcol[d]; }
-        spar.ZT = c->zt_par; spar.DZT = c->dzt_par; sparp = &spar;
-      } else if (sp) {
-        for (int d = 0; d < 3; ++d) { spar.par[d] = -1; spar.gcol[d] = sp->gcol[d]; }
-        spar.ZT = nullptr; spar.DZT = nullptr; sparp = &spar;
-      }
-      launch_sob(sa, true, ns, seeds, gt, wj, c->dring, nullptr, false, sa_st, sparp);
+      SobPar spar{};
+      if (sp) spar = sob_par_of(*sp);      // (a plan without parameter columns has par = -1 throughout: sobolev_plan)
+      if (sp && sp->any_par) { spar.ZT = c->zt_par; spar.DZT = c->dzt_par; }
+      launch_sob(sa, true, ns, seeds, gt, wj, c->dring, nullptr, false, sa_st, sp ? &spar : nullptr);
     }
     else if (fused_gw) launch_snet6(sa, partial, c->pstride, sa_st);
     else if (c->use_snet4) { if (launch_snet4(sa, true, false, sa_st) < 0) return fail(NIF_ERR_STATE, "internal: no k_snet4 form for this net (SIREN planes not packed as half pairs)"); }
@@ -1337,63 +1404,17 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
     if (fused_p) launch_pnet_bwg(pa, partial, c->pstride, rows, pb_st, touch, (long)c->NB * 1024);
     else launch_pnet_bwd(pa, c->NSTB, pb_st); }
   ProfScope pgw(c, NIF_PROF_GW, sb_st);
-  GwArgs g;
-  auto base = [&](GwArgs& q) {
-    memset(&q, 0, sizeof(q));
-    q.ntiles = ntiles; q.B = B; q.partial = partial; q.pstride = c->pstride; q.has_bias = 1; q.scale = 1.0f;
-  };
-  auto sbase = [&](GwArgs& q) {   // ShapeNet reductions also run over the tangent pseudo-tiles
-    base(q);
-    q.ntiles = ntiles * (1 + ns); q.zt_mod = ntiles; q.bias_ntiles = ntiles;
-    for (int d = 0; d < 3; ++d) q.seed[d] = (seeds && d < ns) ? seeds[d] : 0;
-  };
-  const float om_s = sa.omega, om_p = pa.omega;
-  float* sIN = sa.stash; float* sDA = sa.stash + (long)(c->nh + 1) * c->slot_s;
-  if (!fused_gw) {
-  // ShapeNet first layer
-  sbase(g); g.DA = sDA; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.Z = sa.Z; g.r = c->r; g.scale = om_s;
-  g.W = hyper_ref(c, 0, c->n, c->si, c->n);
-  g.Bv = hyper_ref(c, (long)c->si * c->n + (long)c->nh * c->n * c->n + (long)c->n * c->so, 0, 1, c->n);
-  if (sp) g.ntiles = ntiles * (1 + sp->nsc);      // a parameter stream has no tangent input here (x' = 0): its pairs go to sob_par_pass
-  if (sp && sp->hess) g.ntiles = ntiles * 3;      // nor has the second-order stream (a'' = 0 at the first layer)
-  launch_gw_first(g, c->NB, rows, sb_st);
-  // ShapeNet hidden matrices
-  for (int j = 0; j < c->nh; ++j) {
-    sbase(g); g.IN = sIN + (long)j * c->slot_s; g.DA = sDA + (long)(j + 1) * c->slot_s; g.Z = sa.Z; g.r = c->r; g.scale = om_s;
-    g.da_bf16 = wrote_da_bf16 ? 1 : 0;
-    g.in_ph16 = wrote_h_ph16 ? 1 : 0;
-    const long wslot = (long)c->si * c->n + (long)j * c->n * c->n;
-    const long bslot = (long)c->si * c->n + (long)c->nh * c->n * c->n + (long)c->n * c->so + c->n + (long)j * c->n;
-    g.W = hyper_ref(c, wslot, c->n, c->n, c->n);
-    g.Bv = hyper_ref(c, bslot, 0, 1, c->n);
-    if (launch_gw_mfma(g, c->NB, c->NB, rows, sb_st) < 0) return fail(NIF_ERR_STATE, "internal: bf16 dL/da stash rows without a reader of that form");
+  const GwArgs base = gw_base(c, ntiles, B, partial);
+  if (!fused_gw) {     // ShapeNet: its reductions also run over the tangent pseudo-tiles
+    GwArgs sbase = base;
+    gw_add_tangents(sbase, ns, seeds);
+    long first_ntiles = sbase.ntiles;
+    if (sp) first_ntiles = ntiles * (1 + sp->nsc);      // a parameter stream has no tangent input here (x' = 0): its pairs go to sob_par_pass
+    if (sp && sp->hess) first_ntiles = ntiles * 3;      // nor has the second-order stream (a'' = 0 at the first layer)
+    if (gw_hyper_snet_stack(c, sbase, sa, xin, sa.Z, 0, first_ntiles, wrote_da_bf16, wrote_h_ph16, rows, sb_st) < 0)
+      return fail(NIF_ERR_STATE, "internal: bf16 dL/da stash rows without a reader of that form");
   }
-  // ShapeNet last layer
-  {
-    sbase(g); g.IN = sIN + (long)c->nh * c->slot_s; g.SM = sa.DU; g.nc = c->so; g.Z = sa.Z; g.r = c->r; g.scale = 1.0f;
-    const long wslot = (long)c->si * c->n + (long)c->nh * c->n * c->n;
-    const long bslot = wslot + (long)c->n * c->so + c->n + (long)c->nh * c->n;
-    g.W = hyper_ref(c, wslot, c->so, c->n, c->so);
-    g.Bv = hyper_ref(c, bslot, 0, 1, c->so);
-    launch_gw_out(g, c->NB, rows, sb_st);
-  }
-  }
-  // ParameterNet: first, hidden matrices, bottleneck
-  float* pST = pa.stash;
-  if (!fused_p) {
-  base(g); g.DA = pST + (long)(c->nm + 1) * c->slot_p; g.xin = xin; g.ncol = ncol; g.col0 = 0; g.nd = c->pi; g.r = 0; g.scale = om_p;
-  g.W = dense_ref(c->first_w, c->pi, c->nst); g.Bv = vec_ref(c->first_b, c->nst);
-  launch_gw_first(g, c->NSTB, rows, pb_st);
-  for (int mi = 0; mi < c->nm; ++mi) {
-    base(g); g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.r = 0; g.scale = om_p;
-    long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
-    g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
-    launch_gw_mfma(g, c->NSTB, c->NSTB, rows, pb_st);
-  }
-  base(g); g.IN = pST + (long)c->nm * c->slot_p; g.SM = pa.DZ; g.nc = c->r; g.r = 0; g.scale = 1.0f;
-  g.W = dense_ref(c->bott_w, c->nst, c->r); g.Bv = vec_ref(c->bott_b, c->r);
-  launch_gw_out(g, c->NSTB, rows, pb_st);
-  }
+  if (!fused_p) gw_pnet_stack(c, base, xin, pa.stash, pa.DZ, pa.omega, rows, pb_st);
   if (sa_out) *sa_out = sa;
   HIPCHK(hipGetLastError());
   return NIF_OK;
@@ -1487,12 +1508,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
   rc = ensure_capacity(c, ntiles * 32 * (1 + ns), true); if (rc) return rc;
   if (sp && sp->any_par) {   // z' = dz/dp of the parameter columns, in front of the ShapeNet
     PNetArgs pa; fill_pnet(c, pa, xin, B);
-    if (!pjac_supported(pa))
-      return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
-    const long need_zt = (long)c->pi * ntiles * 32 * c->r, need_dzt = 3 * ntiles * 32 * c->r;
-    rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
-    rc = c->dzt_par.reserve(c, need_dzt); if (rc) return rc;
-    launch_pjac_fwd(pa, c->zt_par, c->st);
+    rc = ensure_zt_par(c, pa, ntiles, true); if (rc) return rc;
   }
   c->reg_applied = false;
   if (c->kind == NIF_KIND_LASTLAYER) return loss_grad_ll(c, xin, y, sw, B, Bg, ns, sp, gt, wj);
@@ -1580,9 +1596,8 @@ extern "C" int nif_reserve(nif_ctx* c, int64_t B_max, int32_t n_tangents) {
   if (c->kind == NIF_KIND_LASTLAYER) {
     if (c->use_ll4) {
       SNetArgs sa; fill_snet_ll(c, sa, nullptr, c->pi + c->si, c->pi, B_max);
-      const int nblk = launch_snet4(sa, true, true, c->st);
-      const long need = (long)nblk * 4 * snet3_ring_floats_per_wave(c->n, c->nh);
-      rc = c->dring.reserve(c, need); if (rc) return rc;
+      int nblk = 0;
+      rc = ll4_plan(c, sa, &nblk); if (rc) return rc;
     }
     return NIF_OK;
   }
@@ -1650,8 +1665,7 @@ static int sob_cols_per_pass(nif_ctx* c, const int32_t* x_idx, int nx) {
       SobPlan sp;
       if (sobolev_plan(c, x_idx + g0, ng, &sp) != NIF_OK) return 3;
       SNetArgs sa; fill_snet(c, sa, nullptr, c->pi + c->si, c->pi, 64);
-      SobPar spq{};
-      for (int d = 0; d < 3; ++d) spq.par[d] = sp.par[d];
+      const SobPar spq = sob_par_of(sp);
       ok = launch_sob(sa, true, ng, sp.seeds, nullptr, 0.f, nullptr, nullptr, true, c->st, &spq) >= 0;
     }
     if (ok) return gs;
@@ -1670,14 +1684,13 @@ extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const f
   const int gs = sob_cols_per_pass(c, x_idx, nx);
   const int ngroups = (nx + gs - 1) / gs;
   if (ngroups > 1 && !c->sob_acc) { rc = c->sob_acc.alloc(c->P + 1); if (rc) return rc; }
-  const float jac_l1 = c->jac_l1, act_l1 = c->act_l1, act_l2 = c->act_l2;
   for (int k = 0; k < ngroups; ++k) {
     const int g0 = gs * k, ng = nx - g0 < gs ? nx - g0 : gs;
     SobPlan sp;
     rc = sobolev_plan(c, x_idx + g0, ng, &sp); if (rc) break;
     for (int q = 0; q < 3; ++q) sp.gcol[q] += g0;
     sp.gstride = nx; sp.nx_all = nx; sp.ny = nys; sp.ymask = ymask; sp.no_primal = k > 0;
-    if (k > 0) { c->jac_l1 = 0.f; c->act_l1 = 0.f; c->act_l2 = 0.f; }      // the regularisation losses belong to the first pass
+    const RegsOff regs_off(c, k > 0);      // the regularisation losses belong to the first pass
     rc = loss_grad_core(c, xin, y, sw, B, Bg, ng, sp.seeds, dydx, w_jac, &sp);
     if (rc) break;
     if (ngroups > 1) {
@@ -1685,7 +1698,6 @@ extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const f
       else launch_axpy_cols(c->sob_acc, c->grad, c->P, c->P, c->st);
     }
   }
-  c->jac_l1 = jac_l1; c->act_l1 = act_l1; c->act_l2 = act_l2;
   if (rc) return rc;
   if (ngroups > 1) HIPCHK(hipMemcpyAsync(c->grad, c->sob_acc, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
   c->reg_applied = false;
@@ -1719,8 +1731,8 @@ extern "C" int nif_sobolev2_loss_grad_dev(nif_ctx* c, const float* xin, const fl
   rc = nif_sobolev_loss_grad_dev_y(c, xin, y, dydx, sw, B, Bg, x_idx, nx, y_idx, ny, w_jac); if (rc) return rc;
   if (!c->sob2_acc) { rc = c->sob2_acc.alloc(c->P + 1); if (rc) return rc; }
   HIPCHK(hipMemcpyAsync(c->sob2_acc, c->grad, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
-  const float jac_l1 = c->jac_l1, act_l1 = c->act_l1, act_l2 = c->act_l2;
-  c->jac_l1 = 0.f; c->act_l1 = 0.f; c->act_l2 = 0.f;      // the regularisation losses belong to pass 0
+  {
+  const RegsOff regs_off(c, true);      // the regularisation losses belong to pass 0
   for (int j = 0; j < nx && !rc; ++j)
     for (int k = j; k < nx && !rc; ++k) {
       SobPlan sp;
@@ -1733,7 +1745,7 @@ extern "C" int nif_sobolev2_loss_grad_dev(nif_ctx* c, const float* xin, const fl
       rc = loss_grad_core(c, xin, y, sw, B, Bg, 3, sp.seeds, d2ydx2, w_hess, &sp);
       if (!rc) launch_axpy_cols(c->sob2_acc, c->grad, c->P, c->P, c->st);
     }
-  c->jac_l1 = jac_l1; c->act_l1 = act_l1; c->act_l2 = act_l2;
+  }
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->grad, c->sob2_acc, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
   c->reg_applied = false;
@@ -1769,17 +1781,14 @@ static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const 
   rc = ensure_capacity(c, B, false); if (rc) return rc;
   PNetArgs pa; fill_pnet(c, pa, xin, B);
   launch_pnet(pa, c->NSTB, false, c->st);
-  SobPar spar{};
-  for (int d = 0; d < 3; ++d) { spar.par[d] = sp.par[d]; spar.gcol[d] = sp.gcol[d]; }
-  spar.gstride = sp.gstride; spar.nx_all = sp.nx_all;
+  SobPar spar = sob_par_of(sp);
+  if (sp.any_par) {       // z' = dz/dp of the parameter columns
+    rc = ensure_zt_par(c, pa, (B + 31) / 32, false); if (rc) return rc;
+    spar.ZT = c->zt_par;
+  }
   if (c->kind == NIF_KIND_LASTLAYER) {
-    if (sp.any_par) {       // parameter columns: heads of the epilogue on z' = dz/dp
-      if (!pjac_supported(pa))
-        return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
-      const long need_zt = (long)c->pi * ((B + 31) / 32) * 32 * c->r;
-      rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
-      launch_pjac_fwd(pa, c->zt_par, c->st);
-      spar.npar = sp.ns - sp.nsc; spar.ZT = c->zt_par;
+    if (sp.any_par) {       // ... which are heads of the epilogue here
+      spar.npar = sp.ns - sp.nsc;
       for (int e = 0; e < spar.npar; ++e) { spar.parc[e] = sp.par[sp.nsc + e]; spar.pcol[e] = sp.gcol[sp.nsc + e]; }
       for (int d = 0; d < 3; ++d) spar.par[d] = -1;
     }
@@ -1789,14 +1798,6 @@ static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const 
       return fail(NIF_ERR_INVALID, "Sobolev path: the kernel's working set of this shape does not fit the 160 KB LDS of a CU");
     HIPCHK(hipGetLastError());
     return NIF_OK;
-  }
-  if (sp.any_par) {
-    if (!pjac_supported(pa))
-      return fail(NIF_ERR_INVALID, "Sobolev x_index on parameter columns: ParameterNets of up to 128 units");
-    const long need_zt = (long)c->pi * ((B + 31) / 32) * 32 * c->r;
-    rc = c->zt_par.reserve(c, need_zt); if (rc) return rc;
-    launch_pjac_fwd(pa, c->zt_par, c->st);
-    spar.ZT = c->zt_par;
   }
   SNetArgs sa; fill_snet(c, sa, xin, c->pi + c->si, c->pi, B);
   sa.u_out = u;
@@ -1856,7 +1857,7 @@ static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int
   int rc = ensure_capacity(c, ntiles * 32 * (1 + ndmax), true); if (rc) return rc;
   const long need_mu = (long)(1 + ndmax) * ntiles * 32 * c->r;
   rc = c->jac_mu.reserve(c, need_mu); if (rc) return rc;
-  if (!c->jac_tmp) { const int rca = c->jac_tmp.alloc(c->P + 2); if (rca) return rca; }
+  rc = ensure_jac_tmp(c); if (rc) return rc;
   const long nlp = (B + 127) / 128;
   rc = c->act_loss.reserve(c, nlp); if (rc) return rc;
   PNetArgs pa; fill_pnet(c, pa, xin, B);
@@ -1868,29 +1869,11 @@ static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int
     if (mu_blk) { bool any = false; for (int d = 0; d < nd; ++d) any = any || mu_blk[c0 + d] >= 0; if (!any) continue; }
     const int nloss = mu_blk ? launch_pjac_adj(pa, c->dzt_par, mu_blk, c->jac_mu, c->act_loss, c0, nd, c->st)
                              : launch_pjac(pa, coef, c->jac_mu, c->act_loss, c0, nd, c->st);
-    const long nt_all = ntiles * (1 + nd);
-    const int rows = rows_for(c, nt_all);
-    GwArgs g;
-    auto base = [&](GwArgs& q) {
-      memset(&q, 0, sizeof(q));
-      q.ntiles = nt_all; q.zt_mod = ntiles; q.bias_ntiles = ntiles; q.B = B; q.partial = c->partial; q.pstride = c->pstride;
-      q.has_bias = 1; q.scale = 1.0f; q.r = 0;
-      for (int d = 0; d < 3; ++d) q.seed[d] = d < nd ? c0 + d : 0;
-    };
-    float* pST = c->stash_p;
-    const int ncol = c->pi + c->si;
-    base(g); g.DA = pST + (long)(c->nm + 1) * c->slot_p; g.xin = xin; g.ncol = ncol; g.col0 = 0; g.nd = pi; g.scale = pa.omega;
-    g.W = dense_ref(c->first_w, pi, c->nst); g.Bv = vec_ref(c->first_b, c->nst);
-    launch_gw_first(g, c->NSTB, rows, c->st);
-    for (int mi = 0; mi < c->nm; ++mi) {
-      base(g); g.IN = pST + (long)mi * c->slot_p; g.DA = pST + (long)(c->nm + 2 + mi) * c->slot_p; g.scale = pa.omega;
-      long w_off, b_off; pnet_mat(c, mi, &w_off, &b_off);
-      g.W = dense_ref(w_off, c->nst, c->nst); g.Bv = vec_ref(b_off, c->nst);
-      launch_gw_mfma(g, c->NSTB, c->NSTB, rows, c->st);
-    }
-    base(g); g.IN = pST + (long)c->nm * c->slot_p; g.SM = c->jac_mu; g.nc = c->r; g.scale = 1.0f;
-    g.W = dense_ref(c->bott_w, c->nst, c->r); g.Bv = vec_ref(c->bott_b, c->r);
-    launch_gw_out(g, c->NSTB, rows, c->st);
+    GwArgs base = gw_base(c, ntiles, B, c->partial);
+    const int cols[3] = {c0, c0 + 1, c0 + 2};
+    gw_add_tangents(base, nd, cols);
+    const int rows = rows_for(c, base.ntiles);
+    gw_pnet_stack(c, base, xin, c->stash_p, c->jac_mu, pa.omega, rows, c->st);
     // the ParameterNet core variables are the first last_w columns of a partial row; column last_w of the result = the loss term
     launch_reduce(c->partial, c->pstride, rows, c->act_loss, nloss, c->jac_tmp, c->last_w, c->st);
     launch_axpy_cols(c->grad, c->jac_tmp, c->last_w, c->P, c->st);
@@ -1907,49 +1890,23 @@ static int jac_reg_pass(nif_ctx* c, const float* xin, long B, long Bg, const int
 //   k_sob left in c->dzt_par (jac_reg_pass with given mu).
 static int sob_par_pass(nif_ctx* c, const float* xin, long B, long Bg, const SobPlan& sp, const SNetArgs& sa) {
   const long ntiles = (B + 31) / 32;
-  const int ncol = c->pi + c->si;
   const int rows = rows_for(c, ntiles);
-  if (!c->jac_tmp) { const int rca = c->jac_tmp.alloc(c->P + 2); if (rca) return rca; }
-  const long blk_s = ntiles * 1024 * c->NB;                 // floats of one block of tiles in a ShapeNet stash slot
-  float* sIN = sa.stash; float* sDA = sa.stash + (long)(c->nh + 1) * c->slot_s;
+  { const int rca = ensure_jac_tmp(c); if (rca) return rca; }
   const long kcols = (long)c->r * c->po;                     // the hyper kernel [r][po] = columns last_w .. last_w + r*po
-  int mu_blk[16];
-  for (int q = 0; q < 16; ++q) mu_blk[q] = -1;
+  GwArgs base = gw_base(c, ntiles, B, c->partial);
+  gw_add_tangents(base, 0, nullptr);                         // (one block of tiles per launch, Z by tile as in the main step)
+  MuBlk mu;
   for (int d = sp.nsc; d < sp.ns; ++d) {
     const int col = sp.par[d];
-    mu_blk[col] = d;
+    mu.blk[col] = d;
     const float* ZTd = c->zt_par + (long)col * ntiles * 32 * c->r;
-    GwArgs g;
-    auto base = [&](GwArgs& q) {
-      memset(&q, 0, sizeof(q));
-      q.ntiles = ntiles; q.zt_mod = ntiles; q.bias_ntiles = ntiles; q.B = B; q.partial = c->partial; q.pstride = c->pstride;
-      q.has_bias = 1; q.scale = 1.0f; q.Z = ZTd; q.r = c->r;
-    };
-    base(g); g.DA = sDA + (1 + d) * blk_s; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.scale = sa.omega;
-    g.W = hyper_ref(c, 0, c->n, c->si, c->n);
-    g.Bv = hyper_ref(c, (long)c->si * c->n + (long)c->nh * c->n * c->n + (long)c->n * c->so, 0, 1, c->n);
-    launch_gw_first(g, c->NB, rows, c->st);
-    for (int j = 0; j < c->nh; ++j) {
-      base(g); g.IN = sIN + (long)j * c->slot_s; g.DA = sDA + (long)(j + 1) * c->slot_s + (1 + d) * blk_s; g.scale = sa.omega;
-      const long wslot = (long)c->si * c->n + (long)j * c->n * c->n;
-      const long bslot = (long)c->si * c->n + (long)c->nh * c->n * c->n + (long)c->n * c->so + c->n + (long)j * c->n;
-      g.W = hyper_ref(c, wslot, c->n, c->n, c->n);
-      g.Bv = hyper_ref(c, bslot, 0, 1, c->n);
-      launch_gw_mfma(g, c->NB, c->NB, rows, c->st);
-    }
-    {
-      base(g); g.IN = sIN + (long)c->nh * c->slot_s; g.SM = sa.DU + (long)(1 + d) * ntiles * c->so * 32; g.nc = c->so;
-      const long wslot = (long)c->si * c->n + (long)c->nh * c->n * c->n;
-      const long bslot = wslot + (long)c->n * c->so + c->n + (long)c->nh * c->n;
-      g.W = hyper_ref(c, wslot, c->so, c->n, c->so);
-      g.Bv = hyper_ref(c, bslot, 0, 1, c->so);
-      launch_gw_out(g, c->NB, rows, c->st);
-    }
+    if (gw_hyper_snet_stack(c, base, sa, xin, ZTd, 1 + d, ntiles, false, false, rows, c->st) < 0)
+      return fail(NIF_ERR_STATE, "internal: bf16 dL/da stash rows without a reader of that form");
     launch_reduce(c->partial + c->last_w, c->pstride, rows, nullptr, 0, c->jac_tmp, kcols, c->st);
     launch_axpy_cols(c->grad + c->last_w, c->jac_tmp, kcols, c->P - c->last_w, c->st);
   }
   HIPCHK(hipGetLastError());
-  return jac_reg_pass(c, xin, B, Bg, mu_blk);
+  return jac_reg_pass(c, xin, B, Bg, mu.blk);
 }
 
 // compile(loss=...) of the Keras surface (README.md:33 'mse'): the per-element loss of every training / evaluation entry point of this

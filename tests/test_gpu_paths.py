@@ -114,6 +114,8 @@ KNOBS = [
     ({"NIF_SIDE_PNET": "1", "NIF_FUSE_GW": "0"}, "ms_cfg2_64x4", "plain", "float32"),
     ({"NIF_PBW_TOUCH": "0", "NIF_FUSE_GW": "0"}, "ms_cfg2_64x4", "plain", "float32"),
     ({"NIF_PNET_STASH": "1"}, "ms_cfg3_128x3", "plain", "float32"),        # ParameterNet adjoint through its HBM stash
+    ({"NIF_PNET_STASH": "1"}, "ll_plain_32x2_r3", "plain", "float32"),     # ... from the last-layer class's step (gw_pnet_stack's second caller)
+    ({"NIF_PNET_STASH": "1"}, "ms_cfg5_64x4_si2", "sobolev", "float32"),   # ... and behind the Sobolev kernel
     ({"NIF_PNET_BF2": "0"}, "ms_cfg3_128x3", "plain", "float32"),          # 64-unit ParameterNet on the f32-input MFMAs
     ({"NIF_GW8": "0"}, "ms_cfg3_128x3", "plain", "float32"),               # 128-wide weight gradients on k_gw_lds<4, 2, 1>
     ({"NIF_GW8": "0", "NIF_GW_LDS": "0"}, "ms_cfg3_128x3", "plain", "float32"),   # ... on the register-load form
