@@ -266,34 +266,70 @@ int nif_adam_step_dev(nif_ctx* ctx, const nif_adam* opt);
  *   NIF_OPT_ADABELIEF  external_optimizers.py:322-628 (dense apply :456-530), slots m, v and (amsgrad) vhat: optional warm-up /
  *                      linear decay of lr_d over total_steps, rectification behind sma_threshold (RAdam), v += eps
  *   NIF_OPT_ADAM       nif_adam_step_dev / nif_graph_launch, bit for bit (decay and the AdaBelief fields must be zero)
+ * Keras 2.11's own optimizers (tf.keras.optimizers.*).  Their formulas are restated here from Keras 2.11 and are NOT pinned by a
+ * TensorFlow run (parity unpinned by TensorFlow); lr is the step's learning rate, g the gradient, every operation one float32 rounding:
+ *   NIF_OPT_SGD        beta1 = momentum (beta2, eps zero), slot 0 m.  momentum == 0: theta -= lr g.  Otherwise m = momentum m - lr g and
+ *                      theta += m, or with NIF_OPT_NESTEROV theta += momentum m - lr g (the new m)
+ *   NIF_OPT_RMSPROP    beta2 = rho, beta1 = momentum, slots 0 v, 1 mom, 2 a.  v = rho v + (1-rho) g^2; NIF_OPT_CENTERED: a = rho a +
+ *                      (1-rho) g, d = v - a^2 + eps, else d = v + eps; inc = lr g / sqrt(d); momentum > 0: mom = momentum mom + inc,
+ *                      theta -= mom, else theta -= inc
+ *   NIF_OPT_ADAGRAD    slot 0 acc, which starts at init_acc (Keras' initial_accumulator_value, default 0.1): written into the slot when
+ *                      the kind first runs on a context whose slots are fresh (created, or nif_set_opt_state with all-zero slots and
+ *                      step 0).  acc += g^2; theta -= lr g / sqrt(acc + eps)
+ *   NIF_OPT_ADAMAX     slots 0 m, 1 u.  m += (g - m)(1-b1); u = max(b2 u, |g|); theta -= (lr / (1 - b1^t)) m / (u + eps)
+ *   NIF_OPT_ADAM with NIF_OPT_AMSGRAD: vhat = max(vhat, v) in slot 2, the update divides by sqrt(vhat) + eps
+ *   NIF_OPT_ADAM with NIF_OPT_DECOUPLED_WD (AdamW): theta -= lr weight_decay theta first (lr without the bias corrections), then Adam's
+ *                      update, with or without amsgrad
+ * Learning-rate schedule (tf.keras.optimizers.schedules.*, any kind): `sched` = a NIF_SCHED_* kind | flag bits, evaluated in fp64 at
+ * Keras' step = t - 1 and rounded to float once; it replaces lr, so `decay` must be zero with it.  p = step / decay_steps,
+ * q = min(step, decay_steps) / decay_steps:
+ *   NIF_SCHED_EXPONENTIAL   lr sched_a^p            (sched_a = decay_rate; NIF_SCHED_STAIRCASE: floor(p))
+ *   NIF_SCHED_INVERSE_TIME  lr / (1 + sched_a p)    (likewise)
+ *   NIF_SCHED_COSINE        lr ((1 - sched_a) 0.5 (1 + cos(pi q)) + sched_a)                            (sched_a = alpha)
+ *   NIF_SCHED_POLYNOMIAL    (lr - sched_a) (1 - q)^sched_b + sched_a   (sched_a = end_learning_rate, sched_b = power;
+ *                           NIF_SCHED_CYCLE: decay_steps max(1, ceil(step / decay_steps)) takes the place of decay_steps)
  * The per-step scalars (learning rate, both bias corrections, r_t, the branch) are formed once per step in fp64: on the host for an
- * eager step, per block from device memory inside a captured graph. */
-typedef enum { NIF_OPT_ADAM = 0, NIF_OPT_LION = 1, NIF_OPT_ADABELIEF = 2 } nif_opt_kind;
+ * eager step, per block from device memory inside a captured graph (so a captured epoch follows a schedule step by step). */
+typedef enum { NIF_OPT_ADAM = 0, NIF_OPT_LION = 1, NIF_OPT_ADABELIEF = 2, NIF_OPT_SGD = 3, NIF_OPT_RMSPROP = 4, NIF_OPT_ADAGRAD = 5,
+               NIF_OPT_ADAMAX = 6 } nif_opt_kind;
 #define NIF_OPT_RECTIFY 1      /* AdaBelief rectify=True (the reference's default) */
-#define NIF_OPT_AMSGRAD 2      /* AdaBelief amsgrad=True: the third slot vhat, allocated on first use */
-typedef struct {               /* 72 bytes; reserved fields must be zero */
+#define NIF_OPT_AMSGRAD 2      /* AdaBelief, Adam amsgrad=True: the third slot vhat, allocated on first use */
+#define NIF_OPT_NESTEROV 4     /* SGD nesterov=True */
+#define NIF_OPT_CENTERED 8     /* RMSprop centered=True: the third slot a, allocated on first use */
+#define NIF_OPT_DECOUPLED_WD 16 /* Adam: AdamW's decoupled weight decay by `weight_decay` */
+#define NIF_SCHED_NONE 0
+#define NIF_SCHED_EXPONENTIAL 1
+#define NIF_SCHED_INVERSE_TIME 2
+#define NIF_SCHED_COSINE 3
+#define NIF_SCHED_POLYNOMIAL 4
+#define NIF_SCHED_STAIRCASE 0x100
+#define NIF_SCHED_CYCLE 0x200
+typedef struct {               /* 72 bytes; all-zero sched, decay_steps, sched_a, sched_b, init_acc: no schedule, no Adagrad fill */
   int32_t kind, flags;         /* nif_opt_kind, NIF_OPT_* bits */
-  float lr, beta1, beta2, eps; /* Lion: eps unused */
-  float weight_decay;          /* Lion `wd`, AdaBelief `weight_decay` */
-  float decay;                 /* Keras legacy `decay` keyword */
+  float lr, beta1, beta2, eps; /* Lion: eps unused; SGD: beta1 = momentum; RMSprop: beta1 = momentum, beta2 = rho */
+  float weight_decay;          /* Lion `wd`, AdaBelief `weight_decay`, AdamW `weight_decay` */
+  float decay;                 /* Keras legacy `decay` keyword (Lion, AdaBelief) */
   float sma_threshold, warmup_proportion, min_lr;
-  int32_t reserved0;
+  int32_t sched;               /* NIF_SCHED_* kind | NIF_SCHED_STAIRCASE / NIF_SCHED_CYCLE; 0 = a constant learning rate */
   int64_t total_steps;         /* AdaBelief warm-up / decay horizon; 0 = off */
-  int32_t reserved[4];
+  int32_t decay_steps;         /* the schedule's decay_steps (> 0 with a schedule) */
+  float sched_a, sched_b;      /* the schedule's constants, see above */
+  float init_acc;              /* Adagrad initial_accumulator_value */
 } nif_opt;
 /* optimizer.apply_gradients with any kind on nif_grad_dev() (the fused-tail form under the same conditions as nif_adam_step_dev).
  * nif_train_step and nif_train_step_multi stay Adam-only. */
 int nif_opt_step_dev(nif_ctx* ctx, const nif_opt* opt);
-/* nif_graph_launch for a graph whose steps were recorded by nif_opt_step_dev: NIF_ERR_INVALID when opt's kind or amsgrad flag is not
- * the recorded one.  A capture that mixes kinds fails at the step that mixes them (NIF_ERR_STATE); nif_graph_launch refuses a graph
+/* nif_graph_launch for a graph whose steps were recorded by nif_opt_step_dev: NIF_ERR_INVALID when opt's kind or one of its
+ * slot-shaping flags (NIF_OPT_AMSGRAD, NIF_OPT_CENTERED, NIF_OPT_DECOUPLED_WD) is not the recorded one.  A capture that mixes kinds fails at the step that mixes them (NIF_ERR_STATE); nif_graph_launch refuses a graph
  * recorded with non-Adam steps (NIF_ERR_STATE). */
 int nif_graph_launch_opt(nif_ctx* ctx, int32_t graph_id, const nif_opt* opt);
-/* optimizer slots for checkpoints: slot 0 m, 1 v, 2 vhat (reads zeros before vhat exists; a write allocates it) */
+/* optimizer slots for checkpoints: slot 0 m, 1 v, 2 vhat (reads zeros before vhat exists; a write allocates it); the Keras kinds'
+ * slots are listed at nif_opt_kind */
 int nif_get_opt_slot(nif_ctx* ctx, int32_t slot, float* host, int64_t n);
 int nif_set_opt_slot(nif_ctx* ctx, int32_t slot, const float* host, int64_t n);
 /* the per-step scalars of iteration t (>= 1) as the kernels receive them, in fp64 (host-only, no context):
- * out[0] learning rate, out[1] 1 - b1^t, out[2] 1 - b2^t, out[3] r_t, out[4] 1 when the update divides by (v_hat + eps), else 0
- * (AdaBelief's momentum branch); Lion fills out[0] only */
+ * out[0] learning rate (the schedule's when there is one, for every kind), out[1] 1 - b1^t, out[2] 1 - b2^t, out[3] r_t, out[4] 1 when
+ * the update divides by (v_hat + eps), else 0 (AdaBelief's momentum branch); Lion fills out[0] only */
 int nif_opt_scalars(const nif_opt* opt, int64_t t, double* out5);
 /* Gradient transform in front of the update of every optimizer step of the context (k_gradtf.hip): the reference's
  * centralized_gradients_for_optimizer (nif/optimizers/gtcf.py:7-67) and Keras' clipnorm / clipvalue / global_clipnorm.  A tensor is one

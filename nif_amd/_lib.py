@@ -55,15 +55,19 @@ class nif_adam(C.Structure):
 
 
 OPT_ADAM, OPT_LION, OPT_ADABELIEF = 0, 1, 2
+OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADAMAX = 3, 4, 5, 6
 OPT_RECTIFY, OPT_AMSGRAD = 1, 2
+OPT_NESTEROV, OPT_CENTERED, OPT_DECOUPLED_WD = 4, 8, 16
+SCHED_NONE, SCHED_EXPONENTIAL, SCHED_INVERSE_TIME, SCHED_COSINE, SCHED_POLYNOMIAL = 0, 1, 2, 3, 4
+SCHED_STAIRCASE, SCHED_CYCLE = 0x100, 0x200
 
 
 class nif_opt(C.Structure):
     _fields_ = [
         ("kind", C.c_int32), ("flags", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
         ("eps", C.c_float), ("weight_decay", C.c_float), ("decay", C.c_float), ("sma_threshold", C.c_float),
-        ("warmup_proportion", C.c_float), ("min_lr", C.c_float), ("reserved0", C.c_int32), ("total_steps", C.c_int64),
-        ("reserved", C.c_int32 * 4),
+        ("warmup_proportion", C.c_float), ("min_lr", C.c_float), ("sched", C.c_int32), ("total_steps", C.c_int64),
+        ("decay_steps", C.c_int32), ("sched_a", C.c_float), ("sched_b", C.c_float), ("init_acc", C.c_float),
     ]
 
 

@@ -31,6 +31,10 @@ class LearningRateScheduler(Callback):
 
     def on_epoch_begin(self, epoch, logs=None):
         opt = self.model.optimizer
+        if getattr(opt, "has_schedule", False):
+            # Keras: "optimizer was created with a LearningRateSchedule object as its learning_rate: cannot set a value on it"
+            raise TypeError("LearningRateScheduler: the optimizer's learning_rate is a %s schedule object, a value cannot be set on it "
+                            "(as in Keras); compile with a numeric learning_rate to use this callback" % type(opt.learning_rate).__name__)
         lr = float(self.schedule(epoch, opt.learning_rate))
         opt.learning_rate = lr
         if self.verbose:

@@ -1,16 +1,18 @@
-// k_opt.hip -- the optimizer updates on the flat parameter vector (gfx950): Keras-2.11 Adam (SURVEY a-11) and the reference's Lion and
-// AdaBelief (nif/optimizers/external_optimizers.py:631-735, :322-628), and the fixed-order row reduction of the gradient (k_reduce), which
-// the fused forms share.  Three forms of each update, each one template over (kind, amsgrad):
+// k_opt.hip -- the optimizer updates on the flat parameter vector (gfx950): Keras-2.11 Adam (SURVEY a-11), the reference's Lion and
+// AdaBelief (nif/optimizers/external_optimizers.py:631-735, :322-628), Keras 2.11's SGD, RMSprop, Adagrad, Adamax, AdamW and amsgrad Adam
+// (formulas restated from Keras 2.11, not pinned by TensorFlow), and the fixed-order row reduction of the gradient (k_reduce), which
+// the fused forms share.  Three forms of each update, each one template over (kind, third slot: amsgrad's vhat / centered RMSprop's mean):
 //   * k_opt: the update alone over [0, P), behind an all-reduce, a regulariser or a flushed row reduction.  A stream bound by bandwidth:
 //     Adam reads theta, g, m, v (16 B) and writes theta, m, v (12 B) per parameter; Lion 12 B / 8 B; AdaBelief as Adam, with amsgrad
-//     20 B / 16 B.  Lion and AdaBelief four parameters per thread with 16-byte accesses where every buffer is 16-byte aligned, a
-//     scalar tail for P % 4; Adam one parameter per thread (stream_shape).
+//     20 B / 16 B; SGD and Adagrad 12 B / 8 B (slot 0 only), Adamax and RMSprop as Adam (centered RMSprop, amsgrad Adam and AdamW
+//     20 B / 16 B).  Every kind but plain Adam four parameters per thread with 16-byte accesses where every buffer is 16-byte
+//     aligned, a scalar tail for P % 4; plain Adam one parameter per thread (stream_shape).
 //   * k_reduce_opt: k_reduce's row sum of column i (same summation order), g[i] and the loss g[P] still written, then the update of
 //     column i behind its sum -- bit-identical to k_reduce followed by the standalone update.
 //   * k_opt_dev: hyper-parameters and iteration count from device memory (OptDev) for captured graphs; each block forms the step's
 //     scalars in fp64 (opt_scalars / opt_args, the host's own functions), k_opt_step_inc bumps the count behind the update.
-// Every form runs the same per-element expressions (adam_1 / lion_1 / adab_1) with contraction off, so that the update is the same float
-// sequence whichever form ran it; Adam's one fused multiply-add is written out.
+// Every form runs the same per-element expressions (adam_1 / lion_1 / adab_1 / sgd_1 / rmsprop_1 / adagrad_1 / adamax_1 / adam_ams_1)
+// with contraction off, so that the update is the same float sequence whichever form ran it; Adam's one fused multiply-add is written out.
 #include "nif_internal.h"
 
 #pragma clang fp contract(off)
@@ -51,18 +53,75 @@ __device__ __forceinline__ void adab_1(float& th, float g, float& m, float& v, f
   th = th - a.lr * u;
 }
 
-// one parameter of any kind: Adam slots m, v; Lion m; AdaBelief m, v (+ vhat with AMS)
+// Adam with amsgrad (Keras 2.11): adam_1's m and v, vhat = max(vhat, v), theta -= lr_t m / (sqrt(vhat) + eps)
+__device__ __forceinline__ void adam_ams_1(float& th, float g, float& m, float& v, float& vh, const OptArgs& a) {
+  m = m + (g - m) * (1.0f - a.b1);
+  v = fmaf(g * g - v, 1.0f - a.b2, v);
+  vh = vh >= v ? vh : v;
+  th = th - a.lr * m / (sqrtf(vh) + a.eps);
+}
+
+// SGD (Keras 2.11): theta -= lr g; with momentum m = momentum m - lr g and theta += m, nesterov theta += momentum m - lr g (the new m)
+__device__ __forceinline__ void sgd_1(float& th, float g, float& m, const OptArgs& a) {
+  const float s = a.lr * g;
+  if (a.div == 0) { th = th - s; return; }
+  m = a.b1 * m - s;
+  th = a.div == 2 ? th + (a.b1 * m - s) : th + m;
+}
+
+// RMSprop (Keras 2.11), slots v, mom, a: v = rho v + (1-rho) g^2; centered: a = rho a + (1-rho) g, d = v - a^2 + eps, else d = v + eps;
+// inc = lr g / sqrt(d); with momentum mom = momentum mom + inc, theta -= mom, else theta -= inc
+template <bool CENTERED>
+__device__ __forceinline__ void rmsprop_1(float& th, float g, float& v, float& mom, float& av, const OptArgs& a) {
+  v = a.b2 * v + (1.0f - a.b2) * (g * g);
+  float d = v;
+  if (CENTERED) { av = a.b2 * av + (1.0f - a.b2) * g; d = v - av * av; }
+  d = d + a.eps;
+  const float inc = a.lr * g / sqrtf(d);
+  if (a.div) { mom = a.b1 * mom + inc; th = th - mom; }
+  else th = th - inc;
+}
+
+// Adagrad (Keras 2.11): acc += g^2 (acc starts at initial_accumulator_value); theta -= lr g / sqrt(acc + eps)
+__device__ __forceinline__ void adagrad_1(float& th, float g, float& acc, const OptArgs& a) {
+  acc = acc + g * g;
+  th = th - a.lr * g / sqrtf(acc + a.eps);
+}
+
+// Adamax (Keras 2.11): m += (g - m)(1-b1); u = max(b2 u, |g|); theta -= (lr / (1 - b1^t)) m / (u + eps)   (a.lr carries the correction)
+__device__ __forceinline__ void adamax_1(float& th, float g, float& m, float& u, const OptArgs& a) {
+  m = m + (g - m) * (1.0f - a.b1);
+  u = fmaxf(a.b2 * u, fabsf(g));
+  th = th - a.lr * m / (u + a.eps);
+}
+
+// the kinds with a second slot (Adam v, AdaBelief v, RMSprop mom, Adamax u); slot 0 is every kind's
+template <int KIND> struct Slots { static constexpr bool second = KIND != OPT_LION && KIND != OPT_SGD && KIND != OPT_ADAGRAD; };
+
+// one parameter of any kind: slots (m, v, vh) are Adam / AdaBelief m, v, vhat; Lion, SGD m; RMSprop v, mom, a; Adagrad acc; Adamax m, u.
+// AMS: the third slot is in use.  AdamW: theta -= lr wd theta with the step's learning rate (no bias correction), then Adam
 template <int KIND, bool AMS>
 __device__ __forceinline__ void opt_1(float& th, float g, float& m, float& v, float& vh, const OptArgs& a) {
-  if (KIND == OPT_ADAM) adam_1(th, g, m, v, a);
+  if (KIND == OPT_ADAM && !AMS) adam_1(th, g, m, v, a);
+  else if (KIND == OPT_ADAM) adam_ams_1(th, g, m, v, vh, a);
   else if (KIND == OPT_LION) lion_1(th, g, m, a);
-  else adab_1<AMS>(th, g, m, v, vh, a);
+  else if (KIND == OPT_ADABELIEF) adab_1<AMS>(th, g, m, v, vh, a);
+  else if (KIND == OPT_SGD) sgd_1(th, g, m, a);
+  else if (KIND == OPT_RMSPROP) rmsprop_1<AMS>(th, g, m, v, vh, a);
+  else if (KIND == OPT_ADAGRAD) adagrad_1(th, g, m, a);
+  else if (KIND == OPT_ADAMAX) adamax_1(th, g, m, v, a);
+  else {
+    th = th - a.lr0 * a.wd * th;
+    if (AMS) adam_ams_1(th, g, m, v, vh, a);
+    else adam_1(th, g, m, v, a);
+  }
 }
 
 // n4 = P / 4 when every buffer is 16-byte aligned, else 0 (all scalar)
 template <int KIND, bool AMS>
 __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
                                            float* __restrict__ v, float* __restrict__ vh, long P, long n4, const OptArgs& a) {
+  constexpr bool S1 = Slots<KIND>::second;
   const long stride = (long)gridDim.x * blockDim.x;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (long q = tid; q < n4; q += stride) {
@@ -70,7 +129,7 @@ __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const floa
     const f32x4 g4 = reinterpret_cast<const f32x4*>(g)[q];
     f32x4 m4 = reinterpret_cast<const f32x4*>(m)[q];
     f32x4 v4 = {0.f, 0.f, 0.f, 0.f}, h4 = {0.f, 0.f, 0.f, 0.f};
-    if (KIND != OPT_LION) v4 = reinterpret_cast<const f32x4*>(v)[q];
+    if (S1) v4 = reinterpret_cast<const f32x4*>(v)[q];
     if (AMS) h4 = reinterpret_cast<const f32x4*>(vh)[q];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -80,16 +139,16 @@ __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const floa
     }
     reinterpret_cast<f32x4*>(theta)[q] = t4;
     reinterpret_cast<f32x4*>(m)[q] = m4;
-    if (KIND != OPT_LION) reinterpret_cast<f32x4*>(v)[q] = v4;
+    if (S1) reinterpret_cast<f32x4*>(v)[q] = v4;
     if (AMS) reinterpret_cast<f32x4*>(vh)[q] = h4;
   }
   for (long i = 4 * n4 + tid; i < P; i += stride) {
     float tj = theta[i], mj = m[i], vj = 0.f, hj = 0.f;
-    if (KIND != OPT_LION) vj = v[i];
+    if (S1) vj = v[i];
     if (AMS) hj = vh[i];
     opt_1<KIND, AMS>(tj, g[i], mj, vj, hj, a);
     theta[i] = tj; m[i] = mj;
-    if (KIND != OPT_LION) v[i] = vj;
+    if (S1) v[i] = vj;
     if (AMS) vh[i] = hj;
   }
 }
@@ -134,7 +193,7 @@ __device__ __forceinline__ OptArgs block_args(const OptDev* __restrict__ od) {
   __shared__ OptArgs sa;
   if (threadIdx.x == 0) {
     OptDev o = *od;
-    o.kind = KIND;
+    o.kind = KIND == OPT_ADAMW ? OPT_ADAM : KIND;
     sa = opt_args(o, opt_scalars(o, o.step + 1));
   }
   __syncthreads();
@@ -179,10 +238,10 @@ __global__ __launch_bounds__(512) void k_reduce_opt(const float* __restrict__ pa
   const float gi = reduce_col(partial, pstride, rows, red, col, rg, i, P);
   if (rg == 0 && i < P) {
     g[i] = gi;
-    float th = theta[i], mi = m[i], vi = KIND != OPT_LION ? v[i] : 0.f, hi = AMS ? vh[i] : 0.f;
+    float th = theta[i], mi = m[i], vi = Slots<KIND>::second ? v[i] : 0.f, hi = AMS ? vh[i] : 0.f;
     opt_1<KIND, AMS>(th, gi, mi, vi, hi, a);
     theta[i] = th; m[i] = mi;
-    if (KIND != OPT_LION) v[i] = vi;
+    if (Slots<KIND>::second) v[i] = vi;
     if (AMS) vh[i] = hi;
   }
   if (blockIdx.x == gridDim.x - 1) reduce_loss(lossp, nloss, red, col, rg, g + P);
@@ -196,11 +255,11 @@ void launch_reduce(const float* partial, long pstride, int rows, const float* lo
 
 static bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
 // n4 and the grid of a stream over P parameters (v, vh: nullptr where the kind does not use them): at most 2048 blocks of 256 threads,
-// the rest grid-strided.  Adam runs one parameter per thread (n4 = 0), the shape of its earlier kernels: four per thread serialise
-// four divisions and square roots, and made the captured configs[0] step (P = 6 627, 7 blocks instead of 26) 0.5 us slower
+// the rest grid-strided.  Adam without amsgrad runs one parameter per thread (n4 = 0), the shape of its earlier kernels: four per thread
+// serialise four divisions and square roots, and made the captured configs[0] step (P = 6 627, 7 blocks instead of 26) 0.5 us slower
 static void stream_shape(int kind, const float* theta, const float* g, const float* m, const float* v, const float* vh, long P,
                          long* n4, dim3* grid) {
-  *n4 = (kind != OPT_ADAM && al16(theta) && al16(g) && al16(m) && al16(v) && al16(vh)) ? P / 4 : 0;
+  *n4 = (!(kind == OPT_ADAM && vh == nullptr) && al16(theta) && al16(g) && al16(m) && al16(v) && al16(vh)) ? P / 4 : 0;
   const long work = *n4 > 0 ? *n4 : P;
   long blocks = (work + 255) / 256;
   if (blocks > 2048) blocks = 2048;
@@ -208,42 +267,51 @@ static void stream_shape(int kind, const float* theta, const float* g, const flo
   *grid = dim3((unsigned)blocks);
 }
 
-// kind OPT_*, ams: AdaBelief's amsgrad.  The slots a kind does not use are not touched (v for Lion, vhat without amsgrad: may be null)
+// the instantiation of (kernel kind, third slot): X(KIND, AMS) is expanded with compile-time arguments
+#define OPT_DISPATCH(kind, ams, X)                                                    \
+  switch (kind) {                                                                     \
+    case OPT_ADAM: if (ams) { X(OPT_ADAM, true); } else { X(OPT_ADAM, false); } break; \
+    case OPT_LION: X(OPT_LION, false); break;                                         \
+    case OPT_ADABELIEF: if (ams) { X(OPT_ADABELIEF, true); } else { X(OPT_ADABELIEF, false); } break; \
+    case OPT_SGD: X(OPT_SGD, false); break;                                           \
+    case OPT_RMSPROP: if (ams) { X(OPT_RMSPROP, true); } else { X(OPT_RMSPROP, false); } break; \
+    case OPT_ADAGRAD: X(OPT_ADAGRAD, false); break;                                   \
+    case OPT_ADAMAX: X(OPT_ADAMAX, false); break;                                     \
+    default: if (ams) { X(OPT_ADAMW, true); } else { X(OPT_ADAMW, false); } break;     \
+  }
+static bool second_slot(int kind) { return kind != OPT_LION && kind != OPT_SGD && kind != OPT_ADAGRAD; }
+
+// kind: the kernel kind (kernel_kind: OPT_* with OPT_ADAMW), ams: the third slot is in use (third_slot).  The slots a kind does not use
+// are not touched (may be null)
 void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, const OptArgs& a,
                 hipStream_t st) {
-  if (kind == OPT_LION) v = nullptr;
+  if (!second_slot(kind)) v = nullptr;
   if (!ams) vhat = nullptr;
   long n4; dim3 grid;
   stream_shape(kind, theta, g, m, v, vhat, P, &n4, &grid);
-  if (kind == OPT_ADAM) hipLaunchKernelGGL((k_opt<OPT_ADAM, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
-  else if (kind == OPT_LION) hipLaunchKernelGGL((k_opt<OPT_LION, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
-  else if (ams) hipLaunchKernelGGL((k_opt<OPT_ADABELIEF, true>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
-  else hipLaunchKernelGGL((k_opt<OPT_ADABELIEF, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a);
+#define X(K, A) hipLaunchKernelGGL((k_opt<K, A>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a)
+  OPT_DISPATCH(kind, ams, X)
+#undef X
 }
 
 void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g,
                        long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)((P + 63) / 64)), block(512);
-  if (kind == OPT_ADAM)
-    hipLaunchKernelGGL((k_reduce_opt<OPT_ADAM, false>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
-  else if (kind == OPT_LION)
-    hipLaunchKernelGGL((k_reduce_opt<OPT_LION, false>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
-  else if (ams)
-    hipLaunchKernelGGL((k_reduce_opt<OPT_ADABELIEF, true>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
-  else
-    hipLaunchKernelGGL((k_reduce_opt<OPT_ADABELIEF, false>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a);
+#define X(K, A) \
+  hipLaunchKernelGGL((k_reduce_opt<K, A>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a)
+  OPT_DISPATCH(kind, ams, X)
+#undef X
 }
 
 void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
                     hipStream_t st) {
-  if (kind == OPT_LION) v = nullptr;
+  if (!second_slot(kind)) v = nullptr;
   if (!ams) vhat = nullptr;
   long n4; dim3 grid;
   stream_shape(kind, theta, g, m, v, vhat, P, &n4, &grid);
   const OptDev* o = od;
-  if (kind == OPT_ADAM) hipLaunchKernelGGL((k_opt_dev<OPT_ADAM, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
-  else if (kind == OPT_LION) hipLaunchKernelGGL((k_opt_dev<OPT_LION, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
-  else if (ams) hipLaunchKernelGGL((k_opt_dev<OPT_ADABELIEF, true>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
-  else hipLaunchKernelGGL((k_opt_dev<OPT_ADABELIEF, false>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o);
+#define X(K, A) hipLaunchKernelGGL((k_opt_dev<K, A>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o)
+  OPT_DISPATCH(kind, ams, X)
+#undef X
   hipLaunchKernelGGL(k_opt_step_inc, dim3(1), dim3(1), 0, st, od);
 }

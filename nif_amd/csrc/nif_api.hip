@@ -274,6 +274,9 @@ extern "C" int nif_set_opt_state(nif_ctx* c, const float* mh, const float* vh, i
   HIPCHK(hipMemcpyAsync(c->v, vh, sizeof(float) * n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   c->step = step;
+  // fresh slots (Adagrad's accumulator is still to be initialised): iteration 0 and nothing but zeros, what compile() of a new optimizer writes
+  c->slots_fresh = step == 0;
+  for (int64_t i = 0; i < n && c->slots_fresh; ++i) c->slots_fresh = mh[i] == 0.f && vh[i] == 0.f;
   return NIF_OK;
 }
 
@@ -2122,14 +2125,38 @@ extern "C" int nif_grad_norms(nif_ctx* c, float* per_tensor, int32_t n, float* g
 
 // ---- optimizer steps (include/nif_hip.h nif_adam_step_dev, nif_opt_step_dev; reference nif/optimizers/external_optimizers.py:322-735) ----
 static int opt_check(const nif_opt* o) {
-  if (o->kind < NIF_OPT_ADAM || o->kind > NIF_OPT_ADABELIEF) return fail(NIF_ERR_INVALID, "nif_opt: kind must be NIF_OPT_ADAM, _LION or _ADABELIEF");
-  if (o->reserved0 || o->reserved[0] || o->reserved[1] || o->reserved[2] || o->reserved[3]) return fail(NIF_ERR_INVALID, "nif_opt: reserved fields must be zero");
-  if (o->flags & ~(NIF_OPT_RECTIFY | NIF_OPT_AMSGRAD)) return fail(NIF_ERR_INVALID, "nif_opt: unknown flag bits");
-  if (o->kind != NIF_OPT_ADABELIEF && (o->flags || o->total_steps || o->sma_threshold != 0.f || o->warmup_proportion != 0.f || o->min_lr != 0.f))
+  if (o->kind < NIF_OPT_ADAM || o->kind > NIF_OPT_ADAMAX)
+    return fail(NIF_ERR_INVALID, "nif_opt: kind must be NIF_OPT_ADAM, _LION, _ADABELIEF, _SGD, _RMSPROP, _ADAGRAD or _ADAMAX");
+  const int allowed = o->kind == NIF_OPT_ADAM ? (NIF_OPT_AMSGRAD | NIF_OPT_DECOUPLED_WD) : o->kind == NIF_OPT_ADABELIEF ? (NIF_OPT_RECTIFY | NIF_OPT_AMSGRAD)
+                    : o->kind == NIF_OPT_SGD ? NIF_OPT_NESTEROV : o->kind == NIF_OPT_RMSPROP ? NIF_OPT_CENTERED : 0;
+  if (o->flags & ~(NIF_OPT_RECTIFY | NIF_OPT_AMSGRAD | NIF_OPT_NESTEROV | NIF_OPT_CENTERED | NIF_OPT_DECOUPLED_WD))
+    return fail(NIF_ERR_INVALID, "nif_opt: unknown flag bits");
+  if (o->flags & ~allowed)
+    return fail(NIF_ERR_INVALID, "nif_opt: a flag of another kind (RECTIFY: AdaBelief; AMSGRAD: AdaBelief, Adam; NESTEROV: SGD; CENTERED: RMSprop; DECOUPLED_WD: Adam)");
+  if (o->kind != NIF_OPT_ADABELIEF && (o->total_steps || o->sma_threshold != 0.f || o->warmup_proportion != 0.f || o->min_lr != 0.f))
     return fail(NIF_ERR_INVALID, "nif_opt: flags, sma_threshold, total_steps, warmup_proportion and min_lr are AdaBelief's");
-  if (o->kind == NIF_OPT_ADAM && (o->decay != 0.f || o->weight_decay != 0.f))
-    return fail(NIF_ERR_INVALID, "nif_opt: Adam has no decay / weight_decay on this path (nif_adam)");
+  if (o->kind == NIF_OPT_ADAM && (o->decay != 0.f || (o->weight_decay != 0.f && !(o->flags & NIF_OPT_DECOUPLED_WD))))
+    return fail(NIF_ERR_INVALID, "nif_opt: Adam has no decay / weight_decay on this path (nif_adam); weight_decay needs NIF_OPT_DECOUPLED_WD");
+  if (o->kind >= NIF_OPT_SGD && (o->decay != 0.f || o->weight_decay != 0.f))
+    return fail(NIF_ERR_INVALID, "nif_opt: SGD, RMSprop, Adagrad and Adamax have no decay / weight_decay");
+  if (o->kind == NIF_OPT_SGD && (o->beta2 != 0.f || o->eps != 0.f || !(o->beta1 >= 0.f && o->beta1 <= 1.f)))
+    return fail(NIF_ERR_INVALID, "nif_opt: SGD takes momentum in beta1, within [0, 1]; beta2 and eps must be zero");
+  if (o->kind == NIF_OPT_RMSPROP && !(o->beta1 >= 0.f && o->beta1 <= 1.f))
+    return fail(NIF_ERR_INVALID, "nif_opt: RMSprop takes momentum in beta1, within [0, 1]");
+  if (o->kind == NIF_OPT_ADAGRAD ? !(o->init_acc >= 0.f) : o->init_acc != 0.f)
+    return fail(NIF_ERR_INVALID, "nif_opt: init_acc is Adagrad's, >= 0");
   if (o->total_steps < 0) return fail(NIF_ERR_INVALID, "nif_opt: total_steps < 0");
+  const int sk = o->sched & 0xff, sf = o->sched & ~0xff;
+  if (sk > NIF_SCHED_POLYNOMIAL || o->sched < 0 || (sf & ~(NIF_SCHED_STAIRCASE | NIF_SCHED_CYCLE)))
+    return fail(NIF_ERR_INVALID, "nif_opt: sched must be a NIF_SCHED_* kind with NIF_SCHED_STAIRCASE / NIF_SCHED_CYCLE");
+  if ((sf & NIF_SCHED_STAIRCASE) && sk != NIF_SCHED_EXPONENTIAL && sk != NIF_SCHED_INVERSE_TIME)
+    return fail(NIF_ERR_INVALID, "nif_opt: NIF_SCHED_STAIRCASE is ExponentialDecay's and InverseTimeDecay's");
+  if ((sf & NIF_SCHED_CYCLE) && sk != NIF_SCHED_POLYNOMIAL) return fail(NIF_ERR_INVALID, "nif_opt: NIF_SCHED_CYCLE is PolynomialDecay's");
+  if (sk == NIF_SCHED_NONE && (sf || o->decay_steps || o->sched_a != 0.f || o->sched_b != 0.f))
+    return fail(NIF_ERR_INVALID, "nif_opt: decay_steps, sched_a and sched_b must be zero without a schedule");
+  if (sk != NIF_SCHED_NONE && o->decay_steps <= 0) return fail(NIF_ERR_INVALID, "nif_opt: a schedule needs decay_steps > 0");
+  if (sk != NIF_SCHED_NONE && o->decay != 0.f) return fail(NIF_ERR_INVALID, "nif_opt: the legacy decay and a schedule exclude each other");
+  if (sk != NIF_SCHED_POLYNOMIAL && o->sched_b != 0.f) return fail(NIF_ERR_INVALID, "nif_opt: sched_b is PolynomialDecay's power");
   return NIF_OK;
 }
 static OptDev opt_dev_of(const nif_opt* o, long step) {
@@ -2137,12 +2164,24 @@ static OptDev opt_dev_of(const nif_opt* o, long step) {
   d.kind = o->kind; d.flags = o->flags; d.lr = o->lr; d.beta1 = o->beta1; d.beta2 = o->beta2; d.eps = o->eps; d.wd = o->weight_decay;
   d.decay = o->decay; d.sma_threshold = o->sma_threshold; d.warmup_proportion = o->warmup_proportion; d.min_lr = o->min_lr;
   d.total_steps = (long)o->total_steps; d.step = step;
+  d.sched = o->sched; d.decay_steps = o->decay_steps; d.sched_a = o->sched_a; d.sched_b = o->sched_b;
   return d;
 }
-static bool opt_ams(const nif_opt* o) { return o->kind == NIF_OPT_ADABELIEF && (o->flags & NIF_OPT_AMSGRAD); }
+// the kernel instantiation of a nif_opt and whether it uses the third slot: what a captured graph is tied to
+static int opt_kk(const nif_opt* o) { return kernel_kind(o->kind, o->flags); }
+static bool opt_ams(const nif_opt* o) { return third_slot(o->kind, o->flags); }
+// Adagrad's accumulator starts at initial_accumulator_value: written when the kind first runs on fresh slots (not part of a capture:
+// a replay would write it again)
+static int adagrad_fill(nif_ctx* c, float value) {
+  if (c->capturing) return fail(NIF_ERR_STATE, "Adagrad's accumulator is not initialised yet: run one eager step or nif_set_opt_state before the capture");
+  const std::vector<float> acc((size_t)c->P, value);
+  HIPCHK(hipMemcpyAsync(c->m, acc.data(), sizeof(float) * (size_t)c->P, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
 static int ensure_vhat(nif_ctx* c) {
   if (c->vhat) return NIF_OK;
-  if (c->capturing) return fail(NIF_ERR_STATE, "AMSGrad's vhat slot does not exist yet: run one eager step or nif_set_opt_slot(2, ...) before the capture");
+  if (c->capturing) return fail(NIF_ERR_STATE, "the third slot (AMSGrad's vhat, centered RMSprop's a) does not exist yet: run one eager step or nif_set_opt_slot(2, ...) before the capture");
   DevBuf<float> vh;
   const int rc = vh.alloc(c->P); if (rc) return rc;
   HIPCHK(hipMemsetAsync(vh, 0, sizeof(float) * (size_t)c->P, c->st));
@@ -2170,10 +2209,13 @@ static void theta_stepped(nif_ctx* c) {
 static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
   const bool ams = opt_ams(opt);
-  if (c->capturing && c->cap_kind >= 0 && (c->cap_kind != opt->kind || c->cap_ams != ams))
+  const int kk = opt_kk(opt);
+  if (c->capturing && c->cap_kind >= 0 && (c->cap_kind != kk || c->cap_ams != ams))
     return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
   HIPCHK(hipSetDevice(c->dev));
   if (ams) { const int rc = ensure_vhat(c); if (rc) return rc; }
+  if (opt->kind == NIF_OPT_ADAGRAD && c->slots_fresh && opt->init_acc != 0.f) { const int rc = adagrad_fill(c, opt->init_acc); if (rc) return rc; }
+  c->slots_fresh = false;
   // the step's row reduction and the update in ONE launch -- not with a gradient transform set: a norm needs every column of the
   // gradient before any parameter moves
   const bool fused = c->tail_pending && !c->capturing && !c->gt_on && tail_can_defer(c);
@@ -2188,14 +2230,14 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
   const OptDev d = opt_dev_of(opt, c->step - 1);
   const OptArgs a = opt_args(d, opt_scalars(d, c->step));
   if (fused) {
-    launch_reduce_opt(opt->kind, ams, c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m,
+    launch_reduce_opt(kk, ams, c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m,
                       c->v, c->vhat, a, c->st);
   } else if (c->capturing) {
-    launch_opt_dev(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, c->opt_dev, c->st);
-    c->cap_steps += 1; c->cap_kind = opt->kind; c->cap_ams = ams;
+    launch_opt_dev(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, c->opt_dev, c->st);
+    c->cap_steps += 1; c->cap_kind = kk; c->cap_ams = ams;
   } else {
     ProfScope p_(c, NIF_PROF_ADAM);
-    launch_opt(opt->kind, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, a, c->st);
+    launch_opt(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, a, c->st);
   }
   HIPCHK(hipGetLastError());
   theta_stepped(c);
@@ -2236,8 +2278,8 @@ static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const 
 static bool graph_ok(const nif_ctx* c, int32_t graph_id) { return graph_id >= 0 && graph_id < (int32_t)c->graphs.size() && c->graphs[graph_id]; }
 extern "C" int nif_graph_launch(nif_ctx* c, int32_t graph_id, const nif_adam* opt) {
   if (!c || !opt || !graph_ok(c, graph_id)) return fail(NIF_ERR_INVALID, "bad argument");
-  if (c->graph_kind[graph_id] > OPT_ADAM)
-    return fail(NIF_ERR_STATE, "nif_graph_launch: the graph holds Lion / AdaBelief steps (nif_graph_launch_opt with that optimizer)");
+  if (c->graph_kind[graph_id] > OPT_ADAM || c->graph_ams[graph_id])
+    return fail(NIF_ERR_STATE, "nif_graph_launch: the graph holds Lion / AdaBelief steps or those of another nif_opt kind (nif_graph_launch_opt with that optimizer)");
   const nif_opt o = opt_of_adam(opt);
   return graph_replay(c, graph_id, &o, "nif_graph_launch");
 }
@@ -2245,8 +2287,8 @@ extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt*
   if (!c || !opt || !graph_ok(c, graph_id)) return fail(NIF_ERR_INVALID, "bad argument");
   const int rc = opt_check(opt); if (rc) return rc;
   const int rk = c->graph_kind[graph_id];
-  if (rk >= 0 && (rk != opt->kind || (c->graph_ams[graph_id] != 0) != opt_ams(opt)))
-    return fail(NIF_ERR_INVALID, "nif_graph_launch_opt: the graph was recorded with another optimizer kind / amsgrad flag");
+  if (rk >= 0 && (rk != opt_kk(opt) || (c->graph_ams[graph_id] != 0) != opt_ams(opt)))
+    return fail(NIF_ERR_INVALID, "nif_graph_launch_opt: the graph was recorded with another optimizer kind / amsgrad flag (or centered / decoupled weight decay flag)");
   return graph_replay(c, graph_id, opt, "nif_graph_launch_opt");
 }
 extern "C" int nif_get_opt_slot(nif_ctx* c, int32_t slot, float* host, int64_t n) {
@@ -2270,6 +2312,7 @@ extern "C" int nif_set_opt_slot(nif_ctx* c, int32_t slot, const float* host, int
   float* dst = slot == 0 ? c->m : slot == 1 ? c->v : c->vhat;
   HIPCHK(hipMemcpyAsync(dst, host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
+  c->slots_fresh = false;
   return NIF_OK;
 }
 

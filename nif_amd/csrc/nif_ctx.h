@@ -102,7 +102,8 @@ struct nif_ctx {
   // with the kind it holds
   std::vector<hipGraphExec_t> graphs; std::vector<int> graph_steps; bool capturing = false; int cap_steps = 0; long cap_step0 = 0;
   DevBuf<OptDev> opt_dev; DevBuf<OptDev, true> opt_host;
-  DevBuf<float> vhat;          // AdaBelief's amsgrad slot, allocated on first use
+  DevBuf<float> vhat;          // the third optimizer slot (amsgrad's vhat, centered RMSprop's a), allocated on first use
+  bool slots_fresh = true;     // m, v are zero and the iteration count 0: Adagrad's first step writes its initial accumulator
   int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
   // magnitude pruning (nif_prune_*): the segment table (host copy: the k of the last update), its span [prune_lo, prune_hi), a byte mask
   // over the whole of theta (1 outside the segments), the thresholds and the select's histograms / per-segment state

@@ -267,11 +267,45 @@ void launch_metric(const float* g, long P, float weight, double* acc, hipStream_
 // the optimizer updates (k_opt.hip, include/nif_hip.h nif_adam_step_dev / nif_opt_step_dev).  OptDev: the hyper-parameters of a nif_opt
 // and the iteration count, in device memory for a captured graph of steps; the host forms the same scalars from the same struct for
 // eager steps.
-enum { OPT_ADAM = 0, OPT_LION = 1, OPT_ADABELIEF = 2 };
-enum { OPT_RECTIFY = 1, OPT_AMSGRAD = 2 };
-struct OptDev { int kind, flags; float lr, beta1, beta2, eps, wd, decay, sma_threshold, warmup_proportion, min_lr; long total_steps; long step; };
+// OPT_ADAMW is a kernel kind only (kernel_kind below): in a nif_opt it is NIF_OPT_ADAM with NIF_OPT_DECOUPLED_WD
+enum { OPT_ADAM = 0, OPT_LION = 1, OPT_ADABELIEF = 2, OPT_SGD = 3, OPT_RMSPROP = 4, OPT_ADAGRAD = 5, OPT_ADAMAX = 6, OPT_ADAMW = 7 };
+enum { OPT_RECTIFY = 1, OPT_AMSGRAD = 2, OPT_NESTEROV = 4, OPT_CENTERED = 8, OPT_DECOUPLED_WD = 16 };
+enum { SCHED_NONE = 0, SCHED_EXPONENTIAL = 1, SCHED_INVERSE_TIME = 2, SCHED_COSINE = 3, SCHED_POLYNOMIAL = 4, SCHED_KIND_MASK = 0xff,
+       SCHED_STAIRCASE = 0x100, SCHED_CYCLE = 0x200 };
+// the fields behind `step` are the schedule's and Adagrad's: all zero for the kinds and calls that do not know them
+struct OptDev {
+  int kind, flags; float lr, beta1, beta2, eps, wd, decay, sma_threshold, warmup_proportion, min_lr; long total_steps; long step;
+  int sched, decay_steps; float sched_a, sched_b;
+};
 struct OptScalars { double lr, bc1, bc2, r; int div; };
-// the per-step scalars of iteration t (Keras' iterations + 1) in fp64: lr_d = lr / (1 + decay (t - 1)) (Keras' _decayed_lr); for AdaBelief
+// the kernel instantiation of a step and whether it has a third slot (Adam / AdaBelief amsgrad's vhat, centered RMSprop's mean gradient)
+__host__ __device__ inline int kernel_kind(int kind, int flags) { return kind == OPT_ADAM && (flags & OPT_DECOUPLED_WD) ? OPT_ADAMW : kind; }
+__host__ __device__ inline bool third_slot(int kind, int flags) {
+  return ((kind == OPT_ADAM || kind == OPT_ADABELIEF) && (flags & OPT_AMSGRAD)) || (kind == OPT_RMSPROP && (flags & OPT_CENTERED));
+}
+// a tf.keras.optimizers.schedules.* learning rate at Keras' step = t - 1 in fp64 (formulas restated from Keras 2.11; sched_a / sched_b:
+// Exponential and InverseTime decay_rate; Cosine alpha; Polynomial end_learning_rate, power)
+__host__ __device__ inline double sched_lr(const OptDev& o, double lr, double step) {
+  const int k = o.sched & SCHED_KIND_MASK;
+  const double ds = (double)o.decay_steps, a = (double)o.sched_a, b = (double)o.sched_b;
+  if (k == SCHED_EXPONENTIAL || k == SCHED_INVERSE_TIME) {
+    double p = step / ds;
+    if (o.sched & SCHED_STAIRCASE) p = floor(p);
+    return k == SCHED_EXPONENTIAL ? lr * pow(a, p) : lr / (1.0 + a * p);
+  }
+  if (k == SCHED_COSINE) {
+    const double q = fmin(step, ds) / ds;
+    return lr * ((1.0 - a) * 0.5 * (1.0 + cos(3.14159265358979323846 * q)) + a);
+  }
+  if (k == SCHED_POLYNOMIAL) {
+    const double dsc = (o.sched & SCHED_CYCLE) ? ds * fmax(1.0, ceil(step / ds)) : ds;
+    const double q = fmin(step, dsc) / dsc;
+    return (lr - a) * pow(1.0 - q, b) + a;
+  }
+  return lr;
+}
+// the per-step scalars of iteration t (Keras' iterations + 1) in fp64: the schedule's learning rate, or lr_d = lr / (1 + decay (t - 1))
+// (Keras' _decayed_lr; never both); for AdaBelief
 // the warm-up ramp / linear decay to min_lr over total_steps, the bias corrections 1 - b^t, the rectification factor r_t and whether
 // this step divides by (v_hat + eps) (div = 0: the plain momentum step below sma_threshold)
 __host__ __device__ inline OptScalars opt_scalars(const OptDev& o, long t_) {
@@ -279,6 +313,7 @@ __host__ __device__ inline OptScalars opt_scalars(const OptDev& o, long t_) {
   const double t = (double)t_;
   double lr = (double)o.lr;
   if (o.decay != 0.f) lr = lr / (1.0 + (double)o.decay * (t - 1.0));
+  if (o.sched) lr = sched_lr(o, lr, t - 1.0);
   const double b2 = (double)o.beta2, b2t = pow(b2, t);
   s.bc1 = 1.0 - pow((double)o.beta1, t);
   s.bc2 = 1.0 - b2t;
@@ -301,12 +336,18 @@ __host__ __device__ inline OptScalars opt_scalars(const OptDev& o, long t_) {
   s.lr = lr;
   return s;
 }
-// what one update kernel receives (floats; the fp64 scalars rounded once).  Adam's lr is its step size lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
-struct OptArgs { float lr, b1, b2, eps, wd, bc1, bc2, r; int div; };
+// what one update kernel receives (floats; the fp64 scalars rounded once).  lr: Adam's step size lr_t = lr sqrt(1 - b2^t) / (1 - b1^t),
+// Adamax's lr / (1 - b1^t), else the step's learning rate; lr0: that learning rate without a bias correction (AdamW's decay).  SGD and
+// RMSprop: b1 = momentum, RMSprop b2 = rho; div: SGD 0 no momentum, 1 momentum, 2 nesterov; RMSprop 1 with momentum > 0
+struct OptArgs { float lr, b1, b2, eps, wd, bc1, bc2, r; int div; float lr0; };
 __host__ __device__ inline OptArgs opt_args(const OptDev& o, const OptScalars& s) {
   OptArgs a;
-  a.lr = (float)(o.kind == OPT_ADAM ? s.lr * sqrt(s.bc2) / s.bc1 : s.lr); a.b1 = o.beta1; a.b2 = o.beta2; a.eps = o.eps; a.wd = o.wd;
+  a.lr = (float)(o.kind == OPT_ADAM ? s.lr * sqrt(s.bc2) / s.bc1 : o.kind == OPT_ADAMAX ? s.lr / s.bc1 : s.lr);
+  a.b1 = o.beta1; a.b2 = o.beta2; a.eps = o.eps; a.wd = o.wd;
   a.bc1 = (float)s.bc1; a.bc2 = (float)s.bc2; a.r = (float)s.r; a.div = s.div;
+  if (o.kind == OPT_SGD) a.div = o.beta1 != 0.f ? ((o.flags & OPT_NESTEROV) ? 2 : 1) : 0;
+  if (o.kind == OPT_RMSPROP) a.div = o.beta1 > 0.f ? 1 : 0;
+  a.lr0 = (float)s.lr;
   return a;
 }
 void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, const OptArgs& a,

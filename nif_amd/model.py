@@ -14,7 +14,7 @@ from . import _lib
 from . import distributed as dist
 from .data import ShardBatches
 from .engine import Engine
-from .optimizers import Adam, get as get_optimizer, grad_transform_of
+from .optimizers import Adam, get as get_optimizer, grad_transform_of, slot_layout
 from .spec import Spec
 
 _global_rng = [np.random.default_rng()]
@@ -136,25 +136,34 @@ class Model(object):
 
     def save_weights(self, filepath):
         """Flat parameters in Keras variable order + Adam slots, as .npz (the reference's TF-checkpoint
-        format, README.md:179-195, is a TensorFlow artefact and out of scope).  Compiled with Lion / AdaBelief: the
-        weights + opt_kind, opt_step and that optimizer's slots (opt_m; opt_v; opt_vhat with amsgrad) instead."""
+        format, README.md:179-195, is a TensorFlow artefact and out of scope).  Compiled with another optimizer than plain Adam: the
+        weights + opt_kind, opt_step and that optimizer's slots by index (opt_m slot 0; opt_v slot 1; opt_vhat slot 2 -- amsgrad's
+        vhat, centered RMSprop's mean gradient) and, for AdamW and centered RMSprop, opt_flags instead."""
         ws = self.get_weights()
         arrs = {"w%03d" % i: w for i, w in enumerate(ws)}
         path = filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz"
         names = np.array([nm for nm, _ in self._engine.shapes])
         opt = self.optimizer
-        if opt is not None and not isinstance(opt, Adam):
+        if opt is not None and not self._plain_adam_slots(opt):
             e = self._engine
+            kind, flags, second, third = slot_layout(opt)
             m, v, step = e.get_opt_state()
             slots = {"opt_m": m}
-            if opt.kind == _lib.OPT_ADABELIEF:
+            if second:
                 slots["opt_v"] = v
-                if opt.amsgrad:
-                    slots["opt_vhat"] = e.get_opt_slot(2)
-            np.savez(path, names=names, opt_kind=np.int32(opt.kind), opt_step=np.int64(step), **slots, **arrs, **self._extra_arrays())
+            if third:
+                slots["opt_vhat"] = e.get_opt_slot(2)
+            if flags & ~_lib.OPT_AMSGRAD:                # (amsgrad is read from opt_vhat's presence, as in the files written so far)
+                slots["opt_flags"] = np.int32(flags)
+            np.savez(path, names=names, opt_kind=np.int32(kind), opt_step=np.int64(step), **slots, **arrs, **self._extra_arrays())
             return
         m, v, step = self._engine.get_opt_state()
         np.savez(path, names=names, adam_m=m, adam_v=v, adam_step=np.int64(step), **arrs, **self._extra_arrays())
+
+    @staticmethod
+    def _plain_adam_slots(opt):
+        """Adam's m and v alone (a schedule does not change the slots): the adam_m / adam_v / adam_step file"""
+        return isinstance(opt, Adam) and slot_layout(opt)[1] == 0
 
     def _extra_arrays(self):
         """hook: arrays a wrapper adds to save_weights' file (sparsity.PrunedModel: masks, thresholds, step)"""
@@ -170,7 +179,7 @@ class Model(object):
         self.set_weights([d["w%03d" % i] for i in range(n)])
         opt = self.optimizer
         if "adam_m" in d:
-            if opt is None or isinstance(opt, Adam):
+            if opt is None or self._plain_adam_slots(opt):
                 self._engine.set_opt_state(d["adam_m"], d["adam_v"], int(d["adam_step"]))
                 self._fresh_slots = False
             else:
@@ -178,7 +187,8 @@ class Model(object):
                               "optimizer state not restored" % type(opt).__name__)
         elif "opt_kind" in d:
             kind, ams = int(d["opt_kind"]), "opt_vhat" in d
-            if opt is not None and not isinstance(opt, Adam) and opt.kind == kind and bool(opt.amsgrad) == ams:
+            flags = int(d["opt_flags"]) if "opt_flags" in d else (_lib.OPT_AMSGRAD if ams else 0)
+            if opt is not None and not self._plain_adam_slots(opt) and slot_layout(opt)[:2] == (kind, flags):
                 e = self._engine
                 m = d["opt_m"]
                 e.set_opt_state(m, d["opt_v"] if "opt_v" in d else np.zeros_like(m), int(d["opt_step"]))
@@ -407,11 +417,12 @@ class Model(object):
     def _fit(self, e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch, validation_data,
              steps_per_epoch):
         self.stop_training = False
-        is_adam = isinstance(self.optimizer, Adam)
+        is_adam = isinstance(self.optimizer, Adam) and self.optimizer.is_plain     # (else the step travels as a nif_opt)
         if getattr(self, "_fresh_slots", False):
             z = np.zeros((e.n_params,), dtype=np.float32)
-            e.set_opt_state(z, z, 0)
-            if not is_adam and self.optimizer.amsgrad:
+            acc0 = getattr(self.optimizer, "initial_accumulator_value", None)      # Adagrad's slot 0 starts there
+            e.set_opt_state(z if acc0 is None else np.full_like(z, acc0), z, 0)
+            if slot_layout(self.optimizer)[3]:
                 e.set_opt_slot(2, z)
             self._fresh_slots = False
         ncol = s.pi_dim + s.si_dim
@@ -534,7 +545,7 @@ class Model(object):
                             dt.upload(t[perm])
                         if has_sw:
                             src_sw.upload(sw[perm])
-                adam = self.optimizer.as_struct() if is_adam else self.optimizer.as_opt()    # (Lion / AdaBelief: a nif_opt)
+                adam = self.optimizer.as_struct() if is_adam else self.optimizer.as_opt()    # (every other kind: a nif_opt)
                 step_dev = e.adam_step_dev if is_adam else e.opt_step_dev
                 self._push_losses(e, 1)           # (a callback of the previous epoch may have evaluated another model on the shared engine)
                 e.metric_read(reset=True)

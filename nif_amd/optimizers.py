@@ -1,11 +1,14 @@
 """Optimizers accepted by Model.compile.  The hot path uses stock Keras-2.11 Adam (README.md:33;
-SURVEY a-11); the reference's Lion and AdaBeliefOptimizer (nif/optimizers/__init__.py) are the other two kinds.  All three
-update on the k_opt.hip kernels (k_opt, k_reduce_opt, k_opt_dev)."""
+SURVEY a-11); the reference's Lion and AdaBeliefOptimizer (nif/optimizers/__init__.py) and Keras 2.11's SGD, RMSprop, Adagrad,
+Adamax, AdamW and amsgrad Adam are the other kinds; Adam and the Keras kinds take a nif_amd.optimizers.schedules.* object as
+learning_rate.  All update on the k_opt.hip kernels (k_opt, k_reduce_opt, k_opt_dev).  The Keras kinds' formulas are restated from
+Keras 2.11 and are not pinned by a TensorFlow run (parity unpinned by TensorFlow)."""
 import numbers
 
 import numpy as np
 
 from . import _lib
+from . import schedules
 
 
 _CLIP_KEYS = ("clipnorm", "clipvalue", "global_clipnorm")
@@ -22,16 +25,28 @@ def _clip_constant(name, v):
     return float(v)
 
 
-class Adam(object):
-    """Keras-2.11 Adam.  clipnorm / clipvalue / global_clipnorm are Keras' gradient clipping (per tensor by norm, by value, by the
-    global norm), applied on the device in front of the update (k_gradtf.hip); at most one of them, as in Keras."""
+class _KerasOptimizer(object):
+    """what Adam and the Keras-2.11 kinds share: learning_rate as a number or a schedules.* object, Keras' clip keywords (gradient
+    clipping per tensor by norm, by value, by the global norm, applied on the device in front of the update, k_gradtf.hip; at most
+    one of them, as in Keras), optimizer.lr, get_config / from_config and the nif_opt a step receives"""
+    kind = _lib.OPT_ADAM
+    amsgrad = False
+    _DEFAULT_NAME = None
 
-    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None,
-                 global_clipnorm=None, **kwargs):
+    def _base(self, learning_rate, clipnorm, clipvalue, global_clipnorm, kwargs, name=None):
+        cls = type(self).__name__
+        kwargs = dict(kwargs)
         if "lr" in kwargs:
             learning_rate = kwargs.pop("lr")
-        self.learning_rate = float(learning_rate)
-        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+        kwargs.pop("jit_compile", None)            # (nothing to compile here)
+        if kwargs.pop("use_ema", False):
+            raise NotImplementedError("%s(use_ema=True): not built" % cls)
+        kwargs.pop("ema_momentum", None); kwargs.pop("ema_overwrite_frequency", None)
+        if kwargs.pop("decay", 0):
+            raise NotImplementedError("%s(decay=...): Keras 2.11's optimizers take a schedule instead (schedules.InverseTimeDecay)" % cls)
+        self._unknown_kwargs(kwargs)
+        self.learning_rate = learning_rate
+        self.name = self._DEFAULT_NAME if name is None else name
         self.clipnorm = _clip_constant("clipnorm", clipnorm)
         self.clipvalue = _clip_constant("clipvalue", clipvalue)
         self.global_clipnorm = _clip_constant("global_clipnorm", global_clipnorm)
@@ -39,17 +54,233 @@ class Adam(object):
             raise ValueError("At most one of `clipnorm`, `clipvalue` and `global_clipnorm` can be set. Received: clipnorm=%r, "
                              "clipvalue=%r, global_clipnorm=%r." % (clipnorm, clipvalue, global_clipnorm))
 
+    def _unknown_kwargs(self, kwargs):
+        if kwargs:
+            raise TypeError("%s: unexpected keyword argument(s) %s" % (type(self).__name__, ", ".join(sorted(kwargs))))
+
+    # learning_rate: a float, or a schedule object kept as it is (Keras: optimizer.lr then returns the schedule)
+    @property
+    def learning_rate(self):
+        return self._learning_rate
+
+    @learning_rate.setter
+    def learning_rate(self, v):
+        if isinstance(v, schedules.LearningRateSchedule):
+            if type(v).pack is schedules.LearningRateSchedule.pack:
+                raise NotImplementedError("%s(learning_rate=%s): built schedules are ExponentialDecay, InverseTimeDecay, CosineDecay "
+                                          "and PolynomialDecay" % (type(self).__name__, type(v).__name__))
+            self._learning_rate = v
+        elif callable(v):
+            raise NotImplementedError("%s(learning_rate=%r): a nif_amd.optimizers.schedules object or a number (a Python callable "
+                                      "cannot be evaluated inside the optimizer step)" % (type(self).__name__, v))
+        else:
+            self._learning_rate = float(v)
+
     # Keras exposes optimizer.lr / optimizer.learning_rate; LearningRateScheduler sets it
     @property
     def lr(self):
-        return self.learning_rate
+        return self._learning_rate
 
     @lr.setter
     def lr(self, v):
-        self.learning_rate = float(v)
+        self.learning_rate = v
+
+    @property
+    def has_schedule(self):
+        return isinstance(self._learning_rate, schedules.LearningRateSchedule)
+
+    def _hyper(self):
+        """the constructor arguments besides learning_rate, the clip keywords and name"""
+        return {}
+
+    def get_config(self):
+        lr = self._learning_rate
+        if self.has_schedule:
+            lr = {"class_name": type(lr).__name__, "config": lr.get_config()}
+        cfg = {"name": self.name, "learning_rate": lr}
+        cfg.update(self._hyper())
+        cfg.update({"clipnorm": self.clipnorm, "clipvalue": self.clipvalue, "global_clipnorm": self.global_clipnorm})
+        return cfg
+
+    @classmethod
+    def from_config(cls, config):
+        config = dict(config)
+        lr = config.get("learning_rate")
+        if isinstance(lr, dict):
+            config["learning_rate"] = getattr(schedules, lr["class_name"]).from_config(lr["config"])
+        return cls(**config)
+
+    def _fill(self, o):
+        """the kind's own fields of the nif_opt"""
+
+    def as_opt(self):
+        o = _lib.nif_opt()
+        o.kind = self.kind
+        if self.has_schedule:
+            self._learning_rate.pack(o)
+        else:
+            o.lr = self._learning_rate
+        self._fill(o)
+        return o
+
+
+class Adam(_KerasOptimizer):
+    """Keras-2.11 Adam.  clipnorm / clipvalue / global_clipnorm are Keras' gradient clipping (per tensor by norm, by value, by the
+    global norm), applied on the device in front of the update (k_gradtf.hip); at most one of them, as in Keras.  amsgrad=True keeps
+    vhat = max(vhat, v) in a third slot and divides by sqrt(vhat) + epsilon.  Without amsgrad and with a constant learning rate the
+    step is nif_adam_step_dev's (as_struct); otherwise it travels as a nif_opt (as_opt)."""
+    _DEFAULT_NAME = "Adam"
+
+    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, name=None, **kwargs):
+        self._base(learning_rate, clipnorm, clipvalue, global_clipnorm, kwargs, name)
+        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+        self.amsgrad = bool(amsgrad)
+
+    def _unknown_kwargs(self, kwargs):
+        """(Adam has always let the other keyword arguments of Keras' optimizer base pass)"""
+
+    @property
+    def is_plain(self):
+        """the step nif_adam_step_dev / nif_graph_launch run: no amsgrad, no schedule, no decoupled weight decay"""
+        return type(self)._fill is Adam._fill and not self.amsgrad and not self.has_schedule
+
+    def _hyper(self):
+        return {"beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon, "amsgrad": self.amsgrad}
 
     def as_struct(self):
-        return _lib.nif_adam(self.learning_rate, self.beta_1, self.beta_2, self.epsilon)
+        if not self.is_plain:
+            raise ValueError("%s.as_struct(): amsgrad, a schedule and decoupled weight decay travel as a nif_opt (as_opt)" % type(self).__name__)
+        return _lib.nif_adam(self._learning_rate, self.beta_1, self.beta_2, self.epsilon)
+
+    def _fill(self, o):
+        o.beta1, o.beta2, o.eps = self.beta_1, self.beta_2, self.epsilon
+        o.flags = _lib.OPT_AMSGRAD if self.amsgrad else 0
+
+
+class AdamW(Adam):
+    """Keras-2.11 AdamW: theta -= lr * weight_decay * theta with the step's learning rate, then Adam's update (with or without amsgrad)"""
+    _DEFAULT_NAME = "AdamW"
+
+    def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, clipnorm=None,
+                 clipvalue=None, global_clipnorm=None, name=None, **kwargs):
+        Adam.__init__(self, learning_rate, beta_1, beta_2, epsilon, amsgrad, clipnorm, clipvalue, global_clipnorm, name, **kwargs)
+        if weight_decay is None:
+            raise ValueError("Missing value of `weight_decay` which is required and must be a float value.")
+        self.weight_decay = _number("AdamW", "weight_decay", weight_decay)
+
+    _unknown_kwargs = _KerasOptimizer._unknown_kwargs
+
+    def _hyper(self):
+        return dict(Adam._hyper(self), weight_decay=self.weight_decay)
+
+    def _fill(self, o):
+        Adam._fill(self, o)
+        o.flags |= _lib.OPT_DECOUPLED_WD
+        o.weight_decay = self.weight_decay
+
+
+class SGD(_KerasOptimizer):
+    """Keras-2.11 SGD: theta -= lr g; with momentum m = momentum m - lr g and theta += m, nesterov: theta += momentum m - lr g"""
+    kind = _lib.OPT_SGD
+    _DEFAULT_NAME = "SGD"
+
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, amsgrad=False, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, name=None, **kwargs):
+        self._base(learning_rate, clipnorm, clipvalue, global_clipnorm, kwargs, name)
+        self.momentum = _number("SGD", "momentum", momentum)
+        if not 0.0 <= self.momentum <= 1.0:
+            raise ValueError("`momentum` must be between [0, 1].")
+        self.nesterov = bool(nesterov)
+        if amsgrad:
+            raise NotImplementedError("SGD(amsgrad=True): Keras' SGD has no such update")
+
+    def _hyper(self):
+        return {"momentum": self.momentum, "nesterov": self.nesterov}
+
+    def _fill(self, o):
+        o.beta1 = self.momentum
+        o.flags = _lib.OPT_NESTEROV if self.nesterov else 0
+
+
+class RMSprop(_KerasOptimizer):
+    """Keras-2.11 RMSprop: v = rho v + (1-rho) g^2; centered: a = rho a + (1-rho) g and the denominator v - a^2 + epsilon, else
+    v + epsilon; inc = lr g / sqrt(denominator); with momentum mom = momentum mom + inc and theta -= mom, else theta -= inc"""
+    kind = _lib.OPT_RMSPROP
+    _DEFAULT_NAME = "RMSprop"
+
+    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, name=None, **kwargs):
+        self._base(learning_rate, clipnorm, clipvalue, global_clipnorm, kwargs, name)
+        self.rho, self.epsilon = _number("RMSprop", "rho", rho), float(epsilon)
+        self.momentum = _number("RMSprop", "momentum", momentum)
+        if not 0.0 <= self.momentum <= 1.0:
+            raise ValueError("`momentum` must be between [0, 1].")
+        self.centered = bool(centered)
+
+    def _hyper(self):
+        return {"rho": self.rho, "momentum": self.momentum, "epsilon": self.epsilon, "centered": self.centered}
+
+    def _fill(self, o):
+        o.beta1, o.beta2, o.eps = self.momentum, self.rho, self.epsilon
+        o.flags = _lib.OPT_CENTERED if self.centered else 0
+
+
+class Adagrad(_KerasOptimizer):
+    """Keras-2.11 Adagrad: acc += g^2 from acc = initial_accumulator_value; theta -= lr g / sqrt(acc + epsilon)"""
+    kind = _lib.OPT_ADAGRAD
+    _DEFAULT_NAME = "Adagrad"
+
+    def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, name=None, **kwargs):
+        self._base(learning_rate, clipnorm, clipvalue, global_clipnorm, kwargs, name)
+        self.initial_accumulator_value = _number("Adagrad", "initial_accumulator_value", initial_accumulator_value)
+        if self.initial_accumulator_value < 0.0:
+            raise ValueError("initial_accumulator_value must be non-negative: %r" % (initial_accumulator_value,))
+        self.epsilon = float(epsilon)
+
+    def _hyper(self):
+        return {"initial_accumulator_value": self.initial_accumulator_value, "epsilon": self.epsilon}
+
+    def _fill(self, o):
+        o.eps, o.init_acc = self.epsilon, self.initial_accumulator_value
+
+
+class Adamax(_KerasOptimizer):
+    """Keras-2.11 Adamax: m += (g - m)(1 - beta_1); u = max(beta_2 u, |g|); theta -= (lr / (1 - beta_1^t)) m / (u + epsilon)"""
+    kind = _lib.OPT_ADAMAX
+    _DEFAULT_NAME = "Adamax"
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, name=None, **kwargs):
+        self._base(learning_rate, clipnorm, clipvalue, global_clipnorm, kwargs, name)
+        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+
+    def _hyper(self):
+        return {"beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
+
+    def _fill(self, o):
+        o.beta1, o.beta2, o.eps = self.beta_1, self.beta_2, self.epsilon
+
+
+class Nadam(object):
+    """tf.keras.optimizers.Nadam: not built -- its momentum schedule keeps a running product as state that the optimizer step has no
+    place for"""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("Nadam: not built (its running product of the momentum schedule is state the optimizer step does "
+                                  "not carry); built are Adam, AdamW, SGD, RMSprop, Adagrad, Adamax, Lion and AdaBeliefOptimizer")
+
+
+def slot_layout(opt):
+    """(kind, slot-shaping flags, has a second slot, has a third slot) of a compiled optimizer: what a checkpoint and a captured graph
+    are tied to.  Slots by index: Adam / AdaBelief m, v, vhat; Lion, SGD m; RMSprop v, mom, a; Adagrad acc; Adamax m, u"""
+    if isinstance(opt, _KerasOptimizer):
+        flags = opt.as_opt().flags & (_lib.OPT_AMSGRAD | _lib.OPT_CENTERED | _lib.OPT_DECOUPLED_WD)
+    else:
+        flags = _lib.OPT_AMSGRAD if opt.amsgrad else 0
+    second = opt.kind not in (_lib.OPT_LION, _lib.OPT_SGD, _lib.OPT_ADAGRAD)
+    return opt.kind, flags, second, bool(flags & (_lib.OPT_AMSGRAD | _lib.OPT_CENTERED))
 
 
 def _number(cls, what, v):
@@ -186,8 +417,9 @@ def centralized_gradients_for_optimizer(optimizer):
     Under the reference's pinned TensorFlow 2.11 the hook is inert: Keras' fit() never calls optimizer.get_gradients, so the
     reference trains unchanged whether or not the function was used; what is built here is what its body computes.  The returned
     object cannot be called (there is no symbolic loss): it is a marker."""
-    if not isinstance(optimizer, (Adam, Lion, AdaBeliefOptimizer)):
-        raise TypeError("centralized_gradients_for_optimizer(optimizer): an Adam, Lion or AdaBeliefOptimizer of nif_amd.optimizers")
+    if not isinstance(optimizer, (_KerasOptimizer, Lion, AdaBeliefOptimizer)):
+        raise TypeError("centralized_gradients_for_optimizer(optimizer): an Adam, Lion or AdaBeliefOptimizer of nif_amd.optimizers "
+                        "(or one of its Keras kinds: AdamW, SGD, RMSprop, Adagrad, Adamax)")
     return _CentralizedGradients(optimizer)
 
 
@@ -203,7 +435,7 @@ def grad_transform_of(opt):
             raise ValueError("centralized_gradients_for_optimizer reads clipnorm (its global norm) and clipvalue; global_clipnorm=%r "
                              "is set as well" % (opt.global_clipnorm,))
         return {"centralize": True, "gtcf": True, "clipnorm": positive("clipnorm"), "clipvalue": positive("clipvalue")}
-    if not isinstance(opt, Adam):
+    if not isinstance(opt, _KerasOptimizer):
         return None       # (Lion / AdaBeliefOptimizer take no clip keywords: attributes count on the gtcf route only)
     spec = {k: positive(k) for k in _CLIP_KEYS}
     if sum(1 for v in spec.values() if v) > 1:
@@ -211,17 +443,24 @@ def grad_transform_of(opt):
     return spec if any(spec.values()) else None
 
 
+_BY_NAME = {"adam": Adam, "adamw": AdamW, "sgd": SGD, "rmsprop": RMSprop, "adagrad": Adagrad, "adamax": Adamax}
+
+
 def get(opt):
-    if isinstance(opt, (Adam, Lion, AdaBeliefOptimizer)):
+    if isinstance(opt, (_KerasOptimizer, Lion, AdaBeliefOptimizer)):
         return opt
     if isinstance(opt, str):
-        if opt.lower() == "adam":
-            return Adam()
-        raise NotImplementedError("optimizer %r: only Adam is on the built hot path" % (opt,))
+        if opt.lower() in _BY_NAME:
+            return _BY_NAME[opt.lower()]()
+        if opt.lower() == "nadam":
+            return Nadam()
+        raise NotImplementedError("optimizer %r: Keras' names built here are %s (Lion and AdaBeliefOptimizer are passed as objects)"
+                                  % (opt, ", ".join(sorted(_BY_NAME))))
     # duck-typed: anything with learning_rate/beta_1/beta_2/epsilon (e.g. a config object)
     if all(hasattr(opt, a) for a in ("learning_rate", "beta_1", "beta_2", "epsilon")):
         return Adam(float(opt.learning_rate), float(opt.beta_1), float(opt.beta_2), float(opt.epsilon))
-    raise NotImplementedError("optimizer %r: only Adam is on the built hot path" % (opt,))
+    raise NotImplementedError("optimizer %r: an Adam, AdamW, SGD, RMSprop, Adagrad, Adamax, Lion or AdaBeliefOptimizer of "
+                              "nif_amd.optimizers, or one of Keras' names for them" % (opt,))
 
 
 import numpy as np
