@@ -324,7 +324,8 @@ int nif_opt_step_dev(nif_ctx* ctx, const nif_opt* opt);
  * recorded with non-Adam steps (NIF_ERR_STATE). */
 int nif_graph_launch_opt(nif_ctx* ctx, int32_t graph_id, const nif_opt* opt);
 /* optimizer slots for checkpoints: slot 0 m, 1 v, 2 vhat (reads zeros before vhat exists; a write allocates it); the Keras kinds'
- * slots are listed at nif_opt_kind */
+ * slots are listed at nif_opt_kind.  Slot 3 is the weight average of nif_set_option("ema"): zeros before it exists (or after
+ * nif_set_opt_state reset it), a write creates it, a write inside a capture is NIF_ERR_STATE like every other slot's */
 int nif_get_opt_slot(nif_ctx* ctx, int32_t slot, float* host, int64_t n);
 int nif_set_opt_slot(nif_ctx* ctx, int32_t slot, const float* host, int64_t n);
 /* the per-step scalars of iteration t (>= 1) as the kernels receive them, in fp64 (host-only, no context):
@@ -444,7 +445,17 @@ int nif_f64_grad_read(nif_ctx* ctx, double* loss_out_or_null, double* grad_host_
  * "fuse_gw", "small_step", "fuse_tail" (default 1; NIF_FUSE_GW / NIF_SMALL_STEP / NIF_FUSE_TAIL = 0): the fused-gradient kernel, the
  * one-launch small-batch step, the row reduction deferred to nif_adam_step_dev (which then runs it fused with the update: the
  * [grad | loss] buffer is complete after ANY other call of this library on the context -- nif_grad_dev included -- and after the
- * update; a caller that reads the buffer through a pointer it cached earlier, without such a call, sets "fuse_tail" to 0) */
+ * update; a caller that reads the buffer through a pointer it cached earlier, without such a call, sets "fuse_tail" to 0).
+ * Weight averaging (Keras' use_ema; restated from Keras 2.11's documentation, unpinned by TensorFlow) is context state set here:
+ *   "ema": 0 off (default), -1 on, f >= 1 on and theta overwritten by the average every f steps (the steps that complete an
+ *     iteration t with t % f == 0); any other value NIF_ERR_INVALID;
+ *   "ema_momentum_bits": the IEEE-754 bit pattern of the float32 momentum, default 0.99; NaN or outside [0, 1] NIF_ERR_INVALID.
+ * While on, every optimizer step of the context (nif_adam_step_dev, nif_opt_step_dev, the fused tail, captured steps) also runs
+ * average = momentum average + (1 - momentum) theta on the updated theta, in the same launch.  The average is slot 3 of
+ * nif_get_opt_slot; the first such step that finds none seeds it with theta as it stands before the update; nif_set_opt_state
+ * resets it, nif_set_params does not touch it.  Both keys NIF_ERR_STATE inside nif_graph_begin / nif_graph_end; a capture needs the
+ * average to exist (one eager step or nif_set_opt_slot(3, ...)); a graph is replayed only with the setting (on / off) it was recorded
+ * with (NIF_ERR_STATE), momentum and frequency are read at replay time. */
 int nif_set_option(nif_ctx* ctx, const char* key, int32_t value);
 
 /* ---- multi-GPU: RCCL over xGMI, called directly (replaces `tf.distribute.MirroredStrategy().scope()`, reference

@@ -1,7 +1,8 @@
 // k_opt.hip -- the optimizer updates on the flat parameter vector (gfx950): Keras-2.11 Adam (SURVEY a-11), the reference's Lion and
 // AdaBelief (nif/optimizers/external_optimizers.py:631-735, :322-628), Keras 2.11's SGD, RMSprop, Adagrad, Adamax, AdamW and amsgrad Adam
 // (formulas restated from Keras 2.11, not pinned by TensorFlow), and the fixed-order row reduction of the gradient (k_reduce), which
-// the fused forms share.  Three forms of each update, each one template over (kind, third slot: amsgrad's vhat / centered RMSprop's mean):
+// the fused forms share.  Three forms of each update, each one template over (kind, third slot: amsgrad's vhat / centered RMSprop's mean,
+// weight average: Keras' use_ema behind the update in the same launch, +4 B read and +4 B written per parameter; ema_1):
 //   * k_opt: the update alone over [0, P), behind an all-reduce, a regulariser or a flushed row reduction.  A stream bound by bandwidth:
 //     Adam reads theta, g, m, v (16 B) and writes theta, m, v (12 B) per parameter; Lion 12 B / 8 B; AdaBelief as Adam, with amsgrad
 //     20 B / 16 B; SGD and Adagrad 12 B / 8 B (slot 0 only), Adamax and RMSprop as Adam (centered RMSprop, amsgrad Adam and AdamW
@@ -98,10 +99,18 @@ __device__ __forceinline__ void adamax_1(float& th, float g, float& m, float& u,
 // the kinds with a second slot (Adam v, AdaBelief v, RMSprop mom, Adamax u); slot 0 is every kind's
 template <int KIND> struct Slots { static constexpr bool second = KIND != OPT_LION && KIND != OPT_SGD && KIND != OPT_ADAGRAD; };
 
+// Keras' use_ema behind the update of any kind (Keras 2.11, restated, not pinned by TensorFlow): average = momentum average +
+// (1 - momentum) theta with the UPDATED theta; on an overwrite step (ema_overwrite) theta becomes the average
+__device__ __forceinline__ void ema_1(float& th, float& av, const OptArgs& a) {
+  av = a.ema_mom * av + (1.0f - a.ema_mom) * th;
+  if (a.ema_ow) th = av;
+}
+
 // one parameter of any kind: slots (m, v, vh) are Adam / AdaBelief m, v, vhat; Lion, SGD m; RMSprop v, mom, a; Adagrad acc; Adamax m, u.
-// AMS: the third slot is in use.  AdamW: theta -= lr wd theta with the step's learning rate (no bias correction), then Adam
-template <int KIND, bool AMS>
-__device__ __forceinline__ void opt_1(float& th, float g, float& m, float& v, float& vh, const OptArgs& a) {
+// AMS: the third slot is in use.  AdamW: theta -= lr wd theta with the step's learning rate (no bias correction), then Adam.
+// EMA: av is the weight average, updated behind the kind's update (ema_1)
+template <int KIND, bool AMS, bool EMA>
+__device__ __forceinline__ void opt_1(float& th, float g, float& m, float& v, float& vh, float& av, const OptArgs& a) {
   if (KIND == OPT_ADAM && !AMS) adam_1(th, g, m, v, a);
   else if (KIND == OPT_ADAM) adam_ams_1(th, g, m, v, vh, a);
   else if (KIND == OPT_LION) lion_1(th, g, m, a);
@@ -115,12 +124,14 @@ __device__ __forceinline__ void opt_1(float& th, float g, float& m, float& v, fl
     if (AMS) adam_ams_1(th, g, m, v, vh, a);
     else adam_1(th, g, m, v, a);
   }
+  if (EMA) ema_1(th, av, a);
 }
 
 // n4 = P / 4 when every buffer is 16-byte aligned, else 0 (all scalar)
-template <int KIND, bool AMS>
+template <int KIND, bool AMS, bool EMA>
 __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
-                                           float* __restrict__ v, float* __restrict__ vh, long P, long n4, const OptArgs& a) {
+                                           float* __restrict__ v, float* __restrict__ vh, float* __restrict__ ema, long P, long n4,
+                                           const OptArgs& a) {
   constexpr bool S1 = Slots<KIND>::second;
   const long stride = (long)gridDim.x * blockDim.x;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -128,28 +139,32 @@ __device__ __forceinline__ void opt_stream(float* __restrict__ theta, const floa
     f32x4 t4 = reinterpret_cast<const f32x4*>(theta)[q];
     const f32x4 g4 = reinterpret_cast<const f32x4*>(g)[q];
     f32x4 m4 = reinterpret_cast<const f32x4*>(m)[q];
-    f32x4 v4 = {0.f, 0.f, 0.f, 0.f}, h4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 v4 = {0.f, 0.f, 0.f, 0.f}, h4 = {0.f, 0.f, 0.f, 0.f}, e4 = {0.f, 0.f, 0.f, 0.f};
     if (S1) v4 = reinterpret_cast<const f32x4*>(v)[q];
     if (AMS) h4 = reinterpret_cast<const f32x4*>(vh)[q];
+    if (EMA) e4 = reinterpret_cast<const f32x4*>(ema)[q];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float tj = t4[j], mj = m4[j], vj = v4[j], hj = h4[j];
-      opt_1<KIND, AMS>(tj, g4[j], mj, vj, hj, a);
-      t4[j] = tj; m4[j] = mj; v4[j] = vj; h4[j] = hj;
+      float tj = t4[j], mj = m4[j], vj = v4[j], hj = h4[j], ej = e4[j];
+      opt_1<KIND, AMS, EMA>(tj, g4[j], mj, vj, hj, ej, a);
+      t4[j] = tj; m4[j] = mj; v4[j] = vj; h4[j] = hj; e4[j] = ej;
     }
     reinterpret_cast<f32x4*>(theta)[q] = t4;
     reinterpret_cast<f32x4*>(m)[q] = m4;
     if (S1) reinterpret_cast<f32x4*>(v)[q] = v4;
     if (AMS) reinterpret_cast<f32x4*>(vh)[q] = h4;
+    if (EMA) reinterpret_cast<f32x4*>(ema)[q] = e4;
   }
   for (long i = 4 * n4 + tid; i < P; i += stride) {
-    float tj = theta[i], mj = m[i], vj = 0.f, hj = 0.f;
+    float tj = theta[i], mj = m[i], vj = 0.f, hj = 0.f, ej = 0.f;
     if (S1) vj = v[i];
     if (AMS) hj = vh[i];
-    opt_1<KIND, AMS>(tj, g[i], mj, vj, hj, a);
+    if (EMA) ej = ema[i];
+    opt_1<KIND, AMS, EMA>(tj, g[i], mj, vj, hj, ej, a);
     theta[i] = tj; m[i] = mj;
     if (S1) v[i] = vj;
     if (AMS) vh[i] = hj;
+    if (EMA) ema[i] = ej;
   }
 }
 
@@ -187,14 +202,16 @@ __device__ __forceinline__ void reduce_loss(const float* __restrict__ lossp, int
 }
 
 // the step's scalars from device memory, formed once per block.  od->kind is KIND (a graph is replayed only with the kind it recorded):
-// stating it lets the compiler drop the other kinds' scalar code from the block's prologue
-template <int KIND>
+// stating it lets the compiler drop the other kinds' scalar code from the block's prologue.  EMA: whether this recorded step overwrites
+// theta by the average is decided here, from the count the replay has reached
+template <int KIND, bool EMA>
 __device__ __forceinline__ OptArgs block_args(const OptDev* __restrict__ od) {
   __shared__ OptArgs sa;
   if (threadIdx.x == 0) {
     OptDev o = *od;
     o.kind = KIND == OPT_ADAMW ? OPT_ADAM : KIND;
     sa = opt_args(o, opt_scalars(o, o.step + 1));
+    if (EMA) sa.ema_ow = ema_overwrite(o.step + 1, o.ema_freq) ? 1 : 0;
   }
   __syncthreads();
   return sa;
@@ -214,35 +231,38 @@ __global__ __launch_bounds__(512) void k_reduce(const float* __restrict__ partia
 }
 
 // ---- the three update forms -------------------------------------------------------------------------------------------------------
-template <int KIND, bool AMS>
+// (ema sits behind the arguments the EMA-off instantiations read: theirs keep their places)
+template <int KIND, bool AMS, bool EMA>
 __global__ __launch_bounds__(256) void k_opt(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
-                                             float* __restrict__ v, float* __restrict__ vh, long P, long n4, OptArgs a) {
-  opt_stream<KIND, AMS>(theta, g, m, v, vh, P, n4, a);
+                                             float* __restrict__ v, float* __restrict__ vh, long P, long n4, OptArgs a,
+                                             float* __restrict__ ema) {
+  opt_stream<KIND, AMS, EMA>(theta, g, m, v, vh, ema, P, n4, a);
 }
-template <int KIND, bool AMS>
+template <int KIND, bool AMS, bool EMA>
 __global__ __launch_bounds__(256) void k_opt_dev(float* __restrict__ theta, const float* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, float* __restrict__ vh, long P, long n4,
-                                                 const OptDev* __restrict__ od) {
-  const OptArgs a = block_args<KIND>(od);
-  opt_stream<KIND, AMS>(theta, g, m, v, vh, P, n4, a);
+                                                 const OptDev* __restrict__ od, float* __restrict__ ema) {
+  const OptArgs a = block_args<KIND, EMA>(od);
+  opt_stream<KIND, AMS, EMA>(theta, g, m, v, vh, ema, P, n4, a);
 }
 __global__ void k_opt_step_inc(OptDev* od) { od->step += 1; }
-template <int KIND, bool AMS>
+template <int KIND, bool AMS, bool EMA>
 __global__ __launch_bounds__(512) void k_reduce_opt(const float* __restrict__ partial, long pstride, int rows,
                                                     const float* __restrict__ lossp, int nloss, float* __restrict__ g, long P,
                                                     float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
-                                                    float* __restrict__ vh, OptArgs a) {
+                                                    float* __restrict__ vh, OptArgs a, float* __restrict__ ema) {
   __shared__ float red[8][64];
   const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
   const long i = (long)blockIdx.x * 64 + col;
   const float gi = reduce_col(partial, pstride, rows, red, col, rg, i, P);
   if (rg == 0 && i < P) {
     g[i] = gi;
-    float th = theta[i], mi = m[i], vi = Slots<KIND>::second ? v[i] : 0.f, hi = AMS ? vh[i] : 0.f;
-    opt_1<KIND, AMS>(th, gi, mi, vi, hi, a);
+    float th = theta[i], mi = m[i], vi = Slots<KIND>::second ? v[i] : 0.f, hi = AMS ? vh[i] : 0.f, ei = EMA ? ema[i] : 0.f;
+    opt_1<KIND, AMS, EMA>(th, gi, mi, vi, hi, ei, a);
     theta[i] = th; m[i] = mi;
     if (Slots<KIND>::second) v[i] = vi;
     if (AMS) vh[i] = hi;
+    if (EMA) ema[i] = ei;
   }
   if (blockIdx.x == gridDim.x - 1) reduce_loss(lossp, nloss, red, col, rg, g + P);
 }
@@ -257,9 +277,9 @@ static bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 
 // n4 and the grid of a stream over P parameters (v, vh: nullptr where the kind does not use them): at most 2048 blocks of 256 threads,
 // the rest grid-strided.  Adam without amsgrad runs one parameter per thread (n4 = 0), the shape of its earlier kernels: four per thread
 // serialise four divisions and square roots, and made the captured configs[0] step (P = 6 627, 7 blocks instead of 26) 0.5 us slower
-static void stream_shape(int kind, const float* theta, const float* g, const float* m, const float* v, const float* vh, long P,
-                         long* n4, dim3* grid) {
-  *n4 = (!(kind == OPT_ADAM && vh == nullptr) && al16(theta) && al16(g) && al16(m) && al16(v) && al16(vh)) ? P / 4 : 0;
+static void stream_shape(int kind, const float* theta, const float* g, const float* m, const float* v, const float* vh,
+                         const float* ema, long P, long* n4, dim3* grid) {
+  *n4 = (!(kind == OPT_ADAM && vh == nullptr) && al16(theta) && al16(g) && al16(m) && al16(v) && al16(vh) && al16(ema)) ? P / 4 : 0;
   const long work = *n4 > 0 ? *n4 : P;
   long blocks = (work + 255) / 256;
   if (blocks > 2048) blocks = 2048;
@@ -267,51 +287,54 @@ static void stream_shape(int kind, const float* theta, const float* g, const flo
   *grid = dim3((unsigned)blocks);
 }
 
-// the instantiation of (kernel kind, third slot): X(KIND, AMS) is expanded with compile-time arguments
-#define OPT_DISPATCH(kind, ams, X)                                                    \
-  switch (kind) {                                                                     \
-    case OPT_ADAM: if (ams) { X(OPT_ADAM, true); } else { X(OPT_ADAM, false); } break; \
-    case OPT_LION: X(OPT_LION, false); break;                                         \
-    case OPT_ADABELIEF: if (ams) { X(OPT_ADABELIEF, true); } else { X(OPT_ADABELIEF, false); } break; \
-    case OPT_SGD: X(OPT_SGD, false); break;                                           \
-    case OPT_RMSPROP: if (ams) { X(OPT_RMSPROP, true); } else { X(OPT_RMSPROP, false); } break; \
-    case OPT_ADAGRAD: X(OPT_ADAGRAD, false); break;                                   \
-    case OPT_ADAMAX: X(OPT_ADAMAX, false); break;                                     \
-    default: if (ams) { X(OPT_ADAMW, true); } else { X(OPT_ADAMW, false); } break;     \
+// the instantiation of (kernel kind, third slot, weight average): X(KIND, AMS, EMA) is expanded with compile-time arguments
+#define OPT_DISPATCH_E(kind, ams, E, X)                                                     \
+  switch (kind) {                                                                           \
+    case OPT_ADAM: if (ams) { X(OPT_ADAM, true, E); } else { X(OPT_ADAM, false, E); } break; \
+    case OPT_LION: X(OPT_LION, false, E); break;                                            \
+    case OPT_ADABELIEF: if (ams) { X(OPT_ADABELIEF, true, E); } else { X(OPT_ADABELIEF, false, E); } break; \
+    case OPT_SGD: X(OPT_SGD, false, E); break;                                              \
+    case OPT_RMSPROP: if (ams) { X(OPT_RMSPROP, true, E); } else { X(OPT_RMSPROP, false, E); } break; \
+    case OPT_ADAGRAD: X(OPT_ADAGRAD, false, E); break;                                      \
+    case OPT_ADAMAX: X(OPT_ADAMAX, false, E); break;                                        \
+    default: if (ams) { X(OPT_ADAMW, true, E); } else { X(OPT_ADAMW, false, E); } break;     \
   }
+#define OPT_DISPATCH(kind, ams, ema, X) \
+  if (ema) { OPT_DISPATCH_E(kind, ams, true, X) } else { OPT_DISPATCH_E(kind, ams, false, X) }
 static bool second_slot(int kind) { return kind != OPT_LION && kind != OPT_SGD && kind != OPT_ADAGRAD; }
 
 // kind: the kernel kind (kernel_kind: OPT_* with OPT_ADAMW), ams: the third slot is in use (third_slot).  The slots a kind does not use
-// are not touched (may be null)
-void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, const OptArgs& a,
+// are not touched (may be null).  ema: the weight average (P floats), null = off
+void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, float* ema, long P, const OptArgs& a,
                 hipStream_t st) {
   if (!second_slot(kind)) v = nullptr;
   if (!ams) vhat = nullptr;
   long n4; dim3 grid;
-  stream_shape(kind, theta, g, m, v, vhat, P, &n4, &grid);
-#define X(K, A) hipLaunchKernelGGL((k_opt<K, A>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a)
-  OPT_DISPATCH(kind, ams, X)
+  stream_shape(kind, theta, g, m, v, vhat, ema, P, &n4, &grid);
+#define X(K, A, E) hipLaunchKernelGGL((k_opt<K, A, E>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, a, ema)
+  OPT_DISPATCH(kind, ams, ema != nullptr, X)
 #undef X
 }
 
 void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g,
-                       long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st) {
+                       long P, float* theta, float* m, float* v, float* vhat, float* ema, const OptArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)((P + 63) / 64)), block(512);
-#define X(K, A) \
-  hipLaunchKernelGGL((k_reduce_opt<K, A>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, a)
-  OPT_DISPATCH(kind, ams, X)
+#define X(K, A, E)                                                                                                                   \
+  hipLaunchKernelGGL((k_reduce_opt<K, A, E>), grid, block, 0, st, partial, pstride, rows, loss_partial, nloss, g, P, theta, m, v, vhat, \
+                     a, ema)
+  OPT_DISPATCH(kind, ams, ema != nullptr, X)
 #undef X
 }
 
-void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
+void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, float* ema, long P, OptDev* od,
                     hipStream_t st) {
   if (!second_slot(kind)) v = nullptr;
   if (!ams) vhat = nullptr;
   long n4; dim3 grid;
-  stream_shape(kind, theta, g, m, v, vhat, P, &n4, &grid);
+  stream_shape(kind, theta, g, m, v, vhat, ema, P, &n4, &grid);
   const OptDev* o = od;
-#define X(K, A) hipLaunchKernelGGL((k_opt_dev<K, A>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o)
-  OPT_DISPATCH(kind, ams, X)
+#define X(K, A, E) hipLaunchKernelGGL((k_opt_dev<K, A, E>), grid, dim3(256), 0, st, theta, g, m, v, vhat, P, n4, o, ema)
+  OPT_DISPATCH(kind, ams, ema != nullptr, X)
 #undef X
   hipLaunchKernelGGL(k_opt_step_inc, dim3(1), dim3(1), 0, st, od);
 }

@@ -277,6 +277,7 @@ extern "C" int nif_set_opt_state(nif_ctx* c, const float* mh, const float* vh, i
   // fresh slots (Adagrad's accumulator is still to be initialised): iteration 0 and nothing but zeros, what compile() of a new optimizer writes
   c->slots_fresh = step == 0;
   for (int64_t i = 0; i < n && c->slots_fresh; ++i) c->slots_fresh = mh[i] == 0.f && vh[i] == 0.f;
+  c->ema_valid = false;      // (what fit() calls for a freshly compiled optimizer: the next EMA step seeds the average again)
   return NIF_OK;
 }
 
@@ -1991,7 +1992,7 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
   // weights the previous replay left behind)
   c->packed = false; c->packed32 = false; c->packed_p32 = false;
   HIPCHK(hipStreamBeginCapture(c->st, hipStreamCaptureModeRelaxed));
-  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step; c->cap_kind = -1; c->cap_ams = false; c->cap_gt = 0;
+  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step; c->cap_kind = -1; c->cap_ams = false; c->cap_ema = false; c->cap_gt = 0;
   return NIF_OK;
 }
 extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
@@ -2010,6 +2011,7 @@ extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   if (e != hipSuccess) { (void)hipGetLastError(); return fail(NIF_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
   c->graphs.push_back(ex); c->graph_steps.push_back(c->cap_steps);
   c->graph_kind.push_back(c->cap_kind); c->graph_ams.push_back(c->cap_ams ? 1 : 0); c->graph_gt.push_back((char)c->cap_gt);
+  c->graph_ema.push_back(c->cap_ema ? 1 : 0);
   *graph_id = (int32_t)c->graphs.size() - 1;
   return NIF_OK;
 }
@@ -2159,8 +2161,10 @@ static int opt_check(const nif_opt* o) {
   if (sk != NIF_SCHED_POLYNOMIAL && o->sched_b != 0.f) return fail(NIF_ERR_INVALID, "nif_opt: sched_b is PolynomialDecay's power");
   return NIF_OK;
 }
-static OptDev opt_dev_of(const nif_opt* o, long step) {
+// c: the context whose weight-averaging state the step reads (null: none, nif_opt_scalars)
+static OptDev opt_dev_of(const nif_ctx* c, const nif_opt* o, long step) {
   OptDev d;
+  d.ema_mom = c ? c->ema_mom : 0.f; d.ema_freq = c && c->opt_ema > 0 ? c->opt_ema : 0;
   d.kind = o->kind; d.flags = o->flags; d.lr = o->lr; d.beta1 = o->beta1; d.beta2 = o->beta2; d.eps = o->eps; d.wd = o->weight_decay;
   d.decay = o->decay; d.sma_threshold = o->sma_threshold; d.warmup_proportion = o->warmup_proportion; d.min_lr = o->min_lr;
   d.total_steps = (long)o->total_steps; d.step = step;
@@ -2188,10 +2192,24 @@ static int ensure_vhat(nif_ctx* c) {
   c->vhat = std::move(vh);
   return NIF_OK;
 }
+// the weight average (slot 3) exists and holds values.  seed: it starts as a device copy of theta as it stands (Keras creates the
+// average with the variable's value); else the caller fills it (nif_set_opt_slot)
+static int ensure_ema(nif_ctx* c, bool seed) {
+  if (c->ema && c->ema_valid) return NIF_OK;
+  if (c->capturing) return fail(NIF_ERR_STATE, "the weight average (slot 3) does not exist yet: run one eager step or nif_set_opt_slot(3, ...) before the capture");
+  if (!c->ema) {
+    DevBuf<float> av;
+    const int rc = av.alloc(c->P); if (rc) return rc;
+    c->ema = std::move(av);
+  }
+  if (seed) HIPCHK(hipMemcpyAsync(c->ema, c->theta, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToDevice, c->st));
+  c->ema_valid = true;
+  return NIF_OK;
+}
 extern "C" int nif_opt_scalars(const nif_opt* o, int64_t t, double* out) {
   if (!o || !out || t < 1) return fail(NIF_ERR_INVALID, "bad argument");
   const int rc = opt_check(o); if (rc) return rc;
-  const OptScalars s = opt_scalars(opt_dev_of(o, 0), (long)t);
+  const OptScalars s = opt_scalars(opt_dev_of(nullptr, o, 0), (long)t);
   out[0] = s.lr; out[1] = s.bc1; out[2] = s.bc2; out[3] = s.r; out[4] = (double)s.div;
   return NIF_OK;
 }
@@ -2210,10 +2228,14 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
   const bool ams = opt_ams(opt);
   const int kk = opt_kk(opt);
+  const bool ema = c->opt_ema != 0;
   if (c->capturing && c->cap_kind >= 0 && (c->cap_kind != kk || c->cap_ams != ams))
     return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
+  if (c->capturing && c->cap_kind >= 0 && c->cap_ema != ema)
+    return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps recorded with weight averaging (\"ema\") " + (c->cap_ema ? "on" : "off") + " (one setting per graph)");
   HIPCHK(hipSetDevice(c->dev));
   if (ams) { const int rc = ensure_vhat(c); if (rc) return rc; }
+  if (ema) { const int rc = ensure_ema(c, true); if (rc) return rc; }      // (seeded with theta before this step's update)
   if (opt->kind == NIF_OPT_ADAGRAD && c->slots_fresh && opt->init_acc != 0.f) { const int rc = adagrad_fill(c, opt->init_acc); if (rc) return rc; }
   c->slots_fresh = false;
   // the step's row reduction and the update in ONE launch -- not with a gradient transform set: a norm needs every column of the
@@ -2227,17 +2249,19 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
     if (c->gt_on) gt_run(c);
   }
   c->step += 1;
-  const OptDev d = opt_dev_of(opt, c->step - 1);
-  const OptArgs a = opt_args(d, opt_scalars(d, c->step));
+  const OptDev d = opt_dev_of(c, opt, c->step - 1);
+  OptArgs a = opt_args(d, opt_scalars(d, c->step));
+  a.ema_ow = ema && ema_overwrite(c->step, d.ema_freq) ? 1 : 0;
+  float* const av = ema ? (float*)c->ema : nullptr;
   if (fused) {
     launch_reduce_opt(kk, ams, c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->theta, c->m,
-                      c->v, c->vhat, a, c->st);
+                      c->v, c->vhat, av, a, c->st);
   } else if (c->capturing) {
-    launch_opt_dev(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, c->opt_dev, c->st);
-    c->cap_steps += 1; c->cap_kind = kk; c->cap_ams = ams;
+    launch_opt_dev(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, av, c->P, c->opt_dev, c->st);
+    c->cap_steps += 1; c->cap_kind = kk; c->cap_ams = ams; c->cap_ema = ema;
   } else {
     ProfScope p_(c, NIF_PROF_ADAM);
-    launch_opt(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, c->P, a, c->st);
+    launch_opt(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, av, c->P, a, c->st);
   }
   HIPCHK(hipGetLastError());
   theta_stepped(c);
@@ -2263,11 +2287,15 @@ static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const 
   if (c->capturing) return fail(NIF_ERR_STATE, std::string(who) + " while capturing");
   if (gt_launches(c) > c->graph_gt[graph_id])
     return fail(NIF_ERR_STATE, std::string(who) + ": the context's gradient transform needs launches this graph did not record (set it before the capture)");
+  const bool ema = c->opt_ema != 0;
+  if (c->graph_kind[graph_id] >= 0 && (c->graph_ema[graph_id] != 0) != ema)
+    return fail(NIF_ERR_STATE, std::string(who) + ": the graph was recorded with weight averaging (\"ema\") " + (c->graph_ema[graph_id] ? "on" : "off") + ", the context has it " + (ema ? "on" : "off") + " (set it before the capture)");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
+  if (ema && c->graph_kind[graph_id] >= 0) { const int rce = ensure_ema(c, true); if (rce) return rce; }      // (reset by nif_set_opt_state since the capture: seeded again, at the recorded address)
   { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }      // (the replay overwrites grad[P]: a deferred accumulation takes the loss of the step it was called for)
   HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
-  *c->opt_host = opt_dev_of(opt, c->step);
+  *c->opt_host = opt_dev_of(c, opt, c->step);
   HIPCHK(hipMemcpyAsync(c->opt_dev, c->opt_host, sizeof(OptDev), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipGraphLaunch(c->graphs[graph_id], c->st));
   c->step += c->graph_steps[graph_id];
@@ -2292,27 +2320,29 @@ extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt*
   return graph_replay(c, graph_id, opt, "nif_graph_launch_opt");
 }
 extern "C" int nif_get_opt_slot(nif_ctx* c, int32_t slot, float* host, int64_t n) {
-  if (!c || !host || slot < 0 || slot > 2) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat)");
+  if (!c || !host || slot < 0 || slot > 3) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat, 3 weight average)");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
-  float* src = slot == 0 ? c->m : slot == 1 ? c->v : c->vhat;
+  float* src = slot == 0 ? c->m : slot == 1 ? c->v : slot == 2 ? c->vhat : c->ema;
+  if (slot == 3 && !c->ema_valid) src = nullptr;      // (reset by nif_set_opt_state: zeros until the next step seeds it)
   if (!src) { memset(host, 0, sizeof(float) * (size_t)n); return NIF_OK; }
   HIPCHK(hipMemcpyAsync(host, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
 extern "C" int nif_set_opt_slot(nif_ctx* c, int32_t slot, const float* host, int64_t n) {
-  if (!c || !host || slot < 0 || slot > 2) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat)");
+  if (!c || !host || slot < 0 || slot > 3) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat, 3 weight average)");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
   if (c->capturing) return fail(NIF_ERR_STATE, "nif_set_opt_slot while capturing");
   HIPCHK(hipSetDevice(c->dev));
   TAIL_FLUSH(c)
   if (slot == 2) { const int rc = ensure_vhat(c); if (rc) return rc; }
-  float* dst = slot == 0 ? c->m : slot == 1 ? c->v : c->vhat;
+  if (slot == 3) { const int rc = ensure_ema(c, false); if (rc) return rc; }
+  float* dst = slot == 0 ? c->m : slot == 1 ? c->v : slot == 2 ? c->vhat : c->ema;
   HIPCHK(hipMemcpyAsync(dst, host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
-  c->slots_fresh = false;
+  if (slot != 3) c->slots_fresh = false;      // (the average is no slot of a kind: Adagrad's accumulator is still to be written)
   return NIF_OK;
 }
 
@@ -2454,6 +2484,20 @@ extern "C" int nif_set_option(nif_ctx* c, const char* key, int32_t value) {
   if (strcmp(key, "side_pnet") == 0) { c->opt_side_pnet = value != 0; return NIF_OK; }   // ParameterNet adjoint on the second stream
   if (strcmp(key, "pipe_chunk") == 0) { c->opt_pipe_chunk = value; return NIF_OK; }   // points per chunk, 0 = off, -1 = default
   if (strcmp(key, "pipe_wgs") == 0) { c->opt_pipe_wgs = value; return NIF_OK; }       // workgroups of the fused kernel per chunk
+  // weight averaging behind every optimizer step of the context (Keras' use_ema; read by opt_step / graph_replay at step time)
+  const bool k_ema = strcmp(key, "ema") == 0;
+  if (k_ema || strcmp(key, "ema_momentum_bits") == 0) {
+    if (c->capturing) return fail(NIF_ERR_STATE, std::string("nif_set_option(\"") + key + "\"): not inside a graph capture");
+    if (k_ema) {
+      if (value < -1) return fail(NIF_ERR_INVALID, "nif_set_option(\"ema\"): 0 off, -1 on, f >= 1 on and overwrite every f steps");
+      c->opt_ema = value;
+      return NIF_OK;
+    }
+    float mom; memcpy(&mom, &value, sizeof(mom));
+    if (!(mom >= 0.f && mom <= 1.f)) return fail(NIF_ERR_INVALID, "nif_set_option(\"ema_momentum_bits\"): the bit pattern of a float32 within [0, 1]");
+    c->ema_mom = mom;
+    return NIF_OK;
+  }
   return fail(NIF_ERR_INVALID, std::string("unknown option ") + key);
 }
 

@@ -105,6 +105,11 @@ struct nif_ctx {
   DevBuf<float> vhat;          // the third optimizer slot (amsgrad's vhat, centered RMSprop's a), allocated on first use
   bool slots_fresh = true;     // m, v are zero and the iteration count 0: Adagrad's first step writes its initial accumulator
   int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
+  // weight averaging behind every optimizer step (Keras' use_ema; nif_set_option "ema" / "ema_momentum_bits"): opt_ema 0 off, -1 on,
+  // f >= 1 on and theta overwritten by the average every f steps.  ema is optimizer slot 3, allocated on first use and never freed
+  // (captured graphs hold its address); ema_valid false: the next step (or replay) seeds it with theta (nif_set_opt_state resets it).
+  // cap_ema / graph_ema: whether the steps of a capture were recorded with the average (a graph is replayed only with that setting)
+  int opt_ema = 0; float ema_mom = 0.99f; DevBuf<float> ema; bool ema_valid = false; bool cap_ema = false; std::vector<char> graph_ema;
   // magnitude pruning (nif_prune_*): the segment table (host copy: the k of the last update), its span [prune_lo, prune_hi), a byte mask
   // over the whole of theta (1 outside the segments), the thresholds and the select's histograms / per-segment state
   std::vector<PruneSeg> prune_segs; long prune_nblk = 0, prune_lo = 0, prune_hi = 0;

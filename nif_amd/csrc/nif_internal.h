@@ -272,10 +272,13 @@ enum { OPT_ADAM = 0, OPT_LION = 1, OPT_ADABELIEF = 2, OPT_SGD = 3, OPT_RMSPROP =
 enum { OPT_RECTIFY = 1, OPT_AMSGRAD = 2, OPT_NESTEROV = 4, OPT_CENTERED = 8, OPT_DECOUPLED_WD = 16 };
 enum { SCHED_NONE = 0, SCHED_EXPONENTIAL = 1, SCHED_INVERSE_TIME = 2, SCHED_COSINE = 3, SCHED_POLYNOMIAL = 4, SCHED_KIND_MASK = 0xff,
        SCHED_STAIRCASE = 0x100, SCHED_CYCLE = 0x200 };
-// the fields behind `step` are the schedule's and Adagrad's: all zero for the kinds and calls that do not know them
+// the fields behind `step` are the schedule's and Adagrad's: all zero for the kinds and calls that do not know them.  ema_mom /
+// ema_freq: the context's weight averaging (nif_set_option "ema_momentum_bits" / "ema"; ema_freq 0 = never overwrite), read by the
+// EMA instantiations alone
 struct OptDev {
   int kind, flags; float lr, beta1, beta2, eps, wd, decay, sma_threshold, warmup_proportion, min_lr; long total_steps; long step;
   int sched, decay_steps; float sched_a, sched_b;
+  float ema_mom; int ema_freq;
 };
 struct OptScalars { double lr, bc1, bc2, r; int div; };
 // the kernel instantiation of a step and whether it has a third slot (Adam / AdaBelief amsgrad's vhat, centered RMSprop's mean gradient)
@@ -339,7 +342,11 @@ __host__ __device__ inline OptScalars opt_scalars(const OptDev& o, long t_) {
 // what one update kernel receives (floats; the fp64 scalars rounded once).  lr: Adam's step size lr_t = lr sqrt(1 - b2^t) / (1 - b1^t),
 // Adamax's lr / (1 - b1^t), else the step's learning rate; lr0: that learning rate without a bias correction (AdamW's decay).  SGD and
 // RMSprop: b1 = momentum, RMSprop b2 = rho; div: SGD 0 no momentum, 1 momentum, 2 nesterov; RMSprop 1 with momentum > 0
-struct OptArgs { float lr, b1, b2, eps, wd, bc1, bc2, r; int div; float lr0; };
+// ema_mom, ema_ow: the weight average's momentum and whether this step writes the average back over theta (ema_overwrite)
+struct OptArgs { float lr, b1, b2, eps, wd, bc1, bc2, r; int div; float lr0; float ema_mom; int ema_ow; };
+// Keras' use_ema (restated from Keras 2.11's documentation, not pinned by TensorFlow): with ema_overwrite_frequency f >= 1 the step
+// that completes iteration t (Keras' iterations + 1, the t of opt_scalars) overwrites the weights by their average when t % f == 0
+__host__ __device__ inline bool ema_overwrite(long t, int freq) { return freq >= 1 && t % (long)freq == 0; }
 __host__ __device__ inline OptArgs opt_args(const OptDev& o, const OptScalars& s) {
   OptArgs a;
   a.lr = (float)(o.kind == OPT_ADAM ? s.lr * sqrt(s.bc2) / s.bc1 : o.kind == OPT_ADAMAX ? s.lr / s.bc1 : s.lr);
@@ -348,13 +355,15 @@ __host__ __device__ inline OptArgs opt_args(const OptDev& o, const OptScalars& s
   if (o.kind == OPT_SGD) a.div = o.beta1 != 0.f ? ((o.flags & OPT_NESTEROV) ? 2 : 1) : 0;
   if (o.kind == OPT_RMSPROP) a.div = o.beta1 > 0.f ? 1 : 0;
   a.lr0 = (float)s.lr;
+  a.ema_mom = o.ema_mom; a.ema_ow = 0;      // (ema_ow: set by the EMA forms from the step's count, ema_overwrite)
   return a;
 }
-void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, const OptArgs& a,
+// ema: the weight average, null = off (the EMA-off instantiations)
+void launch_opt(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, float* ema, long P, const OptArgs& a,
                 hipStream_t st);
 void launch_reduce_opt(int kind, bool ams, const float* partial, long pstride, int rows, const float* loss_partial, int nloss, float* g,
-                       long P, float* theta, float* m, float* v, float* vhat, const OptArgs& a, hipStream_t st);
-void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, long P, OptDev* od,
+                       long P, float* theta, float* m, float* v, float* vhat, float* ema, const OptArgs& a, hipStream_t st);
+void launch_opt_dev(int kind, bool ams, float* theta, const float* g, float* m, float* v, float* vhat, float* ema, long P, OptDev* od,
                     hipStream_t st);
 // the gradient transform in front of the update (k_gradtf.hip, nif_set_grad_transform).  GtDev: a nif_grad_transform in device memory,
 // read by the kernels of eager and captured steps alike.  GtBlk: one work block -- 64 columns of a matrix over all its rows, or a chunk

@@ -434,7 +434,7 @@ class Engine(object):
         check(self.lib.nif_graph_launch_opt(self.ctx, int(gid), C.byref(opt)))
 
     def get_opt_slot(self, slot):
-        """slot 0 m, 1 v, 2 vhat (zeros before AMSGrad first used it)"""
+        """slot 0 m, 1 v, 2 vhat (zeros before AMSGrad first used it), 3 the weight average of set_ema (zeros before it exists)"""
         out = np.empty((self.n_params,), dtype=np.float32)
         check(self.lib.nif_get_opt_slot(self.ctx, int(slot), ptr(out), out.size))
         return out
@@ -442,6 +442,20 @@ class Engine(object):
     def set_opt_slot(self, slot, values):
         values = _f32(values)
         check(self.lib.nif_set_opt_slot(self.ctx, int(slot), ptr(values), values.size))
+
+    # Keras' use_ema behind every optimizer step of this context (nif_set_option "ema_momentum_bits" / "ema"; k_opt.hip)
+    def set_ema(self, momentum=None, overwrite_frequency=None):
+        """momentum None: off.  Else every optimizer step of any kind also updates average = momentum average + (1 - momentum) theta
+        (slot 3; created as a copy of theta at the first such step), and with overwrite_frequency f >= 1 every f-th step writes the
+        average back over theta.  Context state until set again: Model.fit sets it from its optimizer and clears it when it returns."""
+        if momentum is None:
+            self.set_option("ema", 0)
+            return
+        f = -1 if overwrite_frequency is None else int(overwrite_frequency)
+        if f < 1 and overwrite_frequency is not None:
+            raise ValueError("set_ema(overwrite_frequency=%r): None or an integer >= 1" % (overwrite_frequency,))
+        self.set_option("ema_momentum_bits", int(np.array([momentum], dtype=np.float32).view(np.int32)[0]))
+        self.set_option("ema", f)
 
     # gradient transform in front of every optimizer step (include/nif_hip.h nif_set_grad_transform; k_gradtf.hip)
     def set_grad_transform(self, spec=None, **kwargs):

@@ -14,7 +14,7 @@ from . import _lib
 from . import distributed as dist
 from .data import ShardBatches
 from .engine import Engine
-from .optimizers import Adam, get as get_optimizer, grad_transform_of, slot_layout
+from .optimizers import Adam, ema_of, get as get_optimizer, grad_transform_of, slot_layout
 from .spec import Spec
 
 _global_rng = [np.random.default_rng()]
@@ -138,9 +138,14 @@ class Model(object):
         """Flat parameters in Keras variable order + Adam slots, as .npz (the reference's TF-checkpoint
         format, README.md:179-195, is a TensorFlow artefact and out of scope).  Compiled with another optimizer than plain Adam: the
         weights + opt_kind, opt_step and that optimizer's slots by index (opt_m slot 0; opt_v slot 1; opt_vhat slot 2 -- amsgrad's
-        vhat, centered RMSprop's mean gradient) and, for AdamW and centered RMSprop, opt_flags instead."""
+        vhat, centered RMSprop's mean gradient) and, for AdamW and centered RMSprop, opt_flags instead.  Compiled with use_ema: opt_ema,
+        the weights' moving average (slot 3), in either layout once it exists (the slot reads all zeros before)."""
         ws = self.get_weights()
         arrs = {"w%03d" % i: w for i, w in enumerate(ws)}
+        if ema_of(self.optimizer) is not None:
+            avg = self._engine.get_opt_slot(3)
+            if avg.any():
+                arrs["opt_ema"] = avg
         path = filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz"
         names = np.array([nm for nm, _ in self._engine.shapes])
         opt = self.optimizer
@@ -178,10 +183,12 @@ class Model(object):
         n = len(self._engine.shapes)
         self.set_weights([d["w%03d" % i] for i in range(n)])
         opt = self.optimizer
+        restored = False
         if "adam_m" in d:
             if opt is None or self._plain_adam_slots(opt):
                 self._engine.set_opt_state(d["adam_m"], d["adam_v"], int(d["adam_step"]))
                 self._fresh_slots = False
+                restored = True
             else:
                 warnings.warn("load_weights: the file holds Adam slots, the model is compiled with %s: weights loaded, "
                               "optimizer state not restored" % type(opt).__name__)
@@ -195,10 +202,13 @@ class Model(object):
                 if ams:
                     e.set_opt_slot(2, d["opt_vhat"])
                 self._fresh_slots = False
+                restored = True
             else:
                 warnings.warn("load_weights: the file holds the slots of another optimizer (kind %d%s) than the compiled one (%s): "
                               "weights loaded, optimizer state not restored"
                               % (kind, ", amsgrad" if ams else "", type(opt).__name__ if opt is not None else "none"))
+        if restored and "opt_ema" in d and ema_of(opt) is not None:      # (behind the other slots: set_opt_state resets the average)
+            self._engine.set_opt_slot(3, d["opt_ema"])
         self._load_extra(d)
 
     # ---- inference -------------------------------------------------------------------------------
@@ -395,6 +405,10 @@ class Model(object):
         if kwargs:
             raise NotImplementedError("fit(%s): not on the built hot path (in-memory x, y, sample_weight only)"
                                       % ", ".join(sorted(kwargs)))
+        ema = ema_of(self.optimizer)
+        if ema is not None and getattr(self, "_is_pruned", False):
+            raise NotImplementedError("fit() of a pruned model (nif_amd.sparsity) with %s(use_ema=True): not built (the average of "
+                                      "unmasked weights written back over masked ones)" % type(self.optimizer).__name__)
         s = self._owner._spec
         e = self._engine
         kinds = getattr(self, "_metrics", [])
@@ -408,11 +422,16 @@ class Model(object):
         if grad_tf is not None:
             e.set_grad_transform(grad_tf)
         try:
+            # Keras' use_ema: engine state for the length of this call as well (every optimizer step of the context keeps the average)
+            if ema is not None:
+                e.set_ema(*ema)
             return self._fit(e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch,
                              validation_data, steps_per_epoch)
         finally:
             if grad_tf is not None:
                 e.set_grad_transform(None)
+            if ema is not None:
+                e.set_ema(None)
 
     def _fit(self, e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch, validation_data,
              steps_per_epoch):
@@ -424,6 +443,8 @@ class Model(object):
             e.set_opt_state(z if acc0 is None else np.full_like(z, acc0), z, 0)
             if slot_layout(self.optimizer)[3]:
                 e.set_opt_slot(2, z)
+            if ema_of(self.optimizer) is not None:
+                e.set_opt_slot(3, e.get_flat())      # Keras creates the average with the variable's value (exists before a captured epoch)
             self._fresh_slots = False
         ncol = s.pi_dim + s.si_dim
         shard = x if isinstance(x, ShardBatches) else None
@@ -653,6 +674,10 @@ class Model(object):
             e.sync()
             for arr in owned:
                 arr.free()
+        # Keras' fit: the weights become their average behind the last epoch, ahead of on_train_end; validation and metrics above saw
+        # the current weights.  Not when no epoch ran, not when an exception ended the call
+        if ema_of(self.optimizer) is not None and epochs > initial_epoch:
+            self.optimizer.finalize_variable_values(self)
         for cb in callbacks:
             if hasattr(cb, "on_train_end"):
                 cb.on_train_end({})

@@ -2,7 +2,9 @@
 SURVEY a-11); the reference's Lion and AdaBeliefOptimizer (nif/optimizers/__init__.py) and Keras 2.11's SGD, RMSprop, Adagrad,
 Adamax, AdamW and amsgrad Adam are the other kinds; Adam and the Keras kinds take a nif_amd.optimizers.schedules.* object as
 learning_rate.  All update on the k_opt.hip kernels (k_opt, k_reduce_opt, k_opt_dev).  The Keras kinds' formulas are restated from
-Keras 2.11 and are not pinned by a TensorFlow run (parity unpinned by TensorFlow)."""
+Keras 2.11 and are not pinned by a TensorFlow run (parity unpinned by TensorFlow).  use_ema / ema_momentum / ema_overwrite_frequency
+of Adam and the Keras kinds: the weights' moving average, kept by the same kernels behind every update (slot 3 of the engine;
+semantics restated from Keras 2.11's documentation, unpinned by TensorFlow)."""
 import numbers
 
 import numpy as np
@@ -39,9 +41,18 @@ class _KerasOptimizer(object):
         if "lr" in kwargs:
             learning_rate = kwargs.pop("lr")
         kwargs.pop("jit_compile", None)            # (nothing to compile here)
-        if kwargs.pop("use_ema", False):
-            raise NotImplementedError("%s(use_ema=True): not built" % cls)
-        kwargs.pop("ema_momentum", None); kwargs.pop("ema_overwrite_frequency", None)
+        # Keras' weight averaging (use_ema): validated as Keras' optimizer base does, and only when it is on
+        self.use_ema = bool(kwargs.pop("use_ema", False))
+        self.ema_momentum = kwargs.pop("ema_momentum", 0.99)
+        self.ema_overwrite_frequency = kwargs.pop("ema_overwrite_frequency", None)
+        if self.use_ema:
+            mom, f = self.ema_momentum, self.ema_overwrite_frequency
+            if isinstance(mom, bool) or not isinstance(mom, (numbers.Real, np.floating, np.integer)) or not 0.0 <= float(mom) <= 1.0:
+                raise ValueError("`ema_momentum` must be in the range [0, 1]. Received: ema_momentum=%r" % (mom,))
+            if f is not None and (isinstance(f, bool) or not isinstance(f, (int, np.integer)) or f < 1):
+                raise ValueError("`ema_overwrite_frequency` must be an integer >= 1 or None. Received: ema_overwrite_frequency=%r" % (f,))
+            self.ema_momentum = float(mom)
+            self.ema_overwrite_frequency = None if f is None else int(f)
         if kwargs.pop("decay", 0):
             raise NotImplementedError("%s(decay=...): Keras 2.11's optimizers take a schedule instead (schedules.InverseTimeDecay)" % cls)
         self._unknown_kwargs(kwargs)
@@ -100,6 +111,7 @@ class _KerasOptimizer(object):
         cfg = {"name": self.name, "learning_rate": lr}
         cfg.update(self._hyper())
         cfg.update({"clipnorm": self.clipnorm, "clipvalue": self.clipvalue, "global_clipnorm": self.global_clipnorm})
+        cfg.update({"use_ema": self.use_ema, "ema_momentum": self.ema_momentum, "ema_overwrite_frequency": self.ema_overwrite_frequency})
         return cfg
 
     @classmethod
@@ -112,6 +124,22 @@ class _KerasOptimizer(object):
 
     def _fill(self, o):
         """the kind's own fields of the nif_opt"""
+
+    def finalize_variable_values(self, var_list):
+        """Keras' optimizer.finalize_variable_values(model.trainable_variables): the weights become their moving average (slot 3 of
+        the engine).  var_list: the model's trainable_variables (the Variable objects know their model) or the model itself.  Nothing
+        happens when use_ema is false; Model.fit calls this after its last epoch."""
+        if not self.use_ema:
+            return
+        model = var_list
+        if isinstance(var_list, (list, tuple)):
+            if not var_list:
+                return
+            model = getattr(var_list[0], "_model", None)
+        e = getattr(model, "_engine", None)
+        if e is None:
+            raise TypeError("finalize_variable_values(var_list): model.trainable_variables or the model")
+        e.set_flat(e.get_opt_slot(3))
 
     def as_opt(self):
         o = _lib.nif_opt()
@@ -270,6 +298,19 @@ class Nadam(object):
     def __init__(self, *args, **kwargs):
         raise NotImplementedError("Nadam: not built (its running product of the momentum schedule is state the optimizer step does "
                                   "not carry); built are Adam, AdamW, SGD, RMSprop, Adagrad, Adamax, Lion and AdaBeliefOptimizer")
+
+
+def ema_overwrite(t, frequency):
+    """whether the step that completes iteration t (1-based) overwrites the weights by their average, for ema_overwrite_frequency
+    `frequency` (None: never): every `frequency` steps, the rule of the kernels (nif_internal.h ema_overwrite)"""
+    return frequency is not None and int(frequency) >= 1 and int(t) % int(frequency) == 0
+
+
+def ema_of(opt):
+    """None, or Engine.set_ema's (momentum, overwrite_frequency) of an optimizer compiled with use_ema"""
+    if not getattr(opt, "use_ema", False):
+        return None
+    return float(opt.ema_momentum), opt.ema_overwrite_frequency
 
 
 def slot_layout(opt):
