@@ -161,6 +161,7 @@ void* nif_params_dev(nif_ctx* ctx);      /* device float[P] */
  * NIFMultiScaleLastLayerParameterized.call :1044-1068.   xin [B, pi+si] -> u [B, so] */
 int nif_forward(nif_ctx* ctx, const float* xin_host, int64_t B, float* u_host);
 int nif_forward_dev(nif_ctx* ctx, const float* xin_dev, int64_t B, float* u_dev);
+/* Snapshot-wise model.predict (T snapshots, one ParameterNet input or latent per whole mesh): include/nif_hip_snapshots.h */
 /* model_p_to_lr().predict(p): model.py:406-420 (last-layer class: :1070-1083).  p [B,pi] -> [B,r] */
 int nif_pnet_latent(nif_ctx* ctx, const float* p_host, int64_t B, float* lr_host);
 /* model_x_to_phi().predict(x) of the last-layer class: model.py:1085-1104.  x [B,si] -> phi [B,so,r] */
@@ -446,6 +447,8 @@ int nif_f64_grad_read(nif_ctx* ctx, double* loss_out_or_null, double* grad_host_
  * one-launch small-batch step, the row reduction deferred to nif_adam_step_dev (which then runs it fused with the update: the
  * [grad | loss] buffer is complete after ANY other call of this library on the context -- nif_grad_dev included -- and after the
  * update; a caller that reads the buffer through a pointer it cached earlier, without such a call, sets "fuse_tail" to 0).
+ * "snapshot_image_bytes": device bytes of combined per-snapshot nets that nif_forward_snapshots* holds at once (it walks the snapshots
+ * in chunks of that many; 0, the default: 256 MiB; at least one snapshot per chunk; the results do not depend on it).
  * Weight averaging (Keras' use_ema; restated from Keras 2.11's documentation, unpinned by TensorFlow) is context state set here:
  *   "ema": 0 off (default), -1 on, f >= 1 on and theta overwritten by the average every f steps (the steps that complete an
  *     iteration t with t % f == 0); any other value NIF_ERR_INVALID;

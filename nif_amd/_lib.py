@@ -190,6 +190,13 @@ SIGNATURES = {
 _lib = None
 
 
+# include/nif_hip_snapshots.h, one to one (bound by load() with the table above)
+SNAPSHOT_SIGNATURES = {
+    "nif_forward_snapshots": (C.c_int, [_CTX, _VP, C.c_int32, C.c_int64, _VP, C.POINTER(C.c_int64), C.c_int64, _VP]),
+    "nif_forward_snapshots_dev": (C.c_int, [_CTX, _VP, C.c_int32, C.c_int64, _VP, C.POINTER(C.c_int64), C.c_int64, _VP]),
+}
+
+
 def load():
     """dlopen libnif_hip.so and bind every symbol of include/nif_hip.h.  Raises if it is absent."""
     global _lib
@@ -200,7 +207,7 @@ def load():
             "libnif_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SNAPSHOT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -45,9 +45,26 @@
 // r3 (VALU diet): omega_0 is folded into the packed planes and into the LDS image of the first layer, the
 // per-plane biases start the MFMA accumulators (no bias FMAs, no zeroing: acc = b^(r) + sum_k zt_k (b^(k) + h (w0 M^(k)))),
 // zero-started chains take the inline constant as C, the chunk stream is a running pointer with a phase counter.
-template <int NBL, bool TRAIN, int ACT, int MODE, bool SGN, bool LL, int PR = 0>
+//
+// SNAP (snapshot-wise inference, k_snap.hip; forward only, r = 0, not LL): blockIdx.y is a snapshot with a combined dense net of its
+// own (SNetArgs.snap_*).  The workgroup rebases its arguments onto that snapshot once and then runs the code below as on a batch of the
+// snapshot's points: tiles never straddle snapshots, the last tile of a snapshot is partly valid.  Off (the default) adds nothing.
+template <int NBL, bool TRAIN, int ACT, int MODE, bool SGN, bool LL, int PR = 0, bool SNAP = false>
 __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && TRAIN && MODE == 0) ? NIF_S4_OCC_LL8 : NIF_S4_OCC_WIDE))) void k_snet4(SNetArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  static_assert(!SNAP || (!TRAIN && !LL), "SNAP: the forward of the hypernetwork classes");
+  if constexpr (SNAP) {
+    const long ts = blockIdx.y;
+    const long p0 = A.snap_off ? A.snap_off[ts] : ts * A.snap_M;
+    const long mt = A.snap_off ? A.snap_off[ts + 1] - p0 : A.snap_M;
+    if ((long)blockIdx.x >= (2 * ((mt + 31) / 32) + 3) / 4) return;      // no tile group of this snapshot for this slot (whole workgroup)
+    A.B = mt;
+    if (A.snap_off) A.xin += p0 * A.ncol;
+    A.u_out += p0 * A.so;
+    A.off_bh += ts * A.po;
+    A.WF4 = reinterpret_cast<const bf16x8*>(A.WF4) + ts * A.snap_wstride;
+    if (PR == 3) A.wscale += ts * 2;
+  }
   constexpr int NT = 256, WAVES = 4;
   constexpr int NCH = NBL / 2;                      // K-step chunks per plane
   constexpr int SPL = (NBL == 8 && LL) ? NIF_S4_SPLIT8 : (NBL == 4 ? NIF_S4_SPLIT4 : 1), NBS = NBL / SPL;   // chunk pieces per K-step, output (input) blocks per piece
@@ -210,14 +227,14 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && T
       else if (e < o_bl) {
         const int j = (e - o_bh) / NP, f = (e - o_bh) - j * NP;
         if (f < n) v = hyp3(A, k, s_bh + (long)j * n + f);
-        if (X16) v *= 4096.0f * A.wscale[(j * (r + 1) + k) * 2];      // the hidden biases start the scaled MFMA chains
+        if (X16) v *= 4096.0f * A.wscale[SNAP ? j * A.snap_T * 2 : (j * (r + 1) + k) * 2];      // the hidden biases start the scaled MFMA chains
       }
       else if (e < o_bl + so) v = hyp3(A, k, s_bl + (e - o_bl));
       else if (LL && e >= o_llb && e < o_llb + sou) v = hyp3(A, k, s_bl + so + (e - o_llb));
       else if (LL && e >= o_lw && e < o_lw + rl * rl) v = hyp3(A, k, s_bl + so + sou + (e - o_lw));
       sm[idx] = v;
     }
-    if (X16) for (int idx = tid; idx < nh * (r + 1) * 2; idx += NT) scl[idx] = A.wscale[idx];
+    if (X16) for (int idx = tid; idx < nh * (r + 1) * 2; idx += NT) scl[idx] = A.wscale[SNAP ? (idx >> 1) * A.snap_T * 2 + (idx & 1) : idx];
     if (cs_left <= 0) cs_left = -1;
 #pragma unroll
     for (int d = 0; d < DIST; ++d) cs_next(d);       // the first DIST chunks

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "nif_ctx.h"
+#include "../../include/nif_hip_snapshots.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
 static inline bool act_on(const nif_ctx* c) { return c->act_l1 != 0.f || c->act_l2 != 0.f; }
@@ -659,31 +660,30 @@ static int ensure_packed(nif_ctx* c) {
   return NIF_OK;
 }
 
-extern "C" int nif_forward_dev(nif_ctx* c, const float* xin, int64_t B, float* u) {
-  if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  int rc = ensure_packed(c); if (rc) return rc;
-  rc = ensure_capacity(c, B, false); if (rc) return rc;
-  PNetArgs pa; fill_pnet(c, pa, xin, B);
-  { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st); }
+// The forward of B rows behind ensure_packed / ensure_capacity.  with_pnet: xin [B][pi + si], the ParameterNet fills Z; without (the
+// snapshot entries): Z already holds every point's latent and the coordinates are columns col0 .. col0 + si of xin [B][ncol]
+static int forward_rows(nif_ctx* c, const float* xin, int ncol, int col0, long B, float* u, bool with_pnet) {
+  if (with_pnet) {
+    PNetArgs pa; fill_pnet(c, pa, xin, B);
+    ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st);
+  }
   if (c->kind == NIF_KIND_LASTLAYER) {
     ProfScope p_(c, NIF_PROF_SNET_FWD);
     if (c->use_ll4) {
-      SNetArgs sa; fill_snet_ll(c, sa, xin, c->pi + c->si, c->pi, B);
+      SNetArgs sa; fill_snet_ll(c, sa, xin, ncol, col0, B);
       sa.u_out = u;
       if (launch_snet4(sa, false, false, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no k_snet4 form for this net (SIREN planes not packed as half pairs)");
       HIPCHK(hipGetLastError());
       return NIF_OK;
     }
-    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, c->pi + c->si, c->pi, B);
+    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, col0, B);
     launch_pnet(ma, c->NB, false, c->st);
     LLArgs la; fill_ll(c, la, B); la.u_out = u;
     launch_ll_out(la, false, c->st);
     HIPCHK(hipGetLastError());
     return NIF_OK;
   }
-  SNetArgs sa; fill_snet(c, sa, xin, c->pi + c->si, c->pi, B);
+  SNetArgs sa; fill_snet(c, sa, xin, ncol, col0, B);
   sa.u_out = u;
   {
     ProfScope p_(c, NIF_PROF_SNET_FWD);
@@ -693,6 +693,14 @@ extern "C" int nif_forward_dev(nif_ctx* c, const float* xin, int64_t B, float* u
   }
   HIPCHK(hipGetLastError());
   return NIF_OK;
+}
+extern "C" int nif_forward_dev(nif_ctx* c, const float* xin, int64_t B, float* u) {
+  if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  int rc = ensure_packed(c); if (rc) return rc;
+  rc = ensure_capacity(c, B, false); if (rc) return rc;
+  return forward_rows(c, xin, c->pi + c->si, c->pi, B, u, true);
 }
 
 static int stage(nif_ctx* c, DevBuf<float>& buf, const float* host, long n) {
@@ -710,6 +718,152 @@ extern "C" int nif_forward(nif_ctx* c, const float* xin, int64_t B, float* u) {
   rc = stage(c, c->d_d, nullptr, B * c->so); if (rc) return rc;
   rc = nif_forward_dev(c, c->d_a, B, c->d_d); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(u, c->d_d, sizeof(float) * (size_t)(B * c->so), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+
+// ---- snapshot-wise inference (k_snap.hip) --------------------------------------------------------------------
+// The nets whose snapshot call is the point-wise forward on a device-built [p_t | x] table, kernel for kernel: every mixed policy and
+// the shapes on the legacy k_snet family.  Everything else runs the ParameterNet once per snapshot.
+static bool snap_pointwise(const nif_ctx* c) {
+  if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32) return true;
+  return c->kind != NIF_KIND_LASTLAYER && !c->use_snet4 && !c->use_snet3;
+}
+static int snap_check(nif_ctx* c, const void* rows, int64_t T, const void* x, const int64_t* offsets, int64_t M, const void* u, long* n) {
+  if (!c || !rows || T <= 0 || (offsets ? offsets[0] != 0 : M < 0)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (offsets) for (int64_t t = 0; t < T; ++t) if (offsets[t + 1] < offsets[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
+  *n = offsets ? (long)offsets[T] : (long)(T * M);
+  if (*n > 0 && (!x || !u)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_forward_snapshots: not capturable (inside nif_graph_begin / nif_graph_end)");
+  return NIF_OK;
+}
+// Hypernetwork classes on k_snet4: every point of snapshot t sees the same combined matrices W_t = sum_k lat_k(t) M^(k), so the snapshot is a
+// dense r = 0 net.  Per chunk of snapshots: the slot vectors w_t in fp32 from theta (the latent-to-weights kernel), their hidden matrices
+// packed from w_t in the forward kernel's chunk format (one launch per hidden matrix over the whole chunk), one forward launch.
+// buf: what is left of c->snap (sized by snap_combined_floats for the same tc).
+#define NIF_SNAP_IMAGE_BYTES (256L << 20)
+static long snap_r4(long f) { return (f + 3) & ~3L; }
+static void snap_combined_sizes(const nif_ctx* c, long* fe, long* be, long* per_bytes) {
+  const bool siren = c->kind != NIF_KIND_NIF;
+  *be = snet4_bwd_elems(c->n, 0);
+  *fe = siren ? *be : snet4_fwd_elems(c->n, 0);       // (the half planes: both directions in the adjoint geometry)
+  *per_bytes = 4 * c->po + (long)c->nh * ((*fe + *be) * 2 + 8);
+}
+static long snap_chunk(const nif_ctx* c, long T) {
+  long fe, be, per; snap_combined_sizes(c, &fe, &be, &per);
+  long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
+  if (tc > 65535) tc = 65535;
+  if (tc > T) tc = T;
+  return tc < 1 ? 1 : tc;
+}
+static long snap_combined_floats(const nif_ctx* c, long tc) {
+  long fe, be, per; snap_combined_sizes(c, &fe, &be, &per);
+  return snap_r4(tc * c->po) + snap_r4(2L * c->nh * tc) + tc * c->nh * (fe + be) / 2 + 4;
+}
+static int snap_combined(nif_ctx* c, float* buf, long tc_max, const float* lat, long T, const float* x, const long* off_dev,
+                         const int64_t* off_host, long M, float* u) {
+  const bool siren = c->kind != NIF_KIND_NIF;
+  long fe, be, per; snap_combined_sizes(c, &fe, &be, &per);
+  float* w = buf;
+  float* ws = w + snap_r4(tc_max * c->po);
+  char* WF = reinterpret_cast<char*>(ws + snap_r4(2L * c->nh * tc_max));
+  char* WB = WF + (size_t)tc_max * c->nh * fe * 2;
+  const int NBL = snet3_nbl(c->n);
+  for (long t0 = 0; t0 < T; t0 += tc_max) {
+    const long tc = T - t0 < tc_max ? T - t0 : tc_max;
+    long mmax = M, n_pts = tc * M;
+    if (off_host) {
+      mmax = 0; n_pts = off_host[t0 + tc] - off_host[t0];
+      for (long t = t0; t < t0 + tc; ++t) if (off_host[t + 1] - off_host[t] > mmax) mmax = off_host[t + 1] - off_host[t];
+    }
+    if (n_pts == 0) continue;
+    SNetArgs sa; fill_snet(c, sa, x, c->si, 0, n_pts);
+    {
+      ProfScope p_(c, NIF_PROF_PACK);
+      launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
+      for (int j = 0; j < c->nh; ++j)
+        launch_pack16b_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + (size_t)j * fe * 2, WB + (size_t)j * be * 2,
+                             c->nh * fe, c->nh * be, sa.omega, c->st, siren ? 3 : 0, ws + (long)j * tc * 2);
+    }
+    sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr;
+    sa.WF4 = WF; sa.wscale = siren ? ws : nullptr;
+    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * fe / 8; sa.snap_T = (int)tc;
+    sa.u_out = off_dev ? u : u + t0 * M * c->so;
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    if (launch_snet4_snap(sa, tc, mmax, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no snapshot form of k_snet4 for this net");
+  }
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+
+extern "C" int nif_forward_snapshots_dev(nif_ctx* c, const float* rows, int32_t rows_are_latent, int64_t T, const float* x,
+                                         const int64_t* offsets, int64_t M, float* u) {
+  long n = 0;
+  int rc = snap_check(c, rows, T, x, offsets, M, u, &n); if (rc) return rc;
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  rc = ensure_packed(c); if (rc) return rc;
+  if (n == 0) return NIF_OK;
+  const bool lat_in = rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
+  const bool pointwise = snap_pointwise(c) && !lat_in;        // (given latents never meet the ParameterNet: nothing of it to reproduce)
+  const bool phi_dot = ll && !offsets && !snap_pointwise(c) && phi_dot_supported(c->r, c->so);
+  // one buffer, one growth: [offsets (ragged) | latent rows (from p) | the table (pointwise, or a shared mesh in front of a point
+  // kernel) or the combined nets of one chunk of snapshots]
+  const long off_f = offsets ? 2 * (T + 1) : 0, lat_f = (pointwise || lat_in) ? 0 : T * c->r;
+  const bool combined = !ll && !snap_pointwise(c) && c->use_snet4;
+  const bool table = pointwise || (!offsets && !phi_dot && !combined);
+  const long tc_max = combined ? snap_chunk(c, T) : 0;
+  const long tab_f = table ? n * (c->pi + c->si) : (combined ? snap_combined_floats(c, tc_max) : 0);
+  rc = c->snap.reserve(c, snap_r4(off_f + lat_f) + tab_f + 1); if (rc) return rc;
+  rc = ensure_capacity(c, combined ? T : (phi_dot ? (T > M ? T : M) : (n > T ? n : T)), false); if (rc) return rc;
+  SnapArgs sn; memset(&sn, 0, sizeof(sn));
+  sn.T = T; sn.M = M; sn.n = n; sn.pi = c->pi; sn.si = c->si; sn.r = c->r; sn.x = x;
+  if (offsets) {      // (host memory of the caller: consumed before this returns)
+    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
+    HIPCHK(hipMemcpyAsync(c->snap.p, offsets, sizeof(int64_t) * (size_t)(T + 1), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
+  }
+  if (table) sn.table = c->snap + snap_r4(off_f + lat_f);
+  if (pointwise) {
+    sn.p = rows;
+    launch_snap_expand(sn, c->st);
+    return forward_rows(c, sn.table, c->pi + c->si, c->pi, n, u, true);
+  }
+  const float* lat = rows;
+  if (!lat_in) {      // the ParameterNet over the T rows, its output back as rows [T][r]
+    PNetArgs pa; fill_pnet(c, pa, rows, T); pa.ncol = c->pi;
+    { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st); }
+    launch_tiles_to_rows(c->Z, T, c->r, c->snap + off_f, c->st);
+    lat = c->snap + off_f;
+  }
+  if (combined) return snap_combined(c, c->snap + snap_r4(off_f + lat_f), tc_max, lat, T, x, sn.offsets, offsets, M, u);
+  if (phi_dot) {      // one ShapeNet pass over the mesh for all snapshots
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, M);
+    launch_pnet(ma, c->NB, false, c->st);
+    launch_phi_dot(c->PHI, lat, c->theta + c->ll_bias, T, M, c->r, c->so, u, c->st);
+    HIPCHK(hipGetLastError());
+    return NIF_OK;
+  }
+  sn.lat = lat; sn.Z = c->Z;
+  launch_snap_expand(sn, c->st);
+  if (table) return forward_rows(c, sn.table, c->pi + c->si, c->pi, n, u, false);
+  return forward_rows(c, x, c->si, 0, n, u, false);
+}
+extern "C" int nif_forward_snapshots(nif_ctx* c, const float* rows, int32_t rows_are_latent, int64_t T, const float* x,
+                                     const int64_t* offsets, int64_t M, float* u) {
+  long n = 0;
+  int rc = snap_check(c, rows, T, x, offsets, M, u, &n); if (rc) return rc;
+  HIPCHK(hipSetDevice(c->dev));
+  TAIL_FLUSH(c)
+  HIPCHK(hipStreamSynchronize(c->st));
+  if (n == 0) return ensure_packed(c);
+  rc = stage(c, c->d_a, rows, T * (rows_are_latent ? c->r : c->pi)); if (rc) return rc;
+  rc = stage(c, c->d_b, x, (offsets ? n : (long)M) * c->si); if (rc) return rc;
+  rc = stage(c, c->d_d, nullptr, n * c->so); if (rc) return rc;
+  rc = nif_forward_snapshots_dev(c, c->d_a, rows_are_latent, T, c->d_b, offsets, M, c->d_d); if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(u, c->d_d, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
@@ -2479,6 +2633,11 @@ extern "C" int nif_set_option(nif_ctx* c, const char* key, int32_t value) {
   if (strcmp(key, "fp32_mfma") == 0) {      // 1: every product on the f32-input MFMAs (k_snet3) instead of the bf16 splits
     c->opt_fp32_mfma = value != 0;
     c->packed = false; c->packed32 = false; c->packed_p32 = false;
+    return NIF_OK;
+  }
+  if (strcmp(key, "snapshot_image_bytes") == 0) {      // nif_forward_snapshots*: bytes of combined nets held at once (0: the default; tests lower it)
+    if (value < 0) return fail(NIF_ERR_INVALID, "nif_set_option(\"snapshot_image_bytes\"): >= 0");
+    c->opt_snap_bytes = value;
     return NIF_OK;
   }
   if (strcmp(key, "side_pnet") == 0) { c->opt_side_pnet = value != 0; return NIF_OK; }   // ParameterNet adjoint on the second stream

@@ -138,6 +138,10 @@ struct nif_ctx {
   hipEvent_t t0 = nullptr, t1 = nullptr;
   // staging for the host-pointer API
   DevBuf<float> d_a, d_b, d_c, d_d;
+  // snapshot-wise inference (nif_forward_snapshots*): [offsets | latent rows | table, or the combined nets of one chunk of snapshots:
+  // slot vectors, plane scales, packed planes] of one call, rebuilt by every call.  opt_snap_bytes: the chunk's budget
+  // (nif_set_option "snapshot_image_bytes", 0 = the default)
+  DevBuf<float> snap; long opt_snap_bytes = 0;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

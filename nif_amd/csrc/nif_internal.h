@@ -127,7 +127,14 @@ struct SNetArgs {
   int h_ph16;                             // prec == 1, 128-wide plain SIREN training: the hidden matrices' INPUT stash rows as 16-bit phases (k_snet3_dev.h;
                                           // the readers are k_snet4's own adjoint sweep and k_gw8<R, true, true>: snet4_writes_h_ph16)
   int wg_cap;                             // k_snet4: at most this many workgroups (0 = fill the device); the chunk pipeline leaves room for stream B
+  // snapshot-wise inference (k_snap.hip; read by the SNAP instantiations of k_snet4 alone).  Workgroup (x, y) is tile-group slot x of
+  // snapshot y: its points are snap_off[y] .. snap_off[y + 1] of xin / u_out (snap_off null: a mesh of snap_M points in xin shared by all,
+  // u_out rows y snap_M ..), its net the dense r = 0 net whose slot vector is theta + off_bh + y po, whose packed hidden planes are
+  // WF4 + y snap_wstride 16-byte units and whose plane scales are wscale[(j snap_T + y) 2 ..] for hidden matrix j
+  const long* snap_off; long snap_M, snap_wstride; int snap_T;
 };
+// the forward of T combined (r = 0) nets in one launch (k_snap.hip); Mmax = the longest snapshot.  -1: no form for this net
+int launch_snet4_snap(const SNetArgs& a, long T, long Mmax, hipStream_t st);
 // slot-ordered copy of the dense ShapeNet parameters of the last-layer class: [W1 | (hidden: unused) | Wl | b1 | bh_j | bl |
 // last_layer_bias | pnet last W (rl x rl)] -- the order k_snet4's prologue indexes (hyp3 with r = 0)
 struct LLSlotSeg { long src, dst, len; };
@@ -443,6 +450,18 @@ void launch_ll_hess(const HessLLArgs& H, hipStream_t st);
 void launch_gather_rows(const float* src, const int* perm, long n, int ncol, float* dst, hipStream_t st);
 void launch_rows_to_tiles(const float* rows, long B, int c, float* tiles, hipStream_t st);
 void launch_tiles_to_rows(const float* tiles, long B, int c, float* rows, hipStream_t st);
+// snapshot-wise inference (k_snap.hip, nif_forward_snapshots*): n points in T snapshots -- a shared mesh of M points (offsets null,
+// n = T M, x [M][si]) or ragged meshes (device offsets [T + 1], x [n][si] concatenated).  Writes, where the pointer is set, the table
+// [n][pi + si] of rows [p_t | x] (p null: zeros in the parameter columns) and the latent tiles Z [tiles][r][32] from lat [T][r]
+struct SnapArgs {
+  const float* p; const float* lat; const float* x; const long* offsets;
+  long T, M, n; int pi, si, r;
+  float* table; float* Z;
+};
+void launch_snap_expand(const SnapArgs& a, hipStream_t st);
+// last-layer class, shared mesh: u [T][M][so] = Dot(PHI [tiles][so r][32], a [T][r]) + bias [so]
+bool phi_dot_supported(int r, int so);
+void launch_phi_dot(const float* PHI, const float* a, const float* bias, long T, long M, int r, int so, float* u, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------
 // device helpers

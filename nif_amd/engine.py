@@ -228,6 +228,61 @@ class Engine(object):
         """predictions of device-resident rows [b, pi+si] into a device buffer [b, so] (nif_forward_dev); asynchronous"""
         check(self.lib.nif_forward_dev(self.ctx, d_x, int(b), d_u))
 
+    # ---- snapshot-wise inference (include/nif_hip_snapshots.h; Model.predict_snapshots plans the chunks) ----------
+    def _not_capturing(self):
+        # nif_forward_snapshots* refuse a capture themselves (NIF_ERR_STATE); the staging around them (allocations, synchronous
+        # copies) would break the capture before they are reached
+        if getattr(self, "_capturing", False):
+            raise _lib.NifError("libnif_hip error -4: nif_forward_snapshots: not capturable (inside nif_graph_begin / nif_graph_end)")
+
+    def snapshot_mesh(self, x):
+        """a shared mesh [M, si] uploaded once: the handle that forward_snapshots reads slices of (free() it when done)"""
+        self._not_capturing()
+        x = self._rows(x, self.spec.si_dim, "coordinates")
+        d = DeviceArray(self, max(x.size, 1))
+        d.upload(x)
+        return d
+
+    def _snapshots(self, rows, is_latent, d_x, x_off, offsets, m, n):
+        self._not_capturing()
+        rows = self._rows(rows, self.spec.pi_hidden if is_latent else self.spec.pi_dim, "latent" if is_latent else "parameter inputs")
+        so = self.spec.so_dim
+        out = np.empty((n, so), dtype=np.float32)
+        if not n:
+            return out
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        d_r, d_u = DeviceArray(self, rows.size), DeviceArray(self, n * so)
+        try:
+            d_r.upload(rows)
+            check(self.lib.nif_forward_snapshots_dev(self.ctx, d_r.at(0), 1 if is_latent else 0, rows.shape[0], d_x.at(x_off),
+                                                     None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64)), int(m), d_u.at(0)))
+            check(self.lib.nif_d2h(self.ctx, ptr(out), d_u.at(0), out.size * 4))
+        finally:
+            d_r.free(); d_u.free()
+        return out
+
+    def forward_snapshots(self, rows, is_latent, mesh, lo, hi):
+        """rows [T, pi] (or [T, r] latents) on the points lo .. hi of a snapshot_mesh handle -> [T, hi - lo, so]"""
+        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
+        return self._snapshots(rows, is_latent, mesh, int(lo) * self.spec.si_dim, None, m, t * m).reshape(t, m, self.spec.so_dim)
+
+    def forward_snapshots_ragged(self, rows, is_latent, xs):
+        """rows [T, .] and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> [sum M_t, so], snapshot after snapshot"""
+        self._not_capturing()
+        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
+        if len(xs) != int(np.shape(rows)[0]):
+            raise ValueError("forward_snapshots_ragged: %d rows for %d meshes" % (int(np.shape(rows)[0]), len(xs)))
+        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
+        n = int(offsets[-1])
+        if not n:
+            return np.empty((0, self.spec.so_dim), dtype=np.float32)
+        d_x = DeviceArray(self, n * self.spec.si_dim)
+        try:
+            d_x.upload(np.concatenate(xs, axis=0))
+            return self._snapshots(rows, is_latent, d_x, 0, offsets, 0, n)
+        finally:
+            d_x.free()
+
     def p_to_lr(self, p):
         p = self._rows(p, self.spec.pi_dim, "parameter inputs")
         out = np.empty((p.shape[0], self.spec.pi_hidden), dtype=np.float32)
@@ -523,9 +578,11 @@ class Engine(object):
     # captured training steps (include/nif_hip.h nif_graph_*)
     def graph_begin(self):
         check(self.lib.nif_graph_begin(self.ctx))
+        self._capturing = True
 
     def graph_end(self):
         gid = C.c_int32(-1)
+        self._capturing = False      # (the library leaves the capture whether or not it could be ended)
         check(self.lib.nif_graph_end(self.ctx, C.byref(gid)))
         return int(gid.value)
 

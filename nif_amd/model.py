@@ -253,6 +253,80 @@ class Model(object):
     def __call__(self, x, training=False):
         return self._run(x)
 
+    _SNAPSHOT_CHUNK_BYTES = 1 << 28
+
+    def predict_snapshots(self, x, p=None, latent=None, batch_size=None):
+        """The field of T snapshots on whole meshes: snapshot t is ONE ParameterNet input p[t] (or one latent vector latent[t], as
+        model_p_to_lr returns it) for every point of its mesh -- the use the reference serves with its three-stage factorisation
+        (README.md:99-117, model.py:956-986).  x [M, si]: one mesh shared by all snapshots, returns [T, M, so]; x a list / tuple of T
+        arrays [M_t, si]: returns a list of T arrays [M_t, so].  out[t] is predict(hstack([tile(p[t], M_t), x_t])) without that table:
+        the rows are expanded on the device, the ParameterNet runs once per snapshot and, for the last-layer class on a shared mesh,
+        the ShapeNet once per mesh chunk.  Device staging is bounded by _SNAPSHOT_CHUNK_BYTES (snapshots, and the points of a long
+        snapshot, go through in chunks; a shared mesh is uploaded once); the result does not depend on it nor on batch_size, which
+        only raises the points per chunk."""
+        if self._role != "full":
+            raise ValueError("predict_snapshots exists on the full model only (%s is a sub-model view)" % self._role)
+        if (p is None) == (latent is None):
+            raise ValueError("predict_snapshots: exactly one of p [T, pi] and latent [T, r]")
+        s = self._owner._spec
+        is_latent = latent is not None
+        width = s.pi_hidden if is_latent else s.pi_dim
+        rows = np.asarray(latent if is_latent else p, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != width:
+            raise ValueError("predict_snapshots: expected %s of shape (T, %d), got %s" % ("latent" if is_latent else "p", width, rows.shape))
+        T, so = rows.shape[0], s.so_dim
+
+        def mesh_of(a):
+            a = np.asarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != s.si_dim:
+                raise ValueError("predict_snapshots: expected coordinates of shape (M, %d), got %s" % (s.si_dim, a.shape))
+            return a
+
+        per_point = 4 * (s.pi_dim + s.si_dim + so + s.pi_hidden * (1 + (so if s.connectivity == "last_layer" else 0)))
+        pts = max(1, int(self._SNAPSHOT_CHUNK_BYTES) // per_point, int(batch_size or 0))
+        e = self._engine
+        if not isinstance(x, (list, tuple)):
+            x = mesh_of(x)
+            M = x.shape[0]
+            out = np.empty((T, M, so), dtype=np.float32)
+            if T == 0 or M == 0:
+                return out
+            mc = min(M, pts)
+            tc = max(1, pts // mc)
+            mesh = e.snapshot_mesh(x)
+            try:
+                for lo in range(0, M, mc):
+                    hi = min(M, lo + mc)
+                    for t0 in range(0, T, tc):
+                        out[t0:t0 + tc, lo:hi] = e.forward_snapshots(rows[t0:t0 + tc], is_latent, mesh, lo, hi)
+            finally:
+                mesh.free()
+            return out
+        xs = [mesh_of(a) for a in x]
+        if len(xs) != T:
+            raise ValueError("predict_snapshots: %d meshes for %d snapshots" % (len(xs), T))
+        outs = [np.empty((a.shape[0], so), dtype=np.float32) for a in xs]
+        group, held = [], 0
+
+        def flush():
+            u = e.forward_snapshots_ragged(rows[[t for t, _, _ in group]], is_latent, [xs[t][lo:hi] for t, lo, hi in group])
+            at = 0
+            for t, lo, hi in group:
+                outs[t][lo:hi] = u[at:at + hi - lo]
+                at += hi - lo
+
+        for t, a in enumerate(xs):
+            for lo in range(0, a.shape[0], pts):
+                hi = min(a.shape[0], lo + pts)
+                if group and held + hi - lo > pts:
+                    flush()
+                    group, held = [], 0
+                group.append((t, lo, hi))
+                held += hi - lo
+        if group:
+            flush()
+        return outs
+
     # ---- training --------------------------------------------------------------------------------
     # Keras' compile(metrics=[...]): names / metric objects -> (history key, kind).  Unweighted (Keras applies sample_weight to
     # `weighted_metrics` only); the value of an epoch is the running mean over every sample the epoch saw, evaluated with the weights
