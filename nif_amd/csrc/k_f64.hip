@@ -542,21 +542,25 @@ static int f64_ensure(nif_ctx* c) {
 
 void nif_f64_release(nif_ctx* c) { delete c->f64; c->f64 = nullptr; }
 
-int nif_f64_set_params_impl(nif_ctx* c, const double* host, int64_t n) {
+// The C-ABI of the path (include/nif_hip.h nif_f64_*).  NIF_FLUSH_NONE throughout: a float64 master vector, [grad | loss] buffer and
+// workspace of their own -- theta, grad, the optimizer slots and a pending row reduction of the float32 path are neither read nor written
+extern "C" int nif_f64_set_params(nif_ctx* c, const double* host, int64_t n) {
+  if (!c || !host) return fail(NIF_ERR_INVALID, "null");
   int rc = f64_supported(c, "nif_f64_set_params"); if (rc) return rc;
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)
   rc = f64_ensure(c); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->f64->theta, host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   c->f64->have_params = true;
   return NIF_OK;
 }
-int nif_f64_get_params_impl(nif_ctx* c, double* host, int64_t n) {
+extern "C" int nif_f64_get_params(nif_ctx* c, double* host, int64_t n) {
+  if (!c || !host) return fail(NIF_ERR_INVALID, "null");
   int rc = f64_supported(c, "nif_f64_get_params"); if (rc) return rc;
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
   if (!c->f64 || !c->f64->have_params) return fail(NIF_ERR_STATE, "nif_f64_get_params before nif_f64_set_params");
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)
   HIPCHK(hipMemcpyAsync(host, c->f64->theta, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
@@ -620,24 +624,27 @@ static int f64_run(nif_ctx* c, const double* xin, const double* y, const double*
   return NIF_OK;
 }
 
-int nif_f64_forward_dev_impl(nif_ctx* c, const double* xin, int64_t B, double* u) {
+extern "C" int nif_f64_forward_dev(nif_ctx* c, const double* xin, int64_t B, double* u) {
+  if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
   int rc = f64_supported(c, "nif_f64_forward_dev"); if (rc) return rc;
   if (!c->f64 || !c->f64->have_params) return fail(NIF_ERR_STATE, "nif_f64_forward_dev before nif_f64_set_params");
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)
   return f64_run(c, xin, nullptr, nullptr, B, B, u);
 }
-int nif_f64_loss_grad_dev_impl(nif_ctx* c, const double* xin, const double* y, const double* sw, int64_t B, int64_t Bg) {
+extern "C" int nif_f64_loss_grad_dev(nif_ctx* c, const double* xin, const double* y, const double* sw, int64_t B, int64_t Bg) {
+  if (!c || !xin || !y || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
   int rc = f64_supported(c, "nif_f64_loss_grad_dev"); if (rc) return rc;
   if (!c->f64 || !c->f64->have_params) return fail(NIF_ERR_STATE, "nif_f64_loss_grad_dev before nif_f64_set_params");
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)
   rc = f64_run(c, xin, y, sw, B, Bg, nullptr); if (rc) return rc;
   c->f64->have_grad = true;
   return NIF_OK;
 }
-int nif_f64_grad_read_impl(nif_ctx* c, double* loss, double* grad) {
+extern "C" int nif_f64_grad_read(nif_ctx* c, double* loss, double* grad) {
+  if (!c) return fail(NIF_ERR_INVALID, "null");
   int rc = f64_supported(c, "nif_f64_grad_read"); if (rc) return rc;
   if (!c->f64 || !c->f64->have_grad) return fail(NIF_ERR_STATE, "nif_f64_grad_read before nif_f64_loss_grad_dev");
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)
   if (grad) HIPCHK(hipMemcpyAsync(grad, c->f64->g, sizeof(double) * (size_t)c->P, hipMemcpyDeviceToHost, c->st));
   if (loss) HIPCHK(hipMemcpyAsync(loss, c->f64->g + c->P, sizeof(double), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));

@@ -215,11 +215,11 @@ nif_ctx::~nif_ctx() {
   for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
   for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
   for (const Rec& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (hipGraphExec_t ex : graphs) if (ex) (void)hipGraphExecDestroy(ex);
+  for (const CapGraph& g : graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
 }
 extern "C" int nif_destroy(nif_ctx* c) {
   if (!c) return NIF_OK;
-  hipSetDevice(c->dev);
+  (void)nif_enter(c, NIF_FLUSH_NONE);      // (a deferred piece goes with the context; a failing device must not keep the memory alive)
   if (c->st) hipStreamSynchronize(c->st);
   delete c;
   return NIF_OK;
@@ -239,18 +239,16 @@ extern "C" int nif_param_layout(nif_ctx* c, nif_tensor_desc* descs, int32_t* n_i
 extern "C" int nif_set_params(nif_ctx* c, const float* host, int64_t n) {
   if (!c || !host) return fail(NIF_ERR_INVALID, "null");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMemcpyAsync(c->theta, host, sizeof(float) * n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
-  c->have_params = true; c->packed = false; c->packed32 = false; c->packed_p32 = false;
+  c->have_params = true; c->planes_stale();
   return NIF_OK;
 }
 extern "C" int nif_get_params(nif_ctx* c, float* host, int64_t n) {
   if (!c || !host) return fail(NIF_ERR_INVALID, "null");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMemcpyAsync(host, c->theta, sizeof(float) * n, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
@@ -258,8 +256,7 @@ extern "C" int nif_get_params(nif_ctx* c, float* host, int64_t n) {
 extern "C" int nif_get_opt_state(nif_ctx* c, float* mh, float* vh, int64_t n, int64_t* step) {
   if (!c || !mh || !vh || !step) return fail(NIF_ERR_INVALID, "null");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMemcpyAsync(mh, c->m, sizeof(float) * n, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(vh, c->v, sizeof(float) * n, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -269,8 +266,7 @@ extern "C" int nif_get_opt_state(nif_ctx* c, float* mh, float* vh, int64_t n, in
 extern "C" int nif_set_opt_state(nif_ctx* c, const float* mh, const float* vh, int64_t n, int64_t step) {
   if (!c || !mh || !vh) return fail(NIF_ERR_INVALID, "null");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMemcpyAsync(c->m, mh, sizeof(float) * n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipMemcpyAsync(c->v, vh, sizeof(float) * n, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -284,54 +280,47 @@ extern "C" int nif_set_opt_state(nif_ctx* c, const float* mh, const float* vh, i
 
 extern "C" int nif_dev_alloc(nif_ctx* c, int64_t bytes, void** dptr) {
   if (!c || !dptr || bytes < 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMalloc(dptr, bytes > 0 ? (size_t)bytes : 4));
   return NIF_OK;
 }
 extern "C" int nif_dev_free(nif_ctx* c, void* dptr) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   if (dptr) HIPCHK(hipFree(dptr));
   return NIF_OK;
 }
 extern "C" int nif_h2d(nif_ctx* c, void* dst, const void* src, int64_t bytes) {
   if (!c || !dst || !src) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
 extern "C" int nif_d2h(nif_ctx* c, void* dst, const void* src, int64_t bytes) {
   if (!c || !dst || !src) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
 extern "C" int nif_sync(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
 // ---- shard streaming: pinned host staging + asynchronous H2D on a copy stream, double buffered -----------------------
 extern "C" int nif_host_alloc(nif_ctx* c, int64_t bytes, void** hptr) {
   if (!c || !hptr || bytes < 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipHostMalloc(hptr, bytes > 0 ? (size_t)bytes : 4, hipHostMallocDefault));
   return NIF_OK;
 }
 extern "C" int nif_host_free(nif_ctx* c, void* hptr) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   if (c->st_copy) HIPCHK(hipStreamSynchronize(c->st_copy));
   if (hptr) HIPCHK(hipHostFree(hptr));
   return NIF_OK;
@@ -349,8 +338,7 @@ static int ensure_copy_stream(nif_ctx* c) {
 }
 extern "C" int nif_h2d_async(nif_ctx* c, void* dst_dev, const void* src_pinned, int64_t bytes, int32_t slot) {
   if (!c || !dst_dev || !src_pinned || bytes < 0 || slot < 0 || slot > 1) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = ensure_copy_stream(c); if (rc) return rc;
   HIPCHK(hipStreamWaitEvent(c->st_copy, c->ev_consumed[slot], 0));   // the steps that read this slot's device buffer are done
   HIPCHK(hipMemcpyAsync(dst_dev, src_pinned, (size_t)bytes, hipMemcpyHostToDevice, c->st_copy));
@@ -359,39 +347,36 @@ extern "C" int nif_h2d_async(nif_ctx* c, void* dst_dev, const void* src_pinned, 
 }
 extern "C" int nif_copy_acquire(nif_ctx* c, int32_t slot) {       // compute stream: wait until the slot's copies have landed
   if (!c || slot < 0 || slot > 1) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = ensure_copy_stream(c); if (rc) return rc;
   HIPCHK(hipStreamWaitEvent(c->st, c->ev_copied[slot], 0));
   return NIF_OK;
 }
 extern "C" int nif_copy_release(nif_ctx* c, int32_t slot) {       // compute stream: everything enqueued so far has consumed the slot
   if (!c || slot < 0 || slot > 1) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = ensure_copy_stream(c); if (rc) return rc;
   HIPCHK(hipEventRecord(c->ev_consumed[slot], c->st));
   return NIF_OK;
 }
 extern "C" int nif_copy_wait_host(nif_ctx* c, int32_t slot) {     // host: the slot's pinned staging buffer may be overwritten
   if (!c || slot < 0 || slot > 1) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = ensure_copy_stream(c); if (rc) return rc;
   HIPCHK(hipEventSynchronize(c->ev_copied[slot]));
   return NIF_OK;
 }
 extern "C" int nif_gather_rows_dev(nif_ctx* c, const float* src_dev, const int32_t* perm_dev, int64_t n, int32_t ncol, float* dst_dev) {
   if (!c || !src_dev || !perm_dev || !dst_dev || n < 0 || ncol < 1) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   if (n > 0) launch_gather_rows(src_dev, perm_dev, n, ncol, dst_dev, c->st);
   HIPCHK(hipGetLastError());
   return NIF_OK;
 }
 
 extern "C" void* nif_stream(nif_ctx* c) { return c ? (void*)c->st : nullptr; }
-extern "C" void* nif_grad_dev(nif_ctx* c) { if (c) (void)nif_tail_flush(c); return c ? (void*)c->grad : nullptr; }
+// (no error code to return and no device work without a pending reduction: the guard only then)
+extern "C" void* nif_grad_dev(nif_ctx* c) { if (c && c->tail_pending) (void)nif_enter(c, NIF_FLUSH_TAIL); return c ? (void*)c->grad : nullptr; }
 extern "C" void* nif_params_dev(nif_ctx* c) { return c ? (void*)c->theta : nullptr; }
 
 // ------------------------------------------------------------------------------------------
@@ -696,8 +681,7 @@ static int forward_rows(nif_ctx* c, const float* xin, int ncol, int col0, long B
 }
 extern "C" int nif_forward_dev(nif_ctx* c, const float* xin, int64_t B, float* u) {
   if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_capacity(c, B, false); if (rc) return rc;
   return forward_rows(c, xin, c->pi + c->si, c->pi, B, u, true);
@@ -711,8 +695,7 @@ static int stage(nif_ctx* c, DevBuf<float>& buf, const float* host, long n) {
 
 extern "C" int nif_forward(nif_ctx* c, const float* xin, int64_t B, float* u) {
   if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = stage(c, c->d_a, xin, B * (c->pi + c->si)); if (rc) return rc;
   rc = stage(c, c->d_d, nullptr, B * c->so); if (rc) return rc;
@@ -800,8 +783,7 @@ extern "C" int nif_forward_snapshots_dev(nif_ctx* c, const float* rows, int32_t 
                                          const int64_t* offsets, int64_t M, float* u) {
   long n = 0;
   int rc = snap_check(c, rows, T, x, offsets, M, u, &n); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   rc = ensure_packed(c); if (rc) return rc;
   if (n == 0) return NIF_OK;
   const bool lat_in = rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
@@ -855,8 +837,7 @@ extern "C" int nif_forward_snapshots(nif_ctx* c, const float* rows, int32_t rows
                                      const int64_t* offsets, int64_t M, float* u) {
   long n = 0;
   int rc = snap_check(c, rows, T, x, offsets, M, u, &n); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   if (n == 0) return ensure_packed(c);
   rc = stage(c, c->d_a, rows, T * (rows_are_latent ? c->r : c->pi)); if (rc) return rc;
@@ -876,8 +857,7 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
     if (y_idx[i] < 0 || y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
   for (int j = 0; j < nx; ++j)
     if (x_idx[j] < 0 || x_idx[j] >= c->pi + c->si) return fail(NIF_ERR_INVALID, "x_index out of range");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_packed32(c); if (rc) return rc;
@@ -1054,15 +1034,13 @@ static int hessian_check(nif_ctx* c, const void* xin, int64_t B, const int32_t* 
 extern "C" int nif_hessian_dev(nif_ctx* c, const float* xin_dev, int64_t B, const int32_t* y_idx, int32_t ny, const int32_t* x_idx,
                                int32_t nx, float* y_dev, float* dydx_dev, float* d2_dev) {
   int rc = hessian_check(c, xin_dev, B, y_idx, ny, x_idx, nx, y_dev, dydx_dev, d2_dev); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   return hessian_core(c, xin_dev, B, y_idx, ny, x_idx, nx, y_dev, dydx_dev, d2_dev);
 }
 extern "C" int nif_hessian(nif_ctx* c, const float* xin, int64_t B, const int32_t* y_idx, int32_t ny, const int32_t* x_idx,
                            int32_t nx, float* y_out, float* dydx_out, float* d2_out) {
   int rc = hessian_check(c, xin, B, y_idx, ny, x_idx, nx, y_out, dydx_out, d2_out); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   rc = stage(c, c->d_a, xin, B * (c->pi + c->si)); if (rc) return rc;
   const size_t n_y = (size_t)B * c->so, n_d = (size_t)B * ny * nx, n_h = n_d * nx;
@@ -1081,8 +1059,7 @@ extern "C" int nif_hessian(nif_ctx* c, const float* xin, int64_t B, const int32_
 
 extern "C" int nif_pnet_latent(nif_ctx* c, const float* p, int64_t B, float* lr) {
   if (!c || !p || !lr || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_capacity(c, B, false); if (rc) return rc;
@@ -1101,8 +1078,7 @@ extern "C" int nif_pnet_latent(nif_ctx* c, const float* p, int64_t B, float* lr)
 extern "C" int nif_x_to_phi(nif_ctx* c, const float* x, int64_t B, float* phi) {
   if (!c || !x || !phi || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
   if (c->kind != NIF_KIND_LASTLAYER) return fail(NIF_ERR_INVALID, "model_x_to_phi exists only for the last-layer class");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_capacity(c, B, false); if (rc) return rc;
@@ -1122,16 +1098,14 @@ extern "C" int nif_latent_to_w_dev(nif_ctx* c, const float* lr, int64_t B, float
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
   if (c->kind == NIF_KIND_LASTLAYER)
     return fail(NIF_ERR_INVALID, "In this class: NIFMultiScaleLastLayerParameterization, `w` is the same as `lr`");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   { ProfScope p_(c, NIF_PROF_LATENT_TO_W); launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lr, B, w, c->st); }
   HIPCHK(hipGetLastError());
   return NIF_OK;
 }
 extern "C" int nif_latent_to_w(nif_ctx* c, const float* lr, int64_t B, float* w) {
   if (!c || !lr || !w || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = stage(c, c->d_a, lr, B * c->r); if (rc) return rc;
   rc = stage(c, c->d_b, nullptr, B * c->po); if (rc) return rc;
@@ -1143,8 +1117,7 @@ extern "C" int nif_latent_to_w(nif_ctx* c, const float* lr, int64_t B, float* w)
 
 extern "C" int nif_shapenet_given_w_dev(nif_ctx* c, const float* x, const float* w, int64_t B, float* u) {
   if (!c || !x || !w || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   if (c->kind == NIF_KIND_LASTLAYER) {   // u = Dot(phi(x), w) + bias with caller-supplied w [B, r]
     int rc = ensure_packed(c); if (rc) return rc;
     rc = ensure_capacity(c, B, false); if (rc) return rc;
@@ -1165,8 +1138,7 @@ extern "C" int nif_shapenet_given_w_dev(nif_ctx* c, const float* x, const float*
 }
 extern "C" int nif_shapenet_given_w(nif_ctx* c, const float* x, const float* w, int64_t B, float* u) {
   if (!c || !x || !w || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = stage(c, c->d_a, x, B * c->si); if (rc) return rc;
   rc = stage(c, c->d_b, w, B * c->po); if (rc) return rc;   // po == r for the last-layer class
@@ -1594,13 +1566,12 @@ static int ensure_small_tables(nif_ctx* c, const PNetArgs& pa, const SNetArgs& s
   return NIF_OK;
 }
 // r6: the row reduction of a plain step waits for its consumer when nothing else needs [grad | loss] first: the optimizer step runs it fused
-// with the update (k_reduce_opt: one launch less per step -- 5 of the 31 us of a 512-point step, 0.5 % of the 2^20-point one).  Every
-// other entry point of the library starts with nif_tail_flush; the reduction is NOT deferred with a communicator attached, inside a graph
-// capture, under the profiler (its per-group events would lose the REDUCE group) or when a regulariser adds to the gradient behind it.
+// with the update (k_reduce_opt: one launch less per step -- 5 of the 31 us of a 512-point step, 0.5 % of the 2^20-point one).  The
+// reduction is NOT deferred with a communicator attached, inside a graph capture, under the profiler (its per-group events would lose
+// the REDUCE group) or when a regulariser adds to the gradient behind it.
 int nif_tail_flush(nif_ctx* c) {
-  if (!c || !c->tail_pending) return NIF_OK;
+  if (!c->tail_pending) return NIF_OK;
   c->tail_pending = false;
-  HIPCHK(hipSetDevice(c->dev));
   launch_reduce(c->partial, c->pstride, c->tail_rows, c->loss_partial, c->tail_nloss, c->grad, c->P, c->st);
   HIPCHK(hipGetLastError());
   return NIF_OK;
@@ -1614,19 +1585,22 @@ static bool tail_can_defer(const nif_ctx* c) {
 // a Keras loss-metric accumulation that nif_metric_accumulate left for the next k_small launch (r6: one launch less per small step):
 // everything that would change grad[P] or read the metric without such a launch runs it now
 int nif_metric_flush(nif_ctx* c) {
-  if (!c || !c->metric_pending) return NIF_OK;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  if (!c->metric_pending) return NIF_OK;
+  const int rc = nif_tail_flush(c); if (rc) return rc;
   c->metric_pending = false;
   launch_metric(c->grad, c->P, c->metric_pending_w, c->metric, c->st);
   HIPCHK(hipGetLastError());
   return NIF_OK;
 }
+int nif_enter(nif_ctx* c, nif_flush what) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (what == NIF_FLUSH_NONE) return NIF_OK;
+  const int rc = nif_tail_flush(c); if (rc) return rc;
+  return what == NIF_FLUSH_METRIC ? nif_metric_flush(c) : NIF_OK;
+}
 static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, int64_t Bg, int ns,
                           const int* seeds, const float* gt, float wj, const SobPlan* sp = nullptr) {
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)      // (a step whose gradient was never consumed: its rows are about to be overwritten)
-  c->last_step_small = false;
+  c->last_step_small = false;      // (also what a refused step leaves behind)
   // r6: a small batch of a small net -- ONE launch for the loss and every gradient (k_small: fp32 FMAs straight from theta, no plane
   // packing), then the usual row reduction.  configs[0]'s 512-point steps spent 82 us in eleven tile-kernel launches
   if (ns == 0 && c->opt_small_step && B <= NIF_SMALL_MAX_B && c->kind != NIF_KIND_LASTLAYER && !act_on(c) && !c->opt_fp32_mfma) {
@@ -1638,7 +1612,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
       const int rows = small_rows(B);
       if (rows > c->rows_cap()) return fail(NIF_ERR_STATE, "internal: partial-row buffer too small for the small-batch step");
       if (rows > c->loss_partial.n) return fail(NIF_ERR_STATE, "internal: loss partial buffer too small for the small-batch step");
-      c->reg_applied = false;
+      c->grad_rewritten();
       sa.y = y; sa.sw = sw; sa.loss_partial = c->loss_partial; sa.inv_bg = 1.0f / (float)Bg;
       rc = ensure_small_tables(c, pa, sa); if (rc) return rc;
       const bool mp = c->metric_pending && c->metric != nullptr;
@@ -1668,7 +1642,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
     PNetArgs pa; fill_pnet(c, pa, xin, B);
     rc = ensure_zt_par(c, pa, ntiles, true); if (rc) return rc;
   }
-  c->reg_applied = false;
+  c->grad_rewritten();
   if (c->kind == NIF_KIND_LASTLAYER) return loss_grad_ll(c, xin, y, sw, B, Bg, ns, sp, gt, wj);
   // Two-stream pipeline over chunks of the batch (plain step on the 16-point-tile kernels): the fused ShapeNet kernel of
   // chunk i+1 (VALU / latency bound, 2 workgroups per CU) overlaps the HBM-bound weight-gradient reductions of chunk i
@@ -1738,6 +1712,7 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
 
 extern "C" int nif_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, int64_t Bg) {
   if (!c || !xin || !y || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
+  NIF_ENTER(c, NIF_FLUSH_TAIL)      // (a step whose gradient was never consumed: its rows are about to be overwritten)
   return loss_grad_core(c, xin, y, sw, B, Bg, 0, nullptr, nullptr, 0.f);
 }
 
@@ -1746,8 +1721,7 @@ extern "C" int nif_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, c
 extern "C" int nif_reserve(nif_ctx* c, int64_t B_max, int32_t n_tangents) {
   if (!c || B_max <= 0 || n_tangents < 0 || n_tangents > 16) return fail(NIF_ERR_INVALID, "bad argument");
   if (n_tangents > 3) n_tangents = 3;      // (more x_index columns run as passes over groups of three)
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = ensure_packed(c); if (rc) return rc;
   const long ntiles = (B_max + 31) / 32;
   rc = ensure_capacity(c, ntiles * 32 * (1 + n_tangents), true); if (rc) return rc;
@@ -1831,14 +1805,10 @@ static int sob_cols_per_pass(nif_ctx* c, const int32_t* x_idx, int nx) {
   return 1;
 }
 
-extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const float* y, const float* dydx, const float* sw,
-                                           int64_t B, int64_t Bg, const int32_t* x_idx, int32_t nx, const int32_t* y_idx, int32_t ny,
-                                           float w_jac) {
-  if (!c || !xin || !y || !dydx || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
-  unsigned ymask; int nys;
-  int rc = sobolev_check(c, x_idx, nx, y_idx, ny, &ymask, &nys); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+// the first-order Sobolev step behind its entry points' checks and guard; ymask / nys: sobolev_check's
+static int sobolev_step(nif_ctx* c, const float* xin, const float* y, const float* dydx, const float* sw, int64_t B, int64_t Bg,
+                        const int32_t* x_idx, int32_t nx, unsigned ymask, int nys, float w_jac) {
+  int rc = NIF_OK;
   const int gs = sob_cols_per_pass(c, x_idx, nx);
   const int ngroups = (nx + gs - 1) / gs;
   if (ngroups > 1 && !c->sob_acc) { rc = c->sob_acc.alloc(c->P + 1); if (rc) return rc; }
@@ -1858,13 +1828,26 @@ extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const f
   }
   if (rc) return rc;
   if (ngroups > 1) HIPCHK(hipMemcpyAsync(c->grad, c->sob_acc, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
-  c->reg_applied = false;
+  c->grad_rewritten();
   HIPCHK(hipGetLastError());
   return NIF_OK;
 }
+extern "C" int nif_sobolev_loss_grad_dev_y(nif_ctx* c, const float* xin, const float* y, const float* dydx, const float* sw,
+                                           int64_t B, int64_t Bg, const int32_t* x_idx, int32_t nx, const int32_t* y_idx, int32_t ny,
+                                           float w_jac) {
+  if (!c || !xin || !y || !dydx || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
+  unsigned ymask; int nys;
+  const int rc = sobolev_check(c, x_idx, nx, y_idx, ny, &ymask, &nys); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
+  return sobolev_step(c, xin, y, dydx, sw, B, Bg, x_idx, nx, ymask, nys, w_jac);
+}
 extern "C" int nif_sobolev_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, const float* dydx, const float* sw,
                                          int64_t B, int64_t Bg, const int32_t* x_idx, int32_t nx, float w_jac) {
-  return nif_sobolev_loss_grad_dev_y(c, xin, y, dydx, sw, B, Bg, x_idx, nx, nullptr, 0, w_jac);
+  if (!c || !xin || !y || !dydx || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
+  unsigned ymask; int nys;
+  const int rc = sobolev_check(c, x_idx, nx, nullptr, 0, &ymask, &nys); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
+  return sobolev_step(c, xin, y, dydx, sw, B, Bg, x_idx, nx, ymask, nys, w_jac);
 }
 // Second-order Sobolev step (HessianLayer as a trained output, gradient.py:130-180, :234-261): pass 0 is the first-order step above
 // (u, du/dx and every regulariser), then one k_sob<.., HESS> pass per unordered coordinate pair j <= k with the primal and first-order
@@ -1884,9 +1867,8 @@ extern "C" int nif_sobolev2_loss_grad_dev(nif_ctx* c, const float* xin, const fl
     if (x_idx[d] < c->pi)
       return fail(NIF_ERR_INVALID, std::string("second-order Sobolev step: parameter columns in x_index are not built (") + built + ")");
   if (c->capturing) return fail(NIF_ERR_STATE, "second-order Sobolev step inside a graph capture (not supported: run it uncaptured)");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  rc = nif_sobolev_loss_grad_dev_y(c, xin, y, dydx, sw, B, Bg, x_idx, nx, y_idx, ny, w_jac); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
+  rc = sobolev_step(c, xin, y, dydx, sw, B, Bg, x_idx, nx, ymask, nys, w_jac); if (rc) return rc;
   if (!c->sob2_acc) { rc = c->sob2_acc.alloc(c->P + 1); if (rc) return rc; }
   HIPCHK(hipMemcpyAsync(c->sob2_acc, c->grad, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
   {
@@ -1906,7 +1888,7 @@ extern "C" int nif_sobolev2_loss_grad_dev(nif_ctx* c, const float* xin, const fl
   }
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->grad, c->sob2_acc, sizeof(float) * (size_t)(c->P + 1), hipMemcpyDeviceToDevice, c->st));
-  c->reg_applied = false;
+  c->grad_rewritten();
   HIPCHK(hipGetLastError());
   return NIF_OK;
 }
@@ -1916,8 +1898,7 @@ extern "C" int nif_sobolev_forward_dev(nif_ctx* c, const float* xin, int64_t B, 
   if (!c || !xin || !u || !dudx || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
   unsigned ymask; int nys;
   int rc = sobolev_check(c, x_idx, nx, nullptr, 0, &ymask, &nys); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   const int gs = sob_cols_per_pass(c, x_idx, nx);
   for (int g0 = 0; g0 < nx; g0 += gs) {      // groups of <= 3 columns, each filling its columns of the [B][so][nx] rows
     const int ng = nx - g0 < gs ? nx - g0 : gs;
@@ -1930,9 +1911,7 @@ extern "C" int nif_sobolev_forward_dev(nif_ctx* c, const float* xin, int64_t B, 
   return NIF_OK;
 }
 static int sobolev_forward_group(nif_ctx* c, const float* xin, int64_t B, const SobPlan& sp, int nx, float* u, float* dudx) {
-  int rc;
-  HIPCHK(hipSetDevice(c->dev));
-  rc = ensure_packed(c); if (rc) return rc;
+  int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_packed32(c); if (rc) return rc;
   if (c->kind != NIF_KIND_LASTLAYER && !c->jac_ok)
     return fail(NIF_ERR_INVALID, "Sobolev path: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
@@ -2091,10 +2070,8 @@ static int ensure_metric(nif_ctx* c) {
 }
 extern "C" int nif_metric_accumulate(nif_ctx* c, float weight) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_METRIC)      // (an earlier accumulation that still waits: first, with the loss it was called for)
   { const int rcm = ensure_metric(c); if (rcm) return rcm; }
-  int rc = nif_metric_flush(c); if (rc) return rc;
   if (c->last_step_small && c->opt_small_step && !c->capturing && !c->comm) {     // behind a small step: rides in the next k_small launch (grad[P] is not
     c->metric_pending = true; c->metric_pending_w = weight;          // touched before that launch's row reduction; every other path flushes)
     return NIF_OK;
@@ -2105,10 +2082,8 @@ extern "C" int nif_metric_accumulate(nif_ctx* c, float weight) {
 }
 extern "C" int nif_metric_read(nif_ctx* c, double* sum, double* cnt, int reset) {
   if (!c || !sum || !cnt) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   double h[2] = {0.0, 0.0};
-  { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }
   if (c->metric) {
     HIPCHK(hipMemcpyAsync(h, c->metric, 2 * sizeof(double), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -2128,11 +2103,9 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   if (c->capturing) return fail(NIF_ERR_STATE, "nif_graph_begin: already capturing");
   if (c->comm) return fail(NIF_ERR_STATE, "nif_graph_begin: not with a communicator attached (the all-reduce is not captured)");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  int rc = nif_metric_flush(c); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   c->last_step_small = false;
-  rc = ensure_packed(c); if (rc) return rc;
+  int rc = ensure_packed(c); if (rc) return rc;
   if (c->kind != NIF_KIND_LASTLAYER) {      // (a captured small step must find its tables)
     PNetArgs pa; fill_pnet(c, pa, nullptr, 32);
     SNetArgs sa; fill_snet(c, sa, nullptr, c->pi + c->si, c->pi, 32);
@@ -2144,18 +2117,19 @@ extern "C" int nif_graph_begin(nif_ctx* c) {
   HIPCHK(hipStreamSynchronize(c->st));
   // (ensure_packed above did every first-use initialisation eagerly; the RECORDED sequence must start with the packing of whatever
   // weights the previous replay left behind)
-  c->packed = false; c->packed32 = false; c->packed_p32 = false;
+  c->planes_stale();
   HIPCHK(hipStreamBeginCapture(c->st, hipStreamCaptureModeRelaxed));
-  c->capturing = true; c->cap_steps = 0; c->cap_step0 = c->step; c->cap_kind = -1; c->cap_ams = false; c->cap_ema = false; c->cap_gt = 0;
+  c->capturing = true; c->rec = CapInfo(); c->rec.step0 = c->step;
   return NIF_OK;
 }
 extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   if (!c || !graph_id) return fail(NIF_ERR_INVALID, "null");
   if (!c->capturing) return fail(NIF_ERR_STATE, "nif_graph_end without nif_graph_begin");
+  NIF_ENTER(c, NIF_FLUSH_NONE)             // (nothing defers inside a capture, and nothing recorded has run)
   c->capturing = false;
   c->last_step_small = false;              // (set by the RECORDED small steps: no eager one ran, the next nif_metric_accumulate must not wait for a k_small launch)
-  c->step = c->cap_step0;                  // nothing has run yet: the recorded steps count when the graph is launched
-  c->packed = false; c->packed32 = false; c->packed_p32 = false;
+  c->step = c->rec.step0;                  // nothing has run yet: the recorded steps count when the graph is launched
+  c->planes_stale();
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(c->st, &g);
   if (e != hipSuccess || !g) { (void)hipGetLastError(); return fail(NIF_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); }
@@ -2163,15 +2137,16 @@ extern "C" int nif_graph_end(nif_ctx* c, int32_t* graph_id) {
   e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) { (void)hipGetLastError(); return fail(NIF_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
-  c->graphs.push_back(ex); c->graph_steps.push_back(c->cap_steps);
-  c->graph_kind.push_back(c->cap_kind); c->graph_ams.push_back(c->cap_ams ? 1 : 0); c->graph_gt.push_back((char)c->cap_gt);
-  c->graph_ema.push_back(c->cap_ema ? 1 : 0);
+  c->rec.step0 = 0;      // (the running capture's alone)
+  c->graphs.push_back({ex, c->rec});
   *graph_id = (int32_t)c->graphs.size() - 1;
   return NIF_OK;
 }
 extern "C" int nif_graph_destroy(nif_ctx* c, int32_t graph_id) {
   if (!c || graph_id < 0 || graph_id >= (int32_t)c->graphs.size()) return fail(NIF_ERR_INVALID, "bad argument");
-  if (c->graphs[graph_id]) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipGraphExecDestroy(c->graphs[graph_id]); c->graphs[graph_id] = nullptr; }
+  NIF_ENTER(c, NIF_FLUSH_NONE)      // (drops an executable: reads nothing a deferred piece would change)
+  hipGraphExec_t& ex = c->graphs[graph_id].exec;
+  if (ex) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipGraphExecDestroy(ex); ex = nullptr; }
   return NIF_OK;
 }
 
@@ -2222,8 +2197,7 @@ extern "C" int nif_set_grad_transform(nif_ctx* c, const nif_grad_transform* t) {
   const bool gtcf = (z.flags & NIF_GT_GTCF) != 0;
   const bool on = (z.flags & NIF_GT_CENTRALIZE) || z.clipnorm > 0.f || z.clipvalue > 0.f || z.global_clipnorm > 0.f;
   if (!on && !c->gt_dev) { c->gt = z; c->gt_on = false; c->gt_norm = false; return NIF_OK; }
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));      // (queued steps still read the device copy)
   GtDev d; d.flags = z.flags; d.clipnorm = z.clipnorm; d.clipvalue = z.clipvalue; d.global_clipnorm = z.global_clipnorm;
   if (!c->gt_dev) {
@@ -2249,13 +2223,12 @@ extern "C" int nif_set_grad_transform(nif_ctx* c, const nif_grad_transform* t) {
 static void gt_run(nif_ctx* c) {
   launch_gt_reduce(c->grad, c->gt_blk, c->gt_nblk, c->gt_part, c->gt_dev, c->st);
   if (c->gt_norm) launch_gt_apply(c->grad, c->gt_blk, c->gt_nblk, (int)c->layout.size(), c->gt_part, c->gt_norms, c->gt_dev, true, c->st);
-  if (c->capturing) c->cap_gt = gt_launches(c);      // (nothing has run yet: graph_replay marks the norms)
+  if (c->capturing) c->rec.gt = gt_launches(c);      // (nothing has run yet: graph_replay marks the norms)
   else c->gt_ran = c->gt_norm ? 2 : 1;
 }
 extern "C" int nif_grad_transform_dev(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
   if (c->gt_on) gt_run(c);
   HIPCHK(hipGetLastError());
@@ -2266,8 +2239,7 @@ extern "C" int nif_grad_norms(nif_ctx* c, float* per_tensor, int32_t n, float* g
   if (per_tensor && n != (int32_t)c->layout.size()) return fail(NIF_ERR_INVALID, "nif_grad_norms: n is the tensor count of nif_param_layout");
   if (c->capturing) return fail(NIF_ERR_STATE, "nif_grad_norms: not inside a graph capture");
   if (!c->gt_ran) return fail(NIF_ERR_STATE, "nif_grad_norms: no gradient transform has run on this context");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   if (c->gt_ran == 1) {      // the last transform had no norm stage: its partial sums are there, the norms are formed now
     launch_gt_apply(c->grad, c->gt_blk, c->gt_nblk, (int)c->layout.size(), c->gt_part, c->gt_norms, c->gt_dev, false, c->st);
     HIPCHK(hipGetLastError());
@@ -2367,27 +2339,21 @@ extern "C" int nif_opt_scalars(const nif_opt* o, int64_t t, double* out) {
   out[0] = s.lr; out[1] = s.bc1; out[2] = s.bc2; out[3] = s.r; out[4] = (double)s.div;
   return NIF_OK;
 }
-// The epilogue of every update of theta by an optimizer step: the packed weight planes are stale, and the regulariser term belongs to ONE
-// gradient -- a following step that skips nif_loss_grad_dev (nif_zero_grad on a rank whose shard ran out of rows) must add it again,
-// like the ranks that did compute a gradient
-static void theta_stepped(nif_ctx* c) {
-  c->packed = false; c->packed32 = false; c->packed_p32 = false;
-  c->reg_applied = false;
-}
 // One optimizer step of any kind, after the all-reduce, in one of three forms: fused with the deferred row reduction (tail_can_defer,
 // no gradient transform set);
 // inside a capture with the scalars from c->opt_dev at replay time (graph_replay refreshes it); else after the flushed reduction and the
-// regulariser term.  `who` names the entry point in the error messages.
+// regulariser term.  `who` names the entry point in the error messages.  Its epilogue (nif_ctx::theta_stepped): the packed weight planes
+// are stale, and the regulariser term belongs to ONE gradient -- a following step that skips nif_loss_grad_dev (nif_zero_grad on a rank
+// whose shard ran out of rows) must add it again, like the ranks that did compute a gradient
 static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
   const bool ams = opt_ams(opt);
   const int kk = opt_kk(opt);
   const bool ema = c->opt_ema != 0;
-  if (c->capturing && c->cap_kind >= 0 && (c->cap_kind != kk || c->cap_ams != ams))
+  if (c->capturing && c->rec.kind >= 0 && (c->rec.kind != kk || c->rec.ams != ams))
     return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps of another optimizer kind / amsgrad flag (one per graph)");
-  if (c->capturing && c->cap_kind >= 0 && c->cap_ema != ema)
-    return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps recorded with weight averaging (\"ema\") " + (c->cap_ema ? "on" : "off") + " (one setting per graph)");
-  HIPCHK(hipSetDevice(c->dev));
+  if (c->capturing && c->rec.kind >= 0 && c->rec.ema != ema)
+    return fail(NIF_ERR_STATE, std::string(who) + ": this capture already holds steps recorded with weight averaging (\"ema\") " + (c->rec.ema ? "on" : "off") + " (one setting per graph)");
   if (ams) { const int rc = ensure_vhat(c); if (rc) return rc; }
   if (ema) { const int rc = ensure_ema(c, true); if (rc) return rc; }      // (seeded with theta before this step's update)
   if (opt->kind == NIF_OPT_ADAGRAD && c->slots_fresh && opt->init_acc != 0.f) { const int rc = adagrad_fill(c, opt->init_acc); if (rc) return rc; }
@@ -2398,7 +2364,7 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
   if (fused) {
     c->tail_pending = false;
   } else {
-    TAIL_FLUSH(c)
+    { const int rct_ = nif_tail_flush(c); if (rct_) return rct_; }
     { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
     if (c->gt_on) gt_run(c);
   }
@@ -2412,13 +2378,13 @@ static int opt_step(nif_ctx* c, const nif_opt* opt, const char* who) {
                       c->v, c->vhat, av, a, c->st);
   } else if (c->capturing) {
     launch_opt_dev(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, av, c->P, c->opt_dev, c->st);
-    c->cap_steps += 1; c->cap_kind = kk; c->cap_ams = ams; c->cap_ema = ema;
+    c->rec.steps += 1; c->rec.kind = kk; c->rec.ams = ams; c->rec.ema = ema;
   } else {
     ProfScope p_(c, NIF_PROF_ADAM);
     launch_opt(kk, ams, c->theta, c->grad, c->m, c->v, c->vhat, av, c->P, a, c->st);
   }
   HIPCHK(hipGetLastError());
-  theta_stepped(c);
+  c->theta_stepped();
   return NIF_OK;
 }
 static nif_opt opt_of_adam(const nif_adam* a) {
@@ -2429,55 +2395,63 @@ static nif_opt opt_of_adam(const nif_adam* a) {
 extern "C" int nif_adam_step_dev(nif_ctx* c, const nif_adam* opt) {
   if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
   const nif_opt o = opt_of_adam(opt);
+  NIF_ENTER(c, NIF_FLUSH_NONE)      // (the step consumes the tail itself: fused with the update where it can, opt_step)
   return opt_step(c, &o, "nif_adam_step_dev");
 }
 extern "C" int nif_opt_step_dev(nif_ctx* c, const nif_opt* opt) {
   if (!c || !opt) return fail(NIF_ERR_INVALID, "null");
   const int rc = opt_check(opt); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_NONE)      // (as nif_adam_step_dev)
   return opt_step(c, opt, "nif_opt_step_dev");
 }
-// replays a captured graph with opt's hyper-parameters (its kind checked by the caller) and the context's iteration count
-static int graph_replay(nif_ctx* c, int32_t graph_id, const nif_opt* opt, const char* who) {
+// what a replay of a graph is refused for by the context's state (the caller has checked the optimizer against g.kind / g.ams)
+static int graph_replay_refused(const nif_ctx* c, const CapInfo& g, const char* who) {
   if (c->capturing) return fail(NIF_ERR_STATE, std::string(who) + " while capturing");
-  if (gt_launches(c) > c->graph_gt[graph_id])
+  if (gt_launches(c) > g.gt)
     return fail(NIF_ERR_STATE, std::string(who) + ": the context's gradient transform needs launches this graph did not record (set it before the capture)");
   const bool ema = c->opt_ema != 0;
-  if (c->graph_kind[graph_id] >= 0 && (c->graph_ema[graph_id] != 0) != ema)
-    return fail(NIF_ERR_STATE, std::string(who) + ": the graph was recorded with weight averaging (\"ema\") " + (c->graph_ema[graph_id] ? "on" : "off") + ", the context has it " + (ema ? "on" : "off") + " (set it before the capture)");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  if (ema && c->graph_kind[graph_id] >= 0) { const int rce = ensure_ema(c, true); if (rce) return rce; }      // (reset by nif_set_opt_state since the capture: seeded again, at the recorded address)
-  { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }      // (the replay overwrites grad[P]: a deferred accumulation takes the loss of the step it was called for)
+  if (g.kind >= 0 && g.ema != ema)
+    return fail(NIF_ERR_STATE, std::string(who) + ": the graph was recorded with weight averaging (\"ema\") " + (g.ema ? "on" : "off") + ", the context has it " + (ema ? "on" : "off") + " (set it before the capture)");
+  return NIF_OK;
+}
+// replays a captured graph with opt's hyper-parameters and the context's iteration count, behind graph_replay_refused and the guard (the
+// replay overwrites grad[P]: a deferred accumulation has taken the loss of the step it was called for)
+static int graph_replay(nif_ctx* c, const CapGraph& g, const nif_opt* opt) {
+  if (c->opt_ema != 0 && g.info.kind >= 0) { const int rce = ensure_ema(c, true); if (rce) return rce; }      // (reset by nif_set_opt_state since the capture: seeded again, at the recorded address)
   HIPCHK(hipStreamSynchronize(c->st));      // (the pinned staging struct is reused: the previous launch's copy must be through)
   *c->opt_host = opt_dev_of(c, opt, c->step);
   HIPCHK(hipMemcpyAsync(c->opt_dev, c->opt_host, sizeof(OptDev), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipGraphLaunch(c->graphs[graph_id], c->st));
-  c->step += c->graph_steps[graph_id];
-  if (c->graph_gt[graph_id]) c->gt_ran = c->graph_gt[graph_id];
-  theta_stepped(c);
+  HIPCHK(hipGraphLaunch(g.exec, c->st));
+  c->step += g.info.steps;
+  if (g.info.gt) c->gt_ran = g.info.gt;
+  c->theta_stepped();
   return NIF_OK;
 }
-static bool graph_ok(const nif_ctx* c, int32_t graph_id) { return graph_id >= 0 && graph_id < (int32_t)c->graphs.size() && c->graphs[graph_id]; }
+static bool graph_ok(const nif_ctx* c, int32_t graph_id) { return graph_id >= 0 && graph_id < (int32_t)c->graphs.size() && c->graphs[graph_id].exec; }
 extern "C" int nif_graph_launch(nif_ctx* c, int32_t graph_id, const nif_adam* opt) {
   if (!c || !opt || !graph_ok(c, graph_id)) return fail(NIF_ERR_INVALID, "bad argument");
-  if (c->graph_kind[graph_id] > OPT_ADAM || c->graph_ams[graph_id])
+  const CapGraph& g = c->graphs[graph_id];
+  if (g.info.kind > OPT_ADAM || g.info.ams)
     return fail(NIF_ERR_STATE, "nif_graph_launch: the graph holds Lion / AdaBelief steps or those of another nif_opt kind (nif_graph_launch_opt with that optimizer)");
   const nif_opt o = opt_of_adam(opt);
-  return graph_replay(c, graph_id, &o, "nif_graph_launch");
+  const int rc = graph_replay_refused(c, g.info, "nif_graph_launch"); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
+  return graph_replay(c, g, &o);
 }
 extern "C" int nif_graph_launch_opt(nif_ctx* c, int32_t graph_id, const nif_opt* opt) {
   if (!c || !opt || !graph_ok(c, graph_id)) return fail(NIF_ERR_INVALID, "bad argument");
-  const int rc = opt_check(opt); if (rc) return rc;
-  const int rk = c->graph_kind[graph_id];
-  if (rk >= 0 && (rk != opt_kk(opt) || (c->graph_ams[graph_id] != 0) != opt_ams(opt)))
+  int rc = opt_check(opt); if (rc) return rc;
+  const CapGraph& g = c->graphs[graph_id];
+  if (g.info.kind >= 0 && (g.info.kind != opt_kk(opt) || g.info.ams != opt_ams(opt)))
     return fail(NIF_ERR_INVALID, "nif_graph_launch_opt: the graph was recorded with another optimizer kind / amsgrad flag (or centered / decoupled weight decay flag)");
-  return graph_replay(c, graph_id, opt, "nif_graph_launch_opt");
+  rc = graph_replay_refused(c, g.info, "nif_graph_launch_opt"); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
+  return graph_replay(c, g, opt);
 }
 extern "C" int nif_get_opt_slot(nif_ctx* c, int32_t slot, float* host, int64_t n) {
   if (!c || !host || slot < 0 || slot > 3) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat, 3 weight average)");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   float* src = slot == 0 ? c->m : slot == 1 ? c->v : slot == 2 ? c->vhat : c->ema;
   if (slot == 3 && !c->ema_valid) src = nullptr;      // (reset by nif_set_opt_state: zeros until the next step seeds it)
   if (!src) { memset(host, 0, sizeof(float) * (size_t)n); return NIF_OK; }
@@ -2489,8 +2463,7 @@ extern "C" int nif_set_opt_slot(nif_ctx* c, int32_t slot, const float* host, int
   if (!c || !host || slot < 0 || slot > 3) return fail(NIF_ERR_INVALID, "bad argument (slot: 0 m, 1 v, 2 vhat, 3 weight average)");
   if (n != c->P) return fail(NIF_ERR_INVALID, "parameter count mismatch");
   if (c->capturing) return fail(NIF_ERR_STATE, "nif_set_opt_slot while capturing");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   if (slot == 2) { const int rc = ensure_vhat(c); if (rc) return rc; }
   if (slot == 3) { const int rc = ensure_ema(c, false); if (rc) return rc; }
   float* dst = slot == 0 ? c->m : slot == 1 ? c->v : slot == 2 ? c->vhat : c->ema;
@@ -2505,13 +2478,12 @@ static void prune_free(nif_ctx* c) {
   c->prune_segs_dev.drop(); c->prune_mask.drop(); c->prune_thr.drop(); c->prune_hist.drop(); c->prune_sel.drop();
   c->prune_segs.clear(); c->prune_nblk = 0; c->prune_lo = 0; c->prune_hi = 0;
 }
-// what every nif_prune_* call does first: no capture, the deferred row reduction and loss-metric accumulation run now
-static int prune_enter(nif_ctx* c, bool need_config) {
+// what every nif_prune_* call is refused for, in front of its guard (NIF_FLUSH_METRIC throughout: the calls of a pruning callback settle
+// everything deferred)
+static int prune_refused(const nif_ctx* c, bool need_config) {
   if (c->capturing) return fail(NIF_ERR_STATE, "nif_prune_*: not inside a graph capture");
   if (need_config && c->prune_segs.empty()) return fail(NIF_ERR_STATE, "pruning is not configured (nif_prune_config)");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  return nif_metric_flush(c);
+  return NIF_OK;
 }
 extern "C" int nif_prune_config(nif_ctx* c, int32_t n, const int64_t* offsets, const int64_t* sizes) {
   if (!c || n < 0 || (n > 0 && (!offsets || !sizes))) return fail(NIF_ERR_INVALID, "bad argument");
@@ -2525,7 +2497,8 @@ extern "C" int nif_prune_config(nif_ctx* c, int32_t n, const int64_t* offsets, c
     nblk += (sz + PRUNE_CHUNK - 1) / PRUNE_CHUNK;
     end = off + sz;
   }
-  int rc = prune_enter(c, false); if (rc) return rc;
+  int rc = prune_refused(c, false); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   HIPCHK(hipStreamSynchronize(c->st));      // (queued work may still read the buffers freed here)
   prune_free(c);
   if (n == 0) return NIF_OK;
@@ -2549,7 +2522,8 @@ extern "C" int nif_prune_config(nif_ctx* c, int32_t n, const int64_t* offsets, c
 extern "C" int nif_prune_update(nif_ctx* c, const int64_t* k) {
   if (!c || !k) return fail(NIF_ERR_INVALID, "null");
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
-  int rc = prune_enter(c, true); if (rc) return rc;
+  int rc = prune_refused(c, true); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   const int n = (int)c->prune_segs.size();
   for (int i = 0; i < n; ++i)
     if (k[i] < 1 || k[i] > c->prune_segs[i].size) return fail(NIF_ERR_INVALID, "nif_prune_update: 1 <= k <= the segment's size");
@@ -2563,10 +2537,11 @@ extern "C" int nif_prune_update(nif_ctx* c, const int64_t* k) {
 extern "C" int nif_prune_apply(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set");
-  int rc = prune_enter(c, true); if (rc) return rc;
+  int rc = prune_refused(c, true); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   launch_prune_apply(c->theta, c->prune_mask, c->prune_lo, c->prune_hi, c->P, c->st);
   HIPCHK(hipGetLastError());
-  c->packed = false; c->packed32 = false; c->packed_p32 = false;      // (theta changed: no stale ShapeNet / ParameterNet planes)
+  c->planes_stale();      // (theta changed)
   return NIF_OK;
 }
 static long prune_total(const nif_ctx* c) {
@@ -2576,7 +2551,8 @@ static long prune_total(const nif_ctx* c) {
 }
 extern "C" int nif_get_prune_state(nif_ctx* c, float* masks, int64_t n_mask, float* thr, int32_t n_seg) {
   if (!c || !masks || !thr) return fail(NIF_ERR_INVALID, "null");
-  int rc = prune_enter(c, true); if (rc) return rc;
+  int rc = prune_refused(c, true); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   if (n_mask != prune_total(c) || n_seg != (int32_t)c->prune_segs.size()) return fail(NIF_ERR_INVALID, "nif_get_prune_state: size mismatch");
   std::vector<unsigned char> h((size_t)c->P);
   HIPCHK(hipMemcpyAsync(h.data(), c->prune_mask, (size_t)c->P, hipMemcpyDeviceToHost, c->st));
@@ -2589,7 +2565,8 @@ extern "C" int nif_get_prune_state(nif_ctx* c, float* masks, int64_t n_mask, flo
 }
 extern "C" int nif_set_prune_state(nif_ctx* c, const float* masks, int64_t n_mask, const float* thr, int32_t n_seg) {
   if (!c || !masks || !thr) return fail(NIF_ERR_INVALID, "null");
-  int rc = prune_enter(c, true); if (rc) return rc;
+  int rc = prune_refused(c, true); if (rc) return rc;
+  NIF_ENTER(c, NIF_FLUSH_METRIC)
   if (n_mask != prune_total(c) || n_seg != (int32_t)c->prune_segs.size()) return fail(NIF_ERR_INVALID, "nif_set_prune_state: size mismatch");
   std::vector<unsigned char> h((size_t)c->P + 16, 1);
   long o = 0;
@@ -2607,12 +2584,10 @@ extern "C" int nif_set_prune_state(nif_ctx* c, const float* masks, int64_t n_mas
 // A rank whose shard has no rows left for a step still joins the collective: with a zero [grad | loss] buffer.
 extern "C" int nif_zero_grad(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  { const int rcf = nif_metric_flush(c); if (rcf) return rcf; }      // (a deferred loss-metric accumulation reads grad[P]: before it is cleared)
+  NIF_ENTER(c, NIF_FLUSH_METRIC)      // (a deferred loss-metric accumulation reads grad[P]: before it is cleared)
   c->last_step_small = false;
   HIPCHK(hipMemsetAsync(c->grad, 0, sizeof(float) * (size_t)(c->P + 1), c->st));
-  c->reg_applied = false;
+  c->grad_rewritten();
   return NIF_OK;
 }
 
@@ -2632,7 +2607,7 @@ extern "C" int nif_set_option(nif_ctx* c, const char* key, int32_t value) {
   if (strcmp(key, "small_step") == 0) { c->opt_small_step = value != 0; return NIF_OK; }   // 0: small batches on the tile kernels too (A/B, tests)
   if (strcmp(key, "fp32_mfma") == 0) {      // 1: every product on the f32-input MFMAs (k_snet3) instead of the bf16 splits
     c->opt_fp32_mfma = value != 0;
-    c->packed = false; c->packed32 = false; c->packed_p32 = false;
+    c->planes_stale();
     return NIF_OK;
   }
   if (strcmp(key, "snapshot_image_bytes") == 0) {      // nif_forward_snapshots*: bytes of combined nets held at once (0: the default; tests lower it)
@@ -2660,49 +2635,25 @@ extern "C" int nif_set_option(nif_ctx* c, const char* key, int32_t value) {
   return fail(NIF_ERR_INVALID, std::string("unknown option ") + key);
 }
 
-// The weight-regulariser term is added (once) and [grad | loss] copied to the host: the read-out half of
-// nif_loss_and_grad for callers that keep the dataset resident (L-BFGS closure).  Either pointer may be NULL.
-extern "C" int nif_grad_read(nif_ctx* c, float* loss, float* grad) {
-  if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
+// The one read-out of [grad | loss] to the host, behind the caller's tail flush; either pointer may be NULL.  with_reg: the
+// weight-regulariser term is added first (once per gradient: apply_reg)
+static int grad_to_host(nif_ctx* c, float* loss, float* grad, bool with_reg) {
+  if (with_reg) { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
   if (grad) HIPCHK(hipMemcpyAsync(grad, c->grad, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToHost, c->st));
   if (loss) HIPCHK(hipMemcpyAsync(loss, c->grad + c->P, sizeof(float), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }
-
-// ---- the L-BFGS closure in double (k_f64.hip; reference nif/optimizers/lbfgs.py:56-88, lbfgs_V2.py:57-79) -------------------------------
-// A float64 master vector, [grad | loss] buffer and workspace of their own: theta, grad, the optimizer slots and a pending row reduction
-// of the float32 path are neither read nor written, so none of these calls flushes the tail.
-extern "C" int nif_f64_set_params(nif_ctx* c, const double* host, int64_t n) {
-  if (!c || !host) return fail(NIF_ERR_INVALID, "null");
-  return nif_f64_set_params_impl(c, host, n);
-}
-extern "C" int nif_f64_get_params(nif_ctx* c, double* host, int64_t n) {
-  if (!c || !host) return fail(NIF_ERR_INVALID, "null");
-  return nif_f64_get_params_impl(c, host, n);
-}
-extern "C" int nif_f64_forward_dev(nif_ctx* c, const double* xin, int64_t B, double* u) {
-  if (!c || !xin || !u || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  return nif_f64_forward_dev_impl(c, xin, B, u);
-}
-extern "C" int nif_f64_loss_grad_dev(nif_ctx* c, const double* xin, const double* y, const double* sw, int64_t B, int64_t Bg) {
-  if (!c || !xin || !y || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
-  return nif_f64_loss_grad_dev_impl(c, xin, y, sw, B, Bg);
-}
-extern "C" int nif_f64_grad_read(nif_ctx* c, double* loss, double* grad) {
+// the read-out half of nif_loss_and_grad for callers that keep the dataset resident (L-BFGS closure)
+extern "C" int nif_grad_read(nif_ctx* c, float* loss, float* grad) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  return nif_f64_grad_read_impl(c, loss, grad);
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
+  return grad_to_host(c, loss, grad, true);
 }
 extern "C" int nif_last_loss(nif_ctx* c, float* loss) {
   if (!c || !loss) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
-  HIPCHK(hipMemcpyAsync(loss, c->grad + c->P, sizeof(float), hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return NIF_OK;
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
+  return grad_to_host(c, loss, nullptr, false);
 }
 
 static int stage_batch(nif_ctx* c, const float* xin, const float* y, const float* sw, long B) {
@@ -2713,7 +2664,6 @@ static int stage_batch(nif_ctx* c, const float* xin, const float* y, const float
   return NIF_OK;
 }
 int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, float** dx, float** dy, float** dsw) {
-  HIPCHK(hipSetDevice(c->dev));
   int rc = stage_batch(c, xin, y, sw, B); if (rc) return rc;
   *dx = c->d_a; *dy = c->d_b; *dsw = sw ? c->d_c : nullptr;
   return NIF_OK;
@@ -2722,29 +2672,21 @@ int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* s
 extern "C" int nif_loss_and_grad(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, float* loss,
                                  float* grad) {
   if (!c || !xin || !y || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = stage_batch(c, xin, y, sw, B); if (rc) return rc;
-  rc = nif_loss_grad_dev(c, c->d_a, c->d_b, sw ? c->d_c : nullptr, B, B); if (rc) return rc;
-  TAIL_FLUSH(c)
-  { const int rcr_ = apply_reg(c); if (rcr_) return rcr_; }
-  if (grad) HIPCHK(hipMemcpyAsync(grad, c->grad, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToHost, c->st));
-  if (loss) HIPCHK(hipMemcpyAsync(loss, c->grad + c->P, sizeof(float), hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return NIF_OK;
+  rc = loss_grad_core(c, c->d_a, c->d_b, sw ? c->d_c : nullptr, B, B, 0, nullptr, nullptr, 0.f); if (rc) return rc;
+  return nif_grad_read(c, loss, grad);      // (through the guard again: the step may have left its row reduction pending)
 }
 
 extern "C" int nif_train_step(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B,
                               const nif_adam* opt, float* loss) {
   if (!c || !xin || !y || !opt || B <= 0) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = stage_batch(c, xin, y, sw, B); if (rc) return rc;
-  rc = nif_loss_grad_dev(c, c->d_a, c->d_b, sw ? c->d_c : nullptr, B, B); if (rc) return rc;
-  rc = nif_adam_step_dev(c, opt); if (rc) return rc;
-  if (loss) HIPCHK(hipMemcpyAsync(loss, c->grad + c->P, sizeof(float), hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return NIF_OK;
+  rc = loss_grad_core(c, c->d_a, c->d_b, sw ? c->d_c : nullptr, B, B, 0, nullptr, nullptr, 0.f); if (rc) return rc;
+  const nif_opt o = opt_of_adam(opt);
+  rc = opt_step(c, &o, "nif_adam_step_dev"); if (rc) return rc;      // (consumes the step's row reduction)
+  return grad_to_host(c, loss, nullptr, false);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2763,16 +2705,14 @@ static int drain_profile(nif_ctx* c) {
 }
 extern "C" int nif_profile_enable(nif_ctx* c, int on) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = drain_profile(c); if (rc) return rc;
   c->prof_on = on != 0;
   return NIF_OK;
 }
 extern "C" int nif_profile_read(nif_ctx* c, float* ms, int64_t* cnt, int n, int reset) {
   if (!c || !ms || !cnt || n < NIF_PROF_N) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   int rc = drain_profile(c); if (rc) return rc;
   for (int i = 0; i < NIF_PROF_N; ++i) { ms[i] = (float)c->prof_ms[i]; cnt[i] = c->prof_cnt[i]; }
   if (reset) for (int i = 0; i < NIF_PROF_N; ++i) { c->prof_ms[i] = 0; c->prof_cnt[i] = 0; }
@@ -2780,8 +2720,7 @@ extern "C" int nif_profile_read(nif_ctx* c, float* ms, int64_t* cnt, int n, int 
 }
 extern "C" int nif_debug_timeline(nif_ctx* c, int64_t* out, int32_t n_pairs) {
   if (!c || n_pairs < 0 || n_pairs > 2048) return fail(NIF_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   if (!c->tl) {
     DevBuf<long long> tl;
@@ -2796,16 +2735,14 @@ extern "C" int nif_debug_timeline(nif_ctx* c, int64_t* out, int32_t n_pairs) {
 }
 extern "C" int nif_timer_start(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   if (!c->t0) { HIPCHK(hipEventCreate(&c->t0)); HIPCHK(hipEventCreate(&c->t1)); }
   HIPCHK(hipEventRecord(c->t0, c->st));
   return NIF_OK;
 }
 extern "C" int nif_timer_stop(nif_ctx* c, float* ms) {
   if (!c || !ms || !c->t0) return fail(NIF_ERR_INVALID, "timer not started");
-  HIPCHK(hipSetDevice(c->dev));
-  TAIL_FLUSH(c)
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipEventRecord(c->t1, c->st));
   HIPCHK(hipEventSynchronize(c->t1));
   HIPCHK(hipEventElapsedTime(ms, c->t0, c->t1));

@@ -49,9 +49,7 @@ static int comm_scratch(nif_ctx* c) {
 extern "C" int nif_comm_init_rank(nif_ctx* c, const void* id, int32_t rank, int32_t world) {
   if (!c || !id || world < 1 || rank < 0 || rank >= world) return fail(NIF_ERR_INVALID, "bad argument");
   if (c->comm) return fail(NIF_ERR_STATE, "context already has a communicator");
-  HIPCHK(hipSetDevice(c->dev));
-  { const int rct = nif_tail_flush(c); if (rct) return rct; }      // (a deferred row reduction: the all-reduce reads [grad | loss])
-  { const int rcm = nif_metric_flush(c); if (rcm) return rcm; }    // (a deferred metric accumulation: with a communicator nothing defers, and the all-reduce rewrites grad[P])
+  NIF_ENTER(c, NIF_FLUSH_METRIC)      // (the all-reduce reads [grad | loss] and rewrites grad[P]; with a communicator nothing defers)
   ncclUniqueId uid;
   memcpy(&uid, id, NIF_COMM_ID_BYTES);
   ncclComm_t comm = nullptr;
@@ -66,8 +64,7 @@ extern "C" int nif_comm_init_all(nif_ctx** ctxs, int32_t n) {
   for (int i = 0; i < n; ++i) {
     if (!ctxs[i]) return fail(NIF_ERR_INVALID, "null context");
     if (ctxs[i]->comm) return fail(NIF_ERR_STATE, "context already has a communicator");
-    { const int rct = nif_tail_flush(ctxs[i]); if (rct) return rct; }
-    { const int rcm = nif_metric_flush(ctxs[i]); if (rcm) return rcm; }
+    if (ctxs[i]->tail_pending || ctxs[i]->metric_pending) NIF_ENTER(ctxs[i], NIF_FLUSH_METRIC)      // (as nif_comm_init_rank; no device change without work)
     devs[i] = ctxs[i]->dev;
     for (int j = 0; j < i; ++j)
       if (devs[j] == devs[i]) return fail(NIF_ERR_INVALID, "two contexts of one communicator on the same device");
@@ -76,7 +73,7 @@ extern "C" int nif_comm_init_all(nif_ctx** ctxs, int32_t n) {
   NCCLCHK(ncclCommInitAll(comms, n, devs));
   for (int i = 0; i < n; ++i) {
     ctxs[i]->comm = comms[i]; ctxs[i]->comm_rank = i; ctxs[i]->comm_world = n;
-    HIPCHK(hipSetDevice(ctxs[i]->dev));
+    NIF_ENTER(ctxs[i], NIF_FLUSH_NONE)      // (its device again, for the scratch word)
     int rc = comm_scratch(ctxs[i]); if (rc) return rc;
   }
   return NIF_OK;
@@ -85,7 +82,7 @@ extern "C" int nif_comm_init_all(nif_ctx** ctxs, int32_t n) {
 extern "C" int nif_comm_destroy(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   if (!c->comm) return NIF_OK;
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)      // (tears the communicator down: reads no buffer of the context)
   HIPCHK(hipStreamSynchronize(c->st));
   ncclComm_t comm = comm_of(c);
   c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1;
@@ -121,8 +118,7 @@ static int op_of(int32_t op, ncclRedOp_t* out) {
 extern "C" int nif_allreduce_grad(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
   if (!c->comm) return c->comm_world == 1 ? NIF_OK : fail(NIF_ERR_STATE, "no communicator");
-  HIPCHK(hipSetDevice(c->dev));
-  { const int rct = nif_tail_flush(c); if (rct) return rct; }
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
   NCCLCHK(ncclAllReduce(c->grad, c->grad, (size_t)(c->P + 1), ncclFloat32, ncclSum, comm_of(c), c->st));
   return NIF_OK;
 }
@@ -137,9 +133,7 @@ __global__ void k_fill_f32(float* __restrict__ p, long n, float v) {
 extern "C" int nif_comm_selftest(nif_ctx* c, int32_t* ranks_seen) {
   if (!c || !ranks_seen) return fail(NIF_ERR_INVALID, "null");
   if (!c->grad) return fail(NIF_ERR_STATE, "no gradient buffer");
-  HIPCHK(hipSetDevice(c->dev));
-  { const int rct = nif_tail_flush(c); if (rct) return rct; }
-  { const int rcm = nif_metric_flush(c); if (rcm) return rcm; }    // (the buffer is about to be filled and zeroed)
+  NIF_ENTER(c, NIF_FLUSH_METRIC)      // (the buffer is about to be filled and zeroed)
   const long n = c->P + 1;
   hipLaunchKernelGGL(k_fill_f32, dim3(64), dim3(256), 0, c->st, c->grad, n, (float)(c->comm_rank + 1));
   int rc = nif_allreduce_grad(c); if (rc) return rc;
@@ -164,7 +158,7 @@ extern "C" int nif_allreduce_grad_multi(nif_ctx** ctxs, int32_t n) {
   if (n == 1 && !ctxs[0]->comm) return NIF_OK;
   for (int i = 0; i < n; ++i)
     if (!ctxs[i] || !ctxs[i]->comm || ctxs[i]->comm_world != n) return fail(NIF_ERR_STATE, "contexts are not one nif_comm_init_all group");
-  for (int i = 0; i < n; ++i) { const int rct = nif_tail_flush(ctxs[i]); if (rct) return rct; }
+  for (int i = 0; i < n; ++i) if (ctxs[i]->tail_pending) NIF_ENTER(ctxs[i], NIF_FLUSH_TAIL)      // (no device change without work)
   NCCLCHK(ncclGroupStart());
   for (int i = 0; i < n; ++i) {
     nif_ctx* c = ctxs[i];
@@ -182,7 +176,7 @@ extern "C" int nif_comm_allreduce(nif_ctx* c, void* dev_buf, int64_t count, int3
   ncclDataType_t dt; ncclRedOp_t ro;
   int rc = dtype_of(dtype, &dt); if (rc) return rc;
   rc = op_of(op, &ro); if (rc) return rc;
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)      // (a caller-owned buffer: none of the context's)
   NCCLCHK(ncclAllReduce(dev_buf, dev_buf, (size_t)count, dt, ro, comm_of(c), c->st));
   return NIF_OK;
 }
@@ -190,7 +184,7 @@ extern "C" int nif_comm_allreduce(nif_ctx* c, void* dev_buf, int64_t count, int3
 // all ranks reach this point, and this context's stream has drained: an all-reduce of one word + a stream sync
 extern "C" int nif_comm_barrier(nif_ctx* c) {
   if (!c) return fail(NIF_ERR_INVALID, "null");
-  HIPCHK(hipSetDevice(c->dev));
+  NIF_ENTER(c, NIF_FLUSH_NONE)      // (the scratch word and the stream: a pending reduction stays pending)
   if (c->comm) NCCLCHK(ncclAllReduce(c->comm_scratch, c->comm_scratch, 1, ncclFloat32, ncclSum, comm_of(c), c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
@@ -218,7 +212,8 @@ extern "C" int nif_train_step_multi(nif_ctx** ctxs, int32_t n, const float* xin,
     nif_ctx* c = ctxs[i];
     const int ncol = c->pi + c->si;
     const int64_t b = lo[i + 1] - lo[i];
-    int r = nif_stage_batch(c, xin + lo[i] * ncol, y + lo[i] * c->so, sw ? sw + lo[i] : nullptr, b, &dx[i], &dy[i], &dsw[i]);
+    int r = nif_enter(c, NIF_FLUSH_NONE);      // (this thread's device, for the staging; the step behind it runs the tail)
+    if (r == NIF_OK) r = nif_stage_batch(c, xin + lo[i] * ncol, y + lo[i] * c->so, sw ? sw + lo[i] : nullptr, b, &dx[i], &dy[i], &dsw[i]);
     if (r == NIF_OK) r = nif_loss_grad_dev(c, dx[i], dy[i], sw ? dsw[i] : nullptr, b, B);
     rcs[i] = r;
     if (r != NIF_OK) msgs[i] = nif_last_error();

@@ -49,6 +49,17 @@ struct DevBuf {
 };
 
 struct NifF64;      // state of the double-precision L-BFGS closure (k_f64.hip), allocated at its first use
+// What a capture (nif_graph_begin .. nif_graph_end) recorded: a replay accounts for it, and a graph is replayed only under the optimizer
+// kind, amsgrad flag and weight-averaging setting it holds
+struct CapInfo {
+  int steps = 0;        // optimizer steps: a replay advances the iteration count by them
+  int kind = -1;        // kernel kind of those steps (-1: no update step) ...
+  bool ams = false;     // ... and whether they use the third slot
+  bool ema = false;     // recorded with the weight average (nif_set_option "ema")
+  int gt = 0;           // gradient-transform launches (0 none, 1 k_gt_reduce, 2 both)
+  long step0 = 0;       // the running capture only: the iteration count at nif_graph_begin (nothing runs until a replay)
+};
+struct CapGraph { hipGraphExec_t exec; CapInfo info; };      // exec null: destroyed (nif_graph_destroy), the id stays taken
 
 struct nif_ctx {
   nif_cfg cfg;
@@ -97,19 +108,16 @@ struct nif_ctx {
   DevBuf<float> zt_par, dzt_par;
   DevBuf<float> dat_par, ztl_par;   // last-layer class: dL/da', z' in latent-row layout   // Sobolev with parameter seeds: dz/dp, dL/d(dz/dp)
   float jac_l1 = 0.f; DevBuf<float> jac_mu, jac_tmp;   // latent Jacobian regulariser (k_pjac)
-  // captured training steps (nif_graph_*): hipGraph executables, the steps each one carries, the device-side optimizer state (and its
-  // pinned staging copy), and the optimizer kind / amsgrad flag each capture recorded (-1: no update step) -- a graph is replayed only
-  // with the kind it holds
-  std::vector<hipGraphExec_t> graphs; std::vector<int> graph_steps; bool capturing = false; int cap_steps = 0; long cap_step0 = 0;
+  // captured training steps (nif_graph_*): the finished graphs, the record of the running capture, and the device-side optimizer
+  // state a replay refreshes (with its pinned staging copy)
+  std::vector<CapGraph> graphs; bool capturing = false; CapInfo rec;
   DevBuf<OptDev> opt_dev; DevBuf<OptDev, true> opt_host;
   DevBuf<float> vhat;          // the third optimizer slot (amsgrad's vhat, centered RMSprop's a), allocated on first use
   bool slots_fresh = true;     // m, v are zero and the iteration count 0: Adagrad's first step writes its initial accumulator
-  int cap_kind = -1; bool cap_ams = false; std::vector<int> graph_kind; std::vector<char> graph_ams;
   // weight averaging behind every optimizer step (Keras' use_ema; nif_set_option "ema" / "ema_momentum_bits"): opt_ema 0 off, -1 on,
   // f >= 1 on and theta overwritten by the average every f steps.  ema is optimizer slot 3, allocated on first use and never freed
   // (captured graphs hold its address); ema_valid false: the next step (or replay) seeds it with theta (nif_set_opt_state resets it).
-  // cap_ema / graph_ema: whether the steps of a capture were recorded with the average (a graph is replayed only with that setting)
-  int opt_ema = 0; float ema_mom = 0.99f; DevBuf<float> ema; bool ema_valid = false; bool cap_ema = false; std::vector<char> graph_ema;
+  int opt_ema = 0; float ema_mom = 0.99f; DevBuf<float> ema; bool ema_valid = false;
   // magnitude pruning (nif_prune_*): the segment table (host copy: the k of the last update), its span [prune_lo, prune_hi), a byte mask
   // over the whole of theta (1 outside the segments), the thresholds and the select's histograms / per-segment state
   std::vector<PruneSeg> prune_segs; long prune_nblk = 0, prune_lo = 0, prune_hi = 0;
@@ -118,10 +126,8 @@ struct nif_ctx {
   // gradient transform (nif_set_grad_transform): the configured struct, whether any stage is on / a norm stage is on, the work-block
   // table, one partial sum of squares per block, the norms [tensors | global], and the struct's device copy; all built at the first
   // non-zero set.  gt_ran: 0 no transform has run, 1 the last one ran without a norm stage (norms not formed yet), 2 with.
-  // cap_gt / graph_gt: the launches a capture recorded (0 none, 1 k_gt_reduce, 2 both)
   nif_grad_transform gt = {}; bool gt_on = false, gt_norm = false; int gt_ran = 0;
   DevBuf<GtBlk> gt_blk; int gt_nblk = 0; DevBuf<float> gt_part, gt_norms; DevBuf<GtDev> gt_dev;
-  int cap_gt = 0; std::vector<char> graph_gt;
   bool ll_mlp_packed = false;        // last-layer class: the f32 planes of the 32-point MLP kernels are current
   int loss_kind = 0;                 // NIF_LOSS_* (nif_set_loss)
   DevBuf<float> sob2_acc;            // [grad | loss] summed over the passes of a second-order Sobolev step (nif_sobolev2_loss_grad_dev)
@@ -157,10 +163,14 @@ struct nif_ctx {
   bool metric_pending = false; float metric_pending_w = 0.f;   // a nif_metric_accumulate deferred into the next k_small launch
   bool last_step_small = false;
   // r6: the row reduction of a plain step may wait for its consumer -- the optimizer step then runs it fused with the update (one launch
-  // less per step); every other entry point of the library runs it first (tail_flush).  nif_set_option("fuse_tail") / NIF_FUSE_TAIL
+  // less per step); what else consumes it says so at the door (nif_enter).  nif_set_option("fuse_tail") / NIF_FUSE_TAIL
   bool tail_pending = false; int tail_rows = 0, tail_nloss = 0; bool opt_fuse_tail = true;
   bool opt_small_step = true;      // nif_set_option("small_step"): batches <= NIF_SMALL_MAX_B points of a net k_small takes run on it (one launch for loss + gradient); default from NIF_SMALL_STEP
   bool opt_fuse_gw = true;         // nif_set_option("fuse_gw"): ShapeNet weight gradients inside the training kernel (k_snet6) where it has the shape; default from NIF_FUSE_GW
+  // the invalidations, each the one statement of what it clears
+  void planes_stale() { packed = false; packed32 = false; packed_p32 = false; }      // theta (or what the planes are packed for) changed
+  void theta_stepped() { planes_stale(); reg_applied = false; }      // an optimizer step or replay: the regulariser term belongs to ONE gradient
+  void grad_rewritten() { reg_applied = false; }      // [grad | loss] holds a new step's sums (or zeros): the old gradient's term is gone
   nif_ctx() = default;
   nif_ctx(const nif_ctx&) = delete;
   ~nif_ctx();      // streams, events, graph executables, the communicator and the float64 state; then the buffers free themselves (nif_api.hip)
@@ -195,19 +205,18 @@ struct ProfScope {
   }
 };
 
+// The door of the C-ABI (DESIGN "Deferred state"): every extern "C" function that touches device state of a context passes it once,
+// behind its argument and state refusals -- the context's device selected, then the deferred pieces run that the entry point names:
+//   NIF_FLUSH_NONE    neither: it works on buffers of its own, consumes the tail itself (the optimizer steps) or ends / drops a capture
+//   NIF_FLUSH_TAIL    the row reduction: it reads or rewrites [grad | loss], the partial rows, theta or the stream's order
+//   NIF_FLUSH_METRIC  and the loss-metric accumulation: it rewrites grad[P] without a k_small launch, or reads the metric
+enum nif_flush { NIF_FLUSH_NONE, NIF_FLUSH_TAIL, NIF_FLUSH_METRIC };
+int nif_enter(nif_ctx* c, nif_flush what);
+#define NIF_ENTER(c_, what_) { const int rce_ = nif_enter(c_, what_); if (rce_) return rce_; }
+// The two pieces of work behind it (nif_api.hip).  Besides nif_enter only their consumers inside a guarded call run them: the optimizer
+// step that cannot fuse the tail, the tile path of a step and apply_reg (both rewrite grad[P]), and nif_metric_flush the tail
+int nif_tail_flush(nif_ctx* c);        // the deferred row reduction of the last plain step (nif_ctx::tail_pending)
+int nif_metric_flush(nif_ctx* c);      // a nif_metric_accumulate that waits for the next k_small launch (nif_ctx::metric_pending)
 // host batch -> this context's staging buffers (asynchronous H2D on c->st); used by the host-pointer entry points
 int nif_stage_batch(nif_ctx* c, const float* xin, const float* y, const float* sw, int64_t B, float** dx, float** dy, float** dsw);
-// the deferred row reduction of the last plain step (nif_ctx::tail_pending), run before anything but the optimizer step touches
-// [grad | loss], the partial rows or the weights (nif_api.hip)
-int nif_tail_flush(nif_ctx* c);
-// a nif_metric_accumulate that waits for the next k_small launch (nif_ctx::metric_pending), run before anything else rewrites grad[P]
-// or reads the metric (nif_api.hip); runs the deferred row reduction first
-int nif_metric_flush(nif_ctx* c);
-// the double-precision path behind include/nif_hip.h's nif_f64_* (k_f64.hip); nif_f64_release deletes its state (~nif_ctx)
-int nif_f64_set_params_impl(nif_ctx* c, const double* host, int64_t n);
-int nif_f64_get_params_impl(nif_ctx* c, double* host, int64_t n);
-int nif_f64_forward_dev_impl(nif_ctx* c, const double* xin, int64_t B, double* u);
-int nif_f64_loss_grad_dev_impl(nif_ctx* c, const double* xin, const double* y, const double* sw, int64_t B, int64_t Bg);
-int nif_f64_grad_read_impl(nif_ctx* c, double* loss, double* grad);
-void nif_f64_release(nif_ctx* c);
-#define TAIL_FLUSH(c_) { const int rct_ = nif_tail_flush(c_); if (rct_) return rct_; }
+void nif_f64_release(nif_ctx* c);      // deletes the state of the double-precision path (k_f64.hip; ~nif_ctx)
