@@ -46,6 +46,7 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? 2 : 1)) void k_jac(JacArgs J) {
   const SNetArgs& A = J.s;
   constexpr int NT = 256, WAVES = 4, NS = NIF_JAC_MAXSEED;
   constexpr int PLANE = NBL * NBL * 256;
+  static_assert(PLANE == plane_elems(PLANES_T16, PLANE_FWD, NBL), "k_pack_dev.h");
   constexpr int PF4 = (PLANE / 4 + NT - 1) / NT;
   constexpr bool PEXACT = (PLANE / 4) % NT == 0;
   constexpr int NP = 16 * NBL;

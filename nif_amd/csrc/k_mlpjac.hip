@@ -10,6 +10,7 @@
 //   SIREN res h+ = .5(h + sin(w0 tW2 + b2))  t' = cos(a1) w0 (h'W); h+' = .5(h' + cos(a2) w0 (t'W2))  (siren.py:381-410)
 //   bottleneck z = hWb + bb                  z' = h'Wb ;  last-layer class: a' = z' Wl
 #include "nif_internal.h"
+#include "k_pack_dev.h"
 
 struct MlpJacArgs {
   PNetArgs p;      // primal arguments (Z = primal output [tiles][r][32]; ZL as in k_pnet)
@@ -29,6 +30,7 @@ __global__ __launch_bounds__(256) void k_mlp_jac(MlpJacArgs J) {
   const long pt = tile * 32 + p;
   const long ptc = pt < A.B ? pt : A.B - 1;
   const long plane = (long)NB * NB * 256;
+  static_assert((long)NB * NB * 256 * 4 == plane_elems(PLANES_T32, PLANE_FWD, NB), "k_pack_dev.h");
   const float* prow = A.xin + ptc * A.ncol + A.col0;
 
   f32x16 h[NB], hd[NB], d[NB], T[NB];

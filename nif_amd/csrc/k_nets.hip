@@ -13,46 +13,10 @@
 //   ShapeNet       NIF._call_shape_net model.py:233-324, NIFMultiScale._call_shape_net_mres :738-954
 //   loss           Keras 'mse' (README.md:33); adjoint hand-derived (SURVEY a-10)
 #include "nif_internal.h"
+#include "k_pack_dev.h"
 #include "k_pnet_bf16.h"
 
 // (forcing a higher occupancy on the ParameterNet kernels with launch bounds was measured: 2-3x slower, spills)
-
-// ============================================================================================
-// weight packing: theta -> MFMA A-operand order
-//   fwd plane: block (ob,ib), quad vq, lane, c : M[in = 32ib + fmap(4vq+c, lane>>5)][out = 32ob + (lane&31)]
-//   bwd plane: block (ib,ob), quad vq, lane, c : M[in = 32ib + (lane&31)][out = 32ob + fmap(4vq+c, lane>>5)]
-// ============================================================================================
-__global__ void k_pack(const float* __restrict__ theta, MatRef m, int NBI, int NBO, float* __restrict__ WF,
-                       float* __restrict__ WB) {
-  const long per_plane = (long)NBI * NBO * 1024;
-  const long total = per_plane * (m.r + 1);
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(idx / per_plane);
-    long rem = idx - (long)k * per_plane;
-    const int c = rem & 3;
-    const int lane = (rem >> 2) & 63;
-    const int vq = (rem >> 8) & 3;
-    const int blk = (int)(rem >> 10);
-    const int v = 4 * vq + c;
-    {  // forward plane: blk = ob*NBI + ib
-      const int ob = blk / NBI, ib = blk % NBI;
-      const int in = 32 * ib + fmap(v, lane >> 5), out = 32 * ob + (lane & 31);
-      WF[idx] = (in < m.nin && out < m.nout) ? theta[matref_index(m, k, in, out)] : 0.f;
-    }
-    {  // backward plane: blk = ib*NBO + ob   (output blocks of U are the in-feature blocks)
-      const int ib = blk / NBO, ob = blk % NBO;
-      const int in = 32 * ib + (lane & 31), out = 32 * ob + fmap(v, lane >> 5);
-      WB[idx] = (in < m.nin && out < m.nout) ? theta[matref_index(m, k, in, out)] : 0.f;
-    }
-  }
-}
-
-void launch_pack(const float* theta, const MatRef& m, int NBI, int NBO, f32x4* WF, f32x4* WB, hipStream_t st) {
-  const long total = (long)NBI * NBO * 1024 * (m.r + 1);
-  int grid = (int)((total + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(k_pack, dim3(grid), dim3(256), 0, st, theta, m, NBI, NBO, (float*)WF, (float*)WB);
-}
 
 // ============================================================================================
 // ParameterNet
@@ -91,6 +55,7 @@ __global__ __launch_bounds__(256) void k_pnet(PNetArgs A) {
   const long ntiles = (A.B + 31) / 32;
   const int nm = A.lst * (A.res ? 2 : 1);
   const long plane = (long)NB * NB * 256;  // f32x4 per packed matrix
+  static_assert((long)NB * NB * 256 * 4 == plane_elems(PLANES_T32, PLANE_FWD, NB), "k_pack_dev.h");
   extern __shared__ __attribute__((aligned(16))) float pn_lds[];   // [LL kind: 4 waves x r x 32][small vectors]
   float* zl_lds = pn_lds;
   // r4: the bottleneck bias and the last-layer class's r x r map + bias live in LDS (tail of the small-vector region) -- the
@@ -222,6 +187,7 @@ __global__ __launch_bounds__(256) void k_pnet_bwd(PNetArgs A) {
   if (tile >= ntiles) return;
   const int nm = A.lst * (A.res ? 2 : 1);
   const long plane = (long)NB * NB * 256;
+  static_assert((long)NB * NB * 256 * 4 == plane_elems(PLANES_T32, PLANE_FWD, NB), "k_pack_dev.h");
 
   f32x16 gh[NB], d[NB], ga[NB], U[NB];
   // through the bottleneck: gh[f] = sum_c dz_c Wb[f][c]
@@ -343,6 +309,7 @@ __global__ __launch_bounds__(256, (NB <= 2 ? 2 : 1)) void k_snet(SNetArgs A) {
     const bool valid = pt < A.B;
     const long ptc = valid ? pt : A.B - 1;
     const long plane = (long)NB * NB * 256;
+    static_assert((long)NB * NB * 256 * 4 == plane_elems(PLANES_T32, PLANE_FWD, NB), "k_pack_dev.h");
     const int n = A.n, r = A.r;
     const float* xrow = A.xin + ptc * A.ncol + A.col0;
     const float* zt_base = A.Z + tile * r * 32 + p;  // zt_k = k<r ? zt_base[k*32] : 1

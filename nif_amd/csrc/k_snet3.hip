@@ -28,42 +28,13 @@
 #endif
 
 
-// ---- packing for the 16x16x4 path -------------------------------------------------------------
-//   fwd plane: ((ob*NBL + ib)*64 + lane)*4 + v : M[in = 16ib + 4(lane>>4) + v][out = 16ob + (lane&15)]
-//   bwd plane: ((ib*NBL + ob)*64 + lane)*4 + v : M[in = 16ib + (lane&15)][out = 16ob + 4(lane>>4) + v]
-__global__ void k_pack16(const float* __restrict__ theta, MatRef m, int NBL, float* __restrict__ WF,
-                         float* __restrict__ WB) {
-  const long per_plane = (long)NBL * NBL * 256;
-  const long total = per_plane * (m.r + 1);
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(idx / per_plane);
-    const long rem = idx - (long)k * per_plane;
-    const int v = rem & 3, lane = (rem >> 2) & 63, blk = (int)(rem >> 8);
-    {
-      const int ob = blk / NBL, ib = blk % NBL;
-      const int in = 16 * ib + 4 * (lane >> 4) + v, out = 16 * ob + (lane & 15);
-      WF[idx] = (in < m.nin && out < m.nout) ? theta[matref_index(m, k, in, out)] : 0.f;
-    }
-    {
-      const int ib = blk / NBL, ob = blk % NBL;
-      const int in = 16 * ib + (lane & 15), out = 16 * ob + 4 * (lane >> 4) + v;
-      WB[idx] = (in < m.nin && out < m.nout) ? theta[matref_index(m, k, in, out)] : 0.f;
-    }
-  }
-}
-void launch_pack16(const float* theta, const MatRef& m, int NBL, f32x4* WF, f32x4* WB, hipStream_t st) {
-  const long total = (long)NBL * NBL * 256 * (m.r + 1);
-  int grid = (int)((total + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(k_pack16, dim3(grid), dim3(256), 0, st, theta, m, NBL, (float*)WF, (float*)WB);
-}
-
 // MODE: 0 = plain (NIFMultiScale without resblock), 1 = SIREN resblock, 2 = NIF skip connection
 template <int NBL, int WAVES, bool TRAIN, int ACT, int MODE>
 __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL == 4 ? NIF_S3_OCC4 : 1)))) void k_snet3(SNetArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NT = WAVES * 64;
   constexpr int PLANE = NBL * NBL * 256;                  // floats per weight plane
+  static_assert(PLANE == plane_elems(PLANES_T16, PLANE_FWD, NBL), "k_pack_dev.h");
   constexpr int PF4 = (PLANE / 4 + NT - 1) / NT;          // f32x4 per thread per plane
   constexpr bool PEXACT = (PLANE / 4) % NT == 0;
   const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -387,12 +358,8 @@ __global__ __launch_bounds__(WAVES * 64, (NBL <= 2 ? 4 : (NBL == 3 ? 3 : (NBL ==
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-static int nbl_of(int n) {
-  const int c = (n + 15) / 16;   // pad to a supported block count
-  return c <= 4 ? c : (c <= 6 ? 6 : 8);
-}
-int snet3_nbl(int n) { return nbl_of(n); }
-int snet3_nsm(int si, int so, int nh, int n) { return (si + so + 1 + nh) * 16 * nbl_of(n) + ((so + 3) & ~3); }
+int snet3_nbl(int n) { return plane_nbl(n); }
+int snet3_nsm(int si, int so, int nh, int n) { return (si + so + 1 + nh) * 16 * plane_nbl(n) + ((so + 3) & ~3); }
 static int waves_of(int NBL) { (void)NBL; return 4; }
 
 static size_t snet3_shmem(const SNetArgs& a, int NBL, int waves) {
@@ -401,18 +368,17 @@ static size_t snet3_shmem(const SNetArgs& a, int NBL, int waves) {
   return (2 * plane + sm_tot + (size_t)waves * (2 * a.r * 64 + a.r * 16) + 8) * sizeof(float);
 }
 bool snet3_supported(const SNetArgs& a) {
-  const int NBL = nbl_of(a.n);
+  const int NBL = plane_nbl(a.n);
   if (a.n > 128) return false;
   // (narrow nets: up to 52 KB keeps three workgroups per CU; beyond that the kernel still runs, at lower occupancy -- far better
   // than the 32-point fallback kernel, and JacobianLayer / HessianLayer / Sobolev exist only on this path)
   return snet3_shmem(a, NBL, waves_of(NBL)) <= 160u * 1024u;
 }
-long snet3_plane_floats(int n) { const int NBL = nbl_of(n); return (long)NBL * NBL * 256; }
-long snet3_ring_floats_per_wave(int n, int nh) { return (long)(nh + 1) * nbl_of(n) * 256; }
+long snet3_ring_floats_per_wave(int n, int nh) { return (long)(nh + 1) * plane_nbl(n) * 256; }
 
 // returns #workgroups (x WAVES = ring owners); query_only: no launch
 int launch_snet3(const SNetArgs& a, bool train, bool query_only, int* waves_out, hipStream_t st) {
-  const int NBL = nbl_of(a.n);
+  const int NBL = plane_nbl(a.n);
   const int waves = waves_of(NBL);
   if (waves_out) *waves_out = waves;
   const long nt16 = 2 * ((a.B + 31) / 32);

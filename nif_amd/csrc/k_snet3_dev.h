@@ -1,6 +1,7 @@
 // k_snet3_dev.h -- device helpers shared by the 16-point-tile kernels (k_snet3.hip, k_jac.hip)
 #pragma once
 #include "nif_internal.h"
+#include "k_pack_dev.h"
 
 __device__ __forceinline__ float hyp3(const SNetArgs& A, int k, long slot) {
   return k < A.r ? A.theta[A.off_Wh + (long)k * A.po + slot] : A.theta[A.off_bh + slot];

@@ -69,6 +69,7 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && T
   constexpr int NCH = NBL / 2;                      // K-step chunks per plane
   constexpr int SPL = (NBL == 8 && LL) ? NIF_S4_SPLIT8 : (NBL == 4 ? NIF_S4_SPLIT4 : 1), NBS = NBL / SPL;   // chunk pieces per K-step, output (input) blocks per piece
   constexpr int CF = NBS * 3 * 64, CB = NBS * 2 * 64;   // 16-byte units per forward / adjoint chunk
+  static_assert(CF * SPL == plane_chunk_units(PLANES_SPLIT, PLANE_FWD, NBL) && CB * SPL == plane_chunk_units(PLANES_SPLIT, PLANE_BWD, NBL), "k_pack_dev.h");
   // the policies' compact plane set (late r4): ONE 16-bit plane per block -- a third / half of the chunk DMA (LDS buffers keep the
   // stride CF: the phi layer's chunks of the last-layer class stay split groups)
   constexpr bool CP = PR == 1 || PR == 2;
@@ -84,6 +85,8 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && T
   constexpr bool PHC = TRAIN && SGN && MODE == 0 && PR == 1 && NBL == 8;
   const bool ph16 = PHC && A.h_ph16 != 0; (void)ph16;
   constexpr int CFH = CP ? NBS * 64 : (X16 ? CB : CF), CBH = CP ? NBS * 64 : CB;   // units per HIDDEN-matrix chunk
+  constexpr PlaneSet HSET = CP ? PLANES_COMPACT : (X16 ? PLANES_HALF : PLANES_SPLIT);
+  static_assert(CFH * SPL == plane_chunk_units(HSET, PLANE_FWD, NBL) && CBH * SPL == plane_chunk_units(HSET, PLANE_BWD, NBL), "k_pack_dev.h");
   constexpr int QF = (CF + NT - 1) / NT;
   // LDS ring of the chunk stream: NBUF buffers, the DMA runs DIST = NBUF - 1 chunk steps ahead of the MFMAs.  r2 had two buffers
   // and drained vmcnt(0) in front of every barrier: the L2 -> LDS latency of a chunk (~1.5-2 k cycles) had to hide behind ONE
@@ -128,6 +131,7 @@ __global__ __launch_bounds__(256, (NBL <= 4 ? NIF_S4_OCC : ((NBL == 8 && LL && T
   // cs_next() issues the DMA of the next chunk of the stream into LDS buffer `buf` and steps the state; behind the last
   // phase the stream wraps to the next tile group's phase 0, or ends (cs_left < 0) when this workgroup has no further group.
   constexpr int PHF = 2 * 3 * 64;                       // units of a phi-layer forward chunk (LL)
+  static_assert(PHF == plane_chunk_units(PLANES_PHI, PLANE_FWD, NBL), "k_pack_dev.h");
   const int NPC = (r + 1) * NCH * SPL;                  // chunks of one hidden matrix
   const bf16x8* cs_src = reinterpret_cast<const bf16x8*>(A.WF4);
   int cs_units = CFH, cs_left = nh * NPC, cs_phase = 0;

@@ -88,6 +88,8 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   constexpr int CF = X16 ? NBL * 2 * 64 : NBL * 3 * 64, CB = NBL * 2 * 64;   // 16-byte units per forward / adjoint chunk
   constexpr bool CP = PR != 0;                           // the policies' compact plane set (k_snet4_dev.h): one plane per block
   constexpr int CFH = CP ? NBL * 64 : CF, CBH = CP ? NBL * 64 : CB;
+  constexpr PlaneSet HSET = CP ? PLANES_COMPACT : PLANES_HALF;
+  static_assert(CFH == plane_chunk_units(HSET, PLANE_FWD, NBL) && CBH == plane_chunk_units(HSET, PLANE_BWD, NBL), "k_pack_dev.h");
   // BIG (r6, the exact-product form): chunks of 16 KB = a whole plane of a hidden matrix (both K steps), TWO chunk steps per layer and
   // direction instead of four: half the per-step fixed costs (DMA issue 170-380 ticks, s_waitcnt 140, barrier >= 140, loop glue 120 of a
   // ~1 250-tick forward step: r6 timeline).  It brings a barrier behind every hidden deposit with it: the consumers' only other window

@@ -141,6 +141,10 @@ __global__ __launch_bounds__(256, ((NBL <= 2 && NSD <= 2) || (NBL <= 4 && NSD ==
   constexpr int NCH = NBL / 2, CF = NBL * 3 * 64, CB = NBL * 2 * 64;       // bf16 planes: K-step chunks, 16-B units
   constexpr int PLANE = BF ? NCH * CF * 4 : NBL * NBL * 256;              // floats per LDS plane buffer
   constexpr int UF = BF ? NCH * CF : PLANE / 4, UB = BF ? NCH * CB : PLANE / 4;   // 16-B units of a forward / adjoint plane
+  constexpr PlaneSet PSET = BF ? PLANES_SPLIT : PLANES_T16;
+  static_assert(CF == plane_chunk_units(PLANES_SPLIT, PLANE_FWD, NBL) && CB == plane_chunk_units(PLANES_SPLIT, PLANE_BWD, NBL), "k_pack_dev.h");
+  static_assert(UF * PLANE_UNIT_BYTES == plane_elems(PSET, PLANE_FWD, NBL) * plane_elem_bytes(PSET) &&
+                UB * PLANE_UNIT_BYTES == plane_elems(PSET, PLANE_BWD, NBL) * plane_elem_bytes(PSET), "k_pack_dev.h");
   constexpr int PF4 = (UF + NT - 1) / NT;
   constexpr int NP = 16 * NBL;
   const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -77,6 +77,9 @@ __global__ __launch_bounds__(64 * NIF_SOBW_WMAX(NBL), (NBL <= 4 ? NIF_SOBW_OCC :
   constexpr int CF = NBL * 3 * 64, CB = NBL * 2 * 64;
   constexpr bool CP = PR;                                // the policy's compact plane set (k_snet4_dev.h): one bf16 plane per block
   constexpr int CFH = CP ? NBL * 64 : CF, CBH = CP ? NBL * 64 : CB;
+  constexpr PlaneSet HSET = CP ? PLANES_COMPACT : PLANES_SPLIT;
+  static_assert(CF == plane_chunk_units(PLANES_SPLIT, PLANE_FWD, NBL) && CB == plane_chunk_units(PLANES_SPLIT, PLANE_BWD, NBL), "k_pack_dev.h");
+  static_assert(CFH == plane_chunk_units(HSET, PLANE_FWD, NBL) && CBH == plane_chunk_units(HSET, PLANE_BWD, NBL), "k_pack_dev.h");
   constexpr int QF = (CF + NT - 1) / NT;
   constexpr int NBUF = 2;
   const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -2,6 +2,7 @@
 // orchestration.  gfx950 only; there is no CPU fallback.
 #include "../../include/nif_hip.h"
 #include "nif_internal.h"
+#include "k_pack_dev.h"
 #include <cstdlib>
 
 #include <cmath>
@@ -100,6 +101,8 @@ static int build_layout(nif_ctx* c) {
   return 0;
 }
 
+// f32x4 of one fp32 plane of `nblk` blocks per side
+static long plane_f32x4(PlaneSet s, int nblk) { return plane_elems(s, PLANE_FWD, nblk) / 4; }
 // the stream and every buffer whose size the configuration fixes
 static int create_buffers(nif_ctx* c) {
   const int nh = c->nh, nm = c->nm;
@@ -109,37 +112,33 @@ static int create_buffers(nif_ctx* c) {
   for (DevBuf<float>* b : {&c->theta, &c->grad, &c->m, &c->v}) { const int rc = b->alloc(pn); if (rc) return rc; }
   for (float* b : {c->m.p, c->v.p, c->grad.p}) HIPCHK(hipMemset(b, 0, sizeof(float) * (size_t)pn));
   int rc = NIF_OK;
-  const long pk_p = (long)(nm > 0 ? nm : 1) * c->NSTB * c->NSTB * 256;      // in f32x4
-  long pk_s = (long)(nh > 0 ? nh : 1) * (c->r + 1) * c->NB * c->NB * 256;
-  {
-    const long pk16 = (long)(nh > 0 ? nh : 1) * (c->r + 1) * snet3_plane_floats(c->n) / 4;
-    if (pk16 > pk_s) pk_s = pk16;
-  }
+  const long pk_p = (long)(nm > 0 ? nm : 1) * plane_f32x4(PLANES_T32, c->NSTB);
+  const long p32 = plane_f32x4(PLANES_T32, c->NB), p16 = plane_f32x4(PLANES_T16, snet3_nbl(c->n));     // one buffer serves either tile size
+  const long pk_s = (long)(nh > 0 ? nh : 1) * (c->r + 1) * (p16 > p32 ? p16 : p32);
   if (!rc) rc = c->pWF.alloc(pk_p);
   if (!rc) rc = c->pWB.alloc(pk_p);
   if (!rc) rc = c->sWF.alloc(pk_s);
   if (!rc) rc = c->sWB.alloc(pk_s);
   if (nh > 0 && !(snet3_nbl(c->n) & 1) && c->n <= 128) {
     const int rr = c->kind == NIF_KIND_LASTLAYER ? 0 : c->r;   // last-layer class: shared dense weights, one plane
-    if (!rc) rc = c->sWF4.alloc((long)nh * snet4_fwd_elems(c->n, rr) * 2);
-    if (!rc) rc = c->sWB4.alloc((long)nh * snet4_bwd_elems(c->n, rr) * 2);
+    auto set = [&](DevBuf<char>& f, DevBuf<char>& b, PlaneSet s, int nmat) {       // both images of `nmat` matrices in set s
+      if (!rc) rc = f.alloc(nmat * plane_mat_bytes(s, PLANE_FWD, c->n, rr));
+      if (!rc) rc = b.alloc(nmat * plane_mat_bytes(s, PLANE_BWD, c->n, rr));
+    };
+    set(c->sWF4, c->sWB4, PLANES_SPLIT, nh);
     if (c->kind != NIF_KIND_NIF) {   // SIREN nets (r5): the exact-product half planes of k_snet4<.., PR = 3> / k_snet6 (class NIF keeps the bf16 splits)
-      if (!rc) rc = c->sWF4x.alloc((long)nh * snet4_bwd_elems(c->n, rr) * 2);
-      if (!rc) rc = c->sWB4x.alloc((long)nh * snet4_bwd_elems(c->n, rr) * 2);
+      set(c->sWF4x, c->sWB4x, PLANES_HALF, nh);
       if (!rc) rc = c->sWscale.alloc((long)nh * (rr + 1) * 2);
     }
-    if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32) {     // the policy's compact plane set (k_snet4 / k_snet6<.., PR>), next to the exact splits
-      if (!rc) rc = c->sWF4h.alloc((long)nh * (snet4_fwd_elems(c->n, rr) / 3) * 2);
-      if (!rc) rc = c->sWB4h.alloc((long)nh * (snet4_bwd_elems(c->n, rr) / 2) * 2);
-    }
-    if (c->kind == NIF_KIND_LASTLAYER && !rc) rc = c->ll_wpf.alloc((long)snet4_phi_fwd_elems(c->n) * 2);
-    if (c->kind == NIF_KIND_LASTLAYER && !rc) rc = c->ll_wpb.alloc((long)snet4_phi_bwd_elems(c->n) * 2);
+    // the policy's compact plane set (k_snet4 / k_snet6<.., PR>), next to the exact splits
+    if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32) set(c->sWF4h, c->sWB4h, PLANES_COMPACT, nh);
+    if (c->kind == NIF_KIND_LASTLAYER) set(c->ll_wpf, c->ll_wpb, PLANES_PHI, 1);
   }
   // slot-ordered copy of the dense ShapeNet parameters of the last-layer class (k_snet4<LL>, k_sob<LL>, k_jac on the r = 0 arguments)
   if (c->kind == NIF_KIND_LASTLAYER && nh > 0 && c->n <= 128 && !rc)
     rc = c->ll_slots.alloc((long)c->si * c->n + (long)nh * c->n * c->n + (long)c->n * c->so * c->r +
                            c->n + (long)nh * c->n + c->so * c->r + c->so + c->r * c->r + 64);
-  const long pk_l = (long)(nh > 0 ? nh : 1) * c->NB * c->NB * 256;
+  const long pk_l = (long)(nh > 0 ? nh : 1) * plane_f32x4(PLANES_T32, c->NB);
   if (!rc && c->kind == NIF_KIND_LASTLAYER) rc = c->lWF.alloc(pk_l);
   if (!rc && c->kind == NIF_KIND_LASTLAYER) rc = c->lWB.alloc(pk_l);
   return rc;
@@ -476,7 +475,7 @@ static void fill_pnet(const nif_ctx* c, PNetArgs& a, const float* xin, long B) {
 // reads them, and packing them after every Adam step cost L launches per step
 static void ensure_ll_mlp_planes(nif_ctx* c) {
   if (c->ll_mlp_packed) return;
-  const long plane_l = (long)c->NB * c->NB * 256;
+  const long plane_l = plane_f32x4(PLANES_T32, c->NB);
   for (int j = 0; j < c->nh; ++j) {
     long w_off, b_off; snet_mat(c, j, &w_off, &b_off);
     launch_pack(c->theta, dense_ref(w_off, c->n, c->n), c->NB, c->NB, c->lWF + j * plane_l, c->lWB + j * plane_l, c->st);
@@ -544,7 +543,7 @@ static int ensure_packed32(nif_ctx* c) {
   if (c->packed32 || c->kind == NIF_KIND_LASTLAYER) return NIF_OK;
   ProfScope ps_(c, NIF_PROF_PACK);
   const bool fmt16 = c->use_snet3 || c->jac_ok;     // 16-point-tile plane format (k_snet3, k_jac, k_sob) / 32-point (k_snet)
-  const long plane_s = fmt16 ? snet3_plane_floats(c->n) / 4 : (long)c->NB * c->NB * 256;
+  const long plane_s = fmt16 ? plane_f32x4(PLANES_T16, snet3_nbl(c->n)) : plane_f32x4(PLANES_T32, c->NB);
   for (int j = 0; j < c->nh; ++j) {
     f32x4* wf = c->sWF + (long)j * (c->r + 1) * plane_s;
     f32x4* wb = c->sWB + (long)j * (c->r + 1) * plane_s;
@@ -561,7 +560,7 @@ static int ensure_packed32(nif_ctx* c) {
 static int ensure_packed_p32(nif_ctx* c) {
   if (c->packed_p32) return NIF_OK;
   ProfScope ps_(c, NIF_PROF_PACK);
-  const long plane_p = (long)c->NSTB * c->NSTB * 256;
+  const long plane_p = plane_f32x4(PLANES_T32, c->NSTB);
   for (int j = 0; j < c->nm; ++j) {
     long w_off, b_off; pnet_mat(c, j, &w_off, &b_off);
     launch_pack(c->theta, dense_ref(w_off, c->nst, c->nst), c->NSTB, c->NSTB, c->pWF + j * plane_p, c->pWB + j * plane_p, c->st);
@@ -569,6 +568,16 @@ static int ensure_packed_p32(nif_ctx* c) {
   HIPCHK(hipGetLastError());
   c->packed_p32 = true;
   return NIF_OK;
+}
+// the 16-bit plane sets of `nmat` hidden matrices from matrix j0 on (mstride slots apart, the first one m0), into the context's images:
+// the split groups, on SIREN nets the half pairs and their scales with them, and the policy's compact set
+static void pack_hidden_planes(nif_ctx* c, const MatRef& m0, long mstride, int nmat, int j0, float scale) {
+  PackJob job{c->theta, m0, mstride, nmat, snet3_nbl(c->n), scale};
+  job.mat0 = j0;
+  job.split = {c->sWF4, c->sWB4};
+  if (c->sWF4x) { job.half = {c->sWF4x, c->sWB4x}; job.pscale = c->sWscale + (size_t)j0 * (m0.r + 1) * 2; }
+  if (c->sWF4h) { job.compact = {c->sWF4h, c->sWB4h}; job.compact_half = policy_prec(c) == 2; }
+  launch_pack_planes(job, c->st);
 }
 static int ensure_packed(nif_ctx* c) {
   if (!c->have_params) return fail(NIF_ERR_STATE, "parameters not set (call nif_set_params first)");
@@ -595,19 +604,7 @@ static int ensure_packed(nif_ctx* c) {
       for (int j = 0; j < nh; ++j) {
         long w_off, b_off; snet_mat(c, j, &w_off, &b_off);
         seg(b_off, s_bh + (long)j * n, n);
-        if (c->use_ll4 && c->sWF4x)       // (r5: split groups + half planes + their scales in one launch)
-          launch_pack16b_dual(c->theta, dense_ref(w_off, n, n), 0, 1, snet3_nbl(n),
-                              (char*)c->sWF4 + (size_t)j * snet4_fwd_elems(n, 0) * 2, (char*)c->sWB4 + (size_t)j * snet4_bwd_elems(n, 0) * 2, 0, 0,
-                              (char*)c->sWF4x + (size_t)j * snet4_bwd_elems(n, 0) * 2, (char*)c->sWB4x + (size_t)j * snet4_bwd_elems(n, 0) * 2,
-                              0, 0, c->cfg.s_omega0, c->sWscale + (size_t)j * 2, c->st);
-        else if (c->use_ll4)
-          launch_pack16b(c->theta, dense_ref(w_off, n, n), snet3_nbl(n),
-                         (char*)c->sWF4 + (size_t)j * snet4_fwd_elems(n, 0) * 2, (char*)c->sWB4 + (size_t)j * snet4_bwd_elems(n, 0) * 2,
-                         c->cfg.s_omega0, c->st);
-        if (c->use_ll4 && c->sWF4h)
-          launch_pack16b(c->theta, dense_ref(w_off, n, n), snet3_nbl(n),
-                         (char*)c->sWF4h + (size_t)j * (snet4_fwd_elems(n, 0) / 3) * 2, (char*)c->sWB4h + (size_t)j * (snet4_bwd_elems(n, 0) / 2) * 2,
-                         c->cfg.s_omega0, c->st, policy_prec(c));
+        if (c->use_ll4) pack_hidden_planes(c, dense_ref(w_off, n, n), 0, 1, j, c->cfg.s_omega0);
       }
       seg(c->s_bott_b, s_bl, sop);
       seg(c->ll_bias, s_bl + sop, c->so);
@@ -628,17 +625,8 @@ static int ensure_packed(nif_ctx* c) {
   // 128 units with latent_dim >= 3 and many matrices -- which k_snet3 / k_jac / k_sob at that width cannot)
   c->use_snet4 = c->sWF4 && !fp32_only && snet4_supported(probe);
   c->packed32 = false;
-  if (c->use_snet4 && c->nh > 0 && c->sWF4x)   // all hidden hyper-matrices (n^2 slots apart): split groups, half planes and their scales in ONE launch (r5)
-    launch_pack16b_dual(c->theta, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, snet3_nbl(c->n),
-                        c->sWF4, c->sWB4, snet4_fwd_elems(c->n, c->r), snet4_bwd_elems(c->n, c->r),
-                        c->sWF4x, c->sWB4x, snet4_bwd_elems(c->n, c->r), snet4_bwd_elems(c->n, c->r), probe.omega, c->sWscale, c->st);
-  else if (c->use_snet4 && c->nh > 0)
-    launch_pack16b_batch(c->theta, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, snet3_nbl(c->n),
-                         c->sWF4, c->sWB4, snet4_fwd_elems(c->n, c->r), snet4_bwd_elems(c->n, c->r), probe.omega, c->st);
-  if (c->use_snet4 && c->nh > 0 && c->sWF4h)
-    launch_pack16b_batch(c->theta, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, snet3_nbl(c->n),
-                         c->sWF4h, c->sWB4h, snet4_fwd_elems(c->n, c->r) / 3, snet4_bwd_elems(c->n, c->r) / 2, probe.omega, c->st,
-                         policy_prec(c));
+  // all hidden hyper-matrices (n^2 slots apart) in one batch: on SIREN nets ONE launch for split groups, half planes and scales (r5)
+  if (c->use_snet4 && c->nh > 0) pack_hidden_planes(c, hyper_w(c, 1), hyper_wslot(c, 2) - hyper_wslot(c, 1), c->nh, 0, probe.omega);
   HIPCHK(hipGetLastError());
   c->packed = true;
   if (!c->use_snet4) return ensure_packed32(c);
@@ -726,31 +714,33 @@ static int snap_check(nif_ctx* c, const void* rows, int64_t T, const void* x, co
 // buf: what is left of c->snap (sized by snap_combined_floats for the same tc).
 #define NIF_SNAP_IMAGE_BYTES (256L << 20)
 static long snap_r4(long f) { return (f + 3) & ~3L; }
-static void snap_combined_sizes(const nif_ctx* c, long* fe, long* be, long* per_bytes) {
-  const bool siren = c->kind != NIF_KIND_NIF;
-  *be = snet4_bwd_elems(c->n, 0);
-  *fe = siren ? *be : snet4_fwd_elems(c->n, 0);       // (the half planes: both directions in the adjoint geometry)
-  *per_bytes = 4 * c->po + (long)c->nh * ((*fe + *be) * 2 + 8);
+// bytes of one combined hidden matrix's forward / adjoint image (SIREN nets: the half pairs, class NIF: the split groups), and of
+// one snapshot: [slot vector | per hidden matrix: both images + its scale pair]
+static void snap_combined_sizes(const nif_ctx* c, long* fb, long* bb, long* per_bytes) {
+  const PlaneSet set = c->kind != NIF_KIND_NIF ? PLANES_HALF : PLANES_SPLIT;
+  *fb = plane_mat_bytes(set, PLANE_FWD, c->n, 0);
+  *bb = plane_mat_bytes(set, PLANE_BWD, c->n, 0);
+  *per_bytes = sizeof(float) * c->po + (long)c->nh * (*fb + *bb + 2 * sizeof(float));
 }
 static long snap_chunk(const nif_ctx* c, long T) {
-  long fe, be, per; snap_combined_sizes(c, &fe, &be, &per);
+  long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per);
   long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
   if (tc > 65535) tc = 65535;
   if (tc > T) tc = T;
   return tc < 1 ? 1 : tc;
 }
 static long snap_combined_floats(const nif_ctx* c, long tc) {
-  long fe, be, per; snap_combined_sizes(c, &fe, &be, &per);
-  return snap_r4(tc * c->po) + snap_r4(2L * c->nh * tc) + tc * c->nh * (fe + be) / 2 + 4;
+  long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per);
+  return snap_r4(tc * c->po) + snap_r4(2L * c->nh * tc) + tc * c->nh * (fb + bb) / (long)sizeof(float) + 4;
 }
 static int snap_combined(nif_ctx* c, float* buf, long tc_max, const float* lat, long T, const float* x, const long* off_dev,
                          const int64_t* off_host, long M, float* u) {
   const bool siren = c->kind != NIF_KIND_NIF;
-  long fe, be, per; snap_combined_sizes(c, &fe, &be, &per);
+  long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per);
   float* w = buf;
   float* ws = w + snap_r4(tc_max * c->po);
   char* WF = reinterpret_cast<char*>(ws + snap_r4(2L * c->nh * tc_max));
-  char* WB = WF + (size_t)tc_max * c->nh * fe * 2;
+  char* WB = WF + (size_t)tc_max * c->nh * fb;
   const int NBL = snet3_nbl(c->n);
   for (long t0 = 0; t0 < T; t0 += tc_max) {
     const long tc = T - t0 < tc_max ? T - t0 : tc_max;
@@ -764,13 +754,17 @@ static int snap_combined(nif_ctx* c, float* buf, long tc_max, const float* lat, 
     {
       ProfScope p_(c, NIF_PROF_PACK);
       launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
-      for (int j = 0; j < c->nh; ++j)
-        launch_pack16b_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + (size_t)j * fe * 2, WB + (size_t)j * be * 2,
-                             c->nh * fe, c->nh * be, sa.omega, c->st, siren ? 3 : 0, ws + (long)j * tc * 2);
+      for (int j = 0; j < c->nh; ++j) {       // matrix j of every snapshot of the chunk: images [snapshot][matrix], scales [matrix][snapshot]
+        PackJob job{w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, sa.omega};
+        job.mat0 = j; job.dstep = c->nh;
+        (siren ? job.half : job.split) = {WF, WB};
+        job.pscale = ws + (long)j * tc * 2;
+        launch_pack_planes(job, c->st);
+      }
     }
     sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr;
     sa.WF4 = WF; sa.wscale = siren ? ws : nullptr;
-    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * fe / 8; sa.snap_T = (int)tc;
+    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * fb / PLANE_UNIT_BYTES; sa.snap_T = (int)tc;
     sa.u_out = off_dev ? u : u + t0 * M * c->so;
     ProfScope p_(c, NIF_PROF_SNET_FWD);
     if (launch_snet4_snap(sa, tc, mmax, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no snapshot form of k_snet4 for this net");
@@ -1255,7 +1249,7 @@ static int fill_snet_ll_sob(nif_ctx* c, SNetArgs& sa, const float* xin, long B, 
   const int NBL = snet3_nbl(c->n);
   if (!c->use_ll4) { sa.WF4 = nullptr; sa.WB4 = nullptr; f32_planes = true; }   // (bf16-split planes are packed for k_snet4<LL> only)
   if (NBL > 6 || f32_planes) {     // (k_jac / the Hessian take the f32-input planes at every width)
-    const long plane_s = snet3_plane_floats(c->n) / 4;
+    const long plane_s = plane_f32x4(PLANES_T16, NBL);
     if (!c->ll_packed32) {
       for (int j = 0; j < c->nh; ++j) {
         long w_off, b_off; snet_mat(c, j, &w_off, &b_off);

@@ -110,10 +110,10 @@ struct SNetArgs {
   float* dring;                           // k_snet3: per-wave ring for act'(a) (register-dump order)
   int nsm;                                // k_snet3: floats per k of the LDS copy of the small hyper-vectors
   long long* tl;                          // -DNIF_TIMELINE builds: s_memtime stamps of wave 0 of block 0
-  const void* WF4; const void* WB4;       // k_snet4: bf16-split planes (k_pack16b), per plane NCH chunks
+  const void* WF4; const void* WB4;       // k_snet4: bf16-split planes (k_pack_dev.h), per plane NCH chunks
   const void* WF4h; const void* WB4h;     // the policies' compact plane set (prec != 0): one bf16 / half plane per block (k_pack16b mode 1 / 2)
   const void* WF4x; const void* WB4x;     // k_snet6 (r5): the exact-product HALF planes (hi, lo), k_pack16b mode 3, both in the adjoint geometry
-  const float* wscale;                    //   their powers of two [matrix][plane][s | 1 / s] (k_plane_scales)
+  const float* wscale;                    //   their powers of two [matrix][plane][s | 1 / s] (plane_scale_shift, k_pack_dev.h)
   // last-layer-parameterised class on k_snet4 (r = 0: shared dense SIREN; theta = the slot-ordered copy built by
   // launch_ll_slots; so = so_u * rl outputs phi): u = Dot(phi, a) + bias, a = Z [tiles][rl][32]
   int ll, rl, so_u;
@@ -140,11 +140,6 @@ int launch_snet4_snap(const SNetArgs& a, long T, long Mmax, hipStream_t st);
 struct LLSlotSeg { long src, dst, len; };
 struct LLSlotMap { int nseg; LLSlotSeg seg[48]; };
 void launch_ll_slots(const float* theta, const LLSlotMap& m, float* slots, hipStream_t st);
-// phi layer (dense [n][sop], sop <= 32) as bf16-split MFMA operands: NBL/2 forward K-step chunks of 2*3*64 16-byte units
-// and one adjoint chunk of NBL*2*64 units
-long snet4_phi_fwd_elems(int n);
-long snet4_phi_bwd_elems(int n);
-void launch_pack_phi(const float* theta, long w_off, int n, int sop, void* WPF, void* WPB, hipStream_t st);
 // slot offsets inside pnet_output (nif/model.py:253-300): computed on the fly
 __host__ __device__ inline long slot_w1(const SNetArgs& a) { return 0; }
 __host__ __device__ inline long slot_wh(const SNetArgs& a, int j) { return (long)a.si * a.n + (long)j * a.n * a.n; }
@@ -186,7 +181,6 @@ bool gw_da_bf16_ok(int NBI, int NBO, int r);
 bool sobw_supported(const SNetArgs& a, int ns, bool any_par);      // k_sobw.hip takes this Sobolev training step
 
 // launchers (implemented in the .hip files); all enqueue on `st`
-void launch_pack(const float* theta, const MatRef& m, int NBI, int NBO, f32x4* WF, f32x4* WB, hipStream_t st);
 void launch_pnet(const PNetArgs& a, int NSTB, bool train, hipStream_t st);
 void launch_pnet_bwd(const PNetArgs& a, int NSTB, hipStream_t st);
 void launch_snet(const SNetArgs& a, int NB, bool train, hipStream_t st);
@@ -200,17 +194,8 @@ void launch_pnet_bwg(const PNetArgs& a, float* partial, long pstride, int rows, 
                      long touch_floats = 0);
 // bf16-split variant of k_snet3 (k_snet4.hip): fp32-exact 6-product forward, 3-product adjoint on the bf16 MFMA
 bool snet4_supported(const SNetArgs& a);
-long snet4_fwd_elems(int n, int r);
-long snet4_bwd_elems(int n, int r);
-// (scale = omega_0 of the layer: the bf16-split planes hold omega_0 M, see k_snet4.hip)
-void launch_pack16b(const float* theta, const MatRef& m, int NBL, void* WF, void* WB, float scale, hipStream_t st, int mode = 0);
-void launch_pack16b_dual(const float* theta, const MatRef& m0, long mstride, int nmat, int NBL, void* WF, void* WB, long fstride_elems,
-                         long bstride_elems, void* WFx, void* WBx, long fxstride_elems, long bxstride_elems, float scale, float* pscale,
-                         hipStream_t st);     // mode 0 + mode 3 (scales found in the kernel) in one launch (k_snet4.hip)
 void launch_snet4_f16(const SNetArgs& a, bool train, int nblk, size_t shm, hipStream_t st);     // k_snet4_f16.hip
 void launch_snet4_x16(const SNetArgs& a, bool train, int nblk, size_t shm, hipStream_t st);     // k_snet4_x16.hip (r5: half-pair exact products)
-void launch_pack16b_batch(const float* theta, const MatRef& m0, long mstride, int nmat, int NBL, void* WF, void* WB,
-                          long fstride_elems, long bstride_elems, float scale, hipStream_t st, int mode = 0, float* pscale = nullptr);
 int launch_snet4(const SNetArgs& a, bool train, bool query_only, hipStream_t st);
 // k_small.hip (r6): loss + every gradient of a small batch in one launch (one partial row per 16 points)
 #define NIF_SMALL_MAX_B 2048
@@ -251,7 +236,6 @@ int launch_sob(const SNetArgs& a, bool train, int ns, const int* seeds, const fl
 bool snet3_supported(const SNetArgs& a);
 int snet3_nbl(int n);
 int snet3_nsm(int si, int so, int nh, int n);
-long snet3_plane_floats(int n);
 long snet3_ring_floats_per_wave(int n, int nh);
 bool jac_supported(const SNetArgs& a);      // JacobianLayer / HessianLayer: wider than snet3_supported (single plane buffer when needed)
 void launch_jac(const SNetArgs& a, int ns, const int* seeds, const float* const* zd, int nx_total, int x0, float* dydx,
@@ -263,7 +247,6 @@ void launch_hess(const SNetArgs& a, int seed_j, int seed_k, int hj, int hk, int 
 void launch_mlp_jac(const PNetArgs& a, int NB, int seed, float* ZD, hipStream_t st);
 void launch_ll_jac_out(const float* PHI, const float* Z, const float* PHID, const float* ZD, long B, int r, int so,
                        int nx_total, int xcol, float* dydx, hipStream_t st);
-void launch_pack16(const float* theta, const MatRef& m, int NBL, f32x4* WF, f32x4* WB, hipStream_t st);
 int launch_gw_mfma(const GwArgs& a, int NBI, int NBO, int rows, hipStream_t st);   // -1: bf16 dL/da rows handed to a shape without a DAB form
 void launch_gw_first(const GwArgs& a, int NBO, int rows, hipStream_t st);
 void launch_gw_out(const GwArgs& a, int NBI, int rows, hipStream_t st);
