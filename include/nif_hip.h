@@ -111,7 +111,10 @@ int nif_abi_version(void);
 int nif_device_count(void);
 
 /* ---- lifetime ------------------------------------------------------------------------- */
-/* replaces: NIF(cfg_shape_net, cfg_parameter_net, mixed_policy) + .build()  model.py:73,345 */
+/* replaces: NIF(cfg_shape_net, cfg_parameter_net, mixed_policy) + .build()  model.py:73,345
+ * Width limits (NIF_ERR_INVALID beyond them): n_st in [1,128]; n_sx in [1,128] for NIF_KIND_NIF / NIF_KIND_MULTISCALE and in [1,512]
+ * for NIF_KIND_LASTLAYER, there above 128 only with s_resblock = 0 and mixed_policy = NIF_POLICY_FLOAT32.  On such a wide context
+ * nif_jacobian, nif_hessian[_dev], nif_sobolev_* return NIF_ERR_INVALID (their kernels stop at 128 units). */
 int nif_create(const nif_cfg* cfg, int device_id, nif_ctx** out);
 int nif_destroy(nif_ctx* ctx);
 

@@ -359,10 +359,18 @@ __global__ __launch_bounds__(64 * NIF_PBW_WAVES) void k_pnet_bwg(PbwArgs G) {
   }
 }
 
+// dynamic LDS of a k_pnet_bwg launch
+static size_t pbw_shm_bytes(const PNetArgs& a) {
+  const int nm = a.lst * (a.res ? 2 : 1);
+  return ((size_t)NIF_PBW_WAVES * ((nm + 2) * 1024 + 256) + (size_t)((psmall_floats(a, 1) + 3) & ~3) + (size_t)nm * 2560) * sizeof(float);
+}
 bool pnet_bwg_supported(const PNetArgs& a) {
   const int nm = a.lst * (a.res ? 2 : 1);
   // (last-layer class: DZ is then dL/dlatent in front of the rl x rl map, whose own gradient stays a k_gw_out launch)
-  return a.nst <= 32 && a.pi <= 6 && a.r <= 32 && nm >= 1 && nm <= 2 && (!a.res || a.lst == 1);
+  if (!(a.nst <= 32 && a.pi <= 6 && a.r <= 32 && nm >= 1 && nm <= 2 && (!a.res || a.lst == 1))) return false;
+  // two matrices and pi + latent_dim >= 16 small vectors: the dynamic part plus the kernel's static `red` passes the 160 KB of a CU and
+  // the launch aborts the queue (seen at latent_dim 16): such a net takes the stash path (k_pnet_bwd + the k_gw_* stack)
+  return pbw_shm_bytes(a) + sizeof(float) * (NIF_PBW_WAVES - 1) * 64 <= 160 * 1024;
 }
 
 void launch_pnet_bwg(const PNetArgs& a, float* partial, long pstride, int rows, hipStream_t st, const float* touch,
@@ -370,8 +378,7 @@ void launch_pnet_bwg(const PNetArgs& a, float* partial, long pstride, int rows, 
   PbwArgs G; G.p = a; G.partial = partial; G.pstride = pstride; G.touch = touch; G.touch_floats = touch_floats;
   const int nm = a.lst * (a.res ? 2 : 1);
   dim3 grid(rows), block(64 * NIF_PBW_WAVES);
-  const size_t shm = ((size_t)NIF_PBW_WAVES * ((nm + 2) * 1024 + 256) + (size_t)((psmall_floats(a, 1) + 3) & ~3) +
-                      (size_t)nm * 2560) * sizeof(float);
+  const size_t shm = pbw_shm_bytes(a);
 #define PBW1(NM_, RES_, ACT_, SM_)                                                                                  \
   {                                                                                                                 \
     (void)hipFuncSetAttribute((const void*)k_pnet_bwg<NM_, RES_, ACT_, SM_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \

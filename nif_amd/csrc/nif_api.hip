@@ -114,7 +114,8 @@ static int create_buffers(nif_ctx* c) {
   int rc = NIF_OK;
   const long pk_p = (long)(nm > 0 ? nm : 1) * plane_f32x4(PLANES_T32, c->NSTB);
   const long p32 = plane_f32x4(PLANES_T32, c->NB), p16 = plane_f32x4(PLANES_T16, snet3_nbl(c->n));     // one buffer serves either tile size
-  const long pk_s = (long)(nh > 0 ? nh : 1) * (c->r + 1) * (p16 > p32 ? p16 : p32);
+  // (a wide last-layer net reads its matrices row-major from theta: no plane image of any kind, one element keeps the buffers non-null)
+  const long pk_s = c->use_wide ? 1 : (long)(nh > 0 ? nh : 1) * (c->r + 1) * (p16 > p32 ? p16 : p32);
   if (!rc) rc = c->pWF.alloc(pk_p);
   if (!rc) rc = c->pWB.alloc(pk_p);
   if (!rc) rc = c->sWF.alloc(pk_s);
@@ -138,7 +139,7 @@ static int create_buffers(nif_ctx* c) {
   if (c->kind == NIF_KIND_LASTLAYER && nh > 0 && c->n <= 128 && !rc)
     rc = c->ll_slots.alloc((long)c->si * c->n + (long)nh * c->n * c->n + (long)c->n * c->so * c->r +
                            c->n + (long)nh * c->n + c->so * c->r + c->so + c->r * c->r + 64);
-  const long pk_l = (long)(nh > 0 ? nh : 1) * plane_f32x4(PLANES_T32, c->NB);
+  const long pk_l = c->use_wide ? 1 : (long)(nh > 0 ? nh : 1) * plane_f32x4(PLANES_T32, c->NB);
   if (!rc && c->kind == NIF_KIND_LASTLAYER) rc = c->lWF.alloc(pk_l);
   if (!rc && c->kind == NIF_KIND_LASTLAYER) rc = c->lWB.alloc(pk_l);
   return rc;
@@ -166,8 +167,17 @@ extern "C" int nif_create(const nif_cfg* cfg, int device_id, nif_ctx** out) {
     return fail(NIF_ERR_INVALID, "last-layer class: latent_dim * output_dim must be <= 64");
   if (cfg->pi_dim < 1 || cfg->si_dim < 1 || cfg->so_dim < 1 || cfg->latent_dim < 1)
     return fail(NIF_ERR_INVALID, "dims must be >= 1");
-  if (cfg->n_sx < 1 || cfg->n_sx > 128 || cfg->n_st < 1 || cfg->n_st > 128)
-    return fail(NIF_ERR_INVALID, "units must be in [1,128]");
+  if (cfg->n_sx < 1 || cfg->n_st < 1) return fail(NIF_ERR_INVALID, "units must be >= 1");
+  if (cfg->n_st > 128) return fail(NIF_ERR_INVALID, "ParameterNet units must be in [1,128]");
+  // ShapeNets wider than 128 units: the last-layer class alone, on the workgroup-tiled layer kernels (k_wide.hip)
+  const bool wide = cfg->n_sx > 128;
+  if (wide && cfg->kind != NIF_KIND_LASTLAYER)
+    return fail(NIF_ERR_INVALID, "ShapeNet units must be in [1,128] for NIF / NIFMultiScale: only the last-layer class goes wider (up to 512)");
+  if (cfg->n_sx > 512) return fail(NIF_ERR_INVALID, "ShapeNet units must be in [1,512] for the last-layer class");
+  if (wide && cfg->s_resblock)
+    return fail(NIF_ERR_INVALID, "ShapeNet wider than 128 units: plain SIREN only, use_resblock stops at 128 units");
+  if (wide && cfg->mixed_policy != NIF_POLICY_FLOAT32)
+    return fail(NIF_ERR_INVALID, "ShapeNet wider than 128 units: mixed_policy float32 only, the mixed policies stop at 128 units");
   if (cfg->latent_dim > 64) return fail(NIF_ERR_INVALID, "latent_dim must be <= 64");
   if (cfg->pi_dim > 16 || cfg->si_dim > 16 || cfg->so_dim > 16)
     return fail(NIF_ERR_INVALID, "input/output dims must be <= 16");
@@ -193,6 +203,7 @@ extern "C" int nif_create(const nif_cfg* cfg, int device_id, nif_ctx** out) {
   c->kind = cfg->kind; c->pi = cfg->pi_dim; c->si = cfg->si_dim; c->so = cfg->so_dim;
   c->n = cfg->n_sx; c->L = cfg->l_sx; c->nst = cfg->n_st; c->lst = cfg->l_st; c->r = cfg->latent_dim;
   c->nh = nh; c->nm = nm;
+  c->use_wide = wide;
   c->NB = c->n <= 32 ? 1 : (c->n <= 64 ? 2 : 4);
   c->NSTB = c->nst <= 32 ? 1 : (c->nst <= 64 ? 2 : 4);
   c->po = (long)nh * c->n * c->n + (long)(c->si + c->so + 1 + nh) * c->n + c->so;
@@ -393,16 +404,23 @@ static int ensure_rows(nif_ctx* c, long B) {
 // way leaves none and cap = 0, so the next call builds them again.
 static int ensure_capacity(nif_ctx* c, long B, bool train) {
   const long pts = (B + 31) / 32 * 32;
-  if (pts > c->cap || (train && !c->stash_s)) {
+  if (pts > c->cap || (train && !(c->use_wide ? c->wide_stash : c->stash_s))) {
     const long newcap = pts > c->cap ? pts : c->cap;
     const bool ll = c->kind == NIF_KIND_LASTLAYER;
+    if (c->use_wide && c->capturing)
+      return fail(NIF_ERR_STATE, "a workspace of the wide ShapeNet would have to grow inside a graph capture: call nif_reserve for the largest batch first");
     DevBuf<float>* ws[] = {&c->Z, &c->DZ, &c->DU, &c->ZL, &c->PHI, &c->DPHI, &c->DA, &c->DZL};
     const long wsz[] = {(long)c->r * newcap, (long)c->r * newcap, (long)c->so * newcap, (long)32 * c->RB * newcap,
                         (long)c->r * c->so * newcap, (long)c->r * c->so * newcap, (long)c->r * newcap, (long)c->r * newcap};
     int rc = NIF_OK;
     for (int i = 0; i < (ll ? 8 : 4) && !rc; ++i) rc = ws[i]->reserve(c, wsz[i]);
-    if (!rc && newcap > c->cap) { rc = c->stash_s.release(c); if (!rc) rc = c->stash_p.release(c); }      // (their slot strides follow cap)
-    if (!rc && train) {
+    if (!rc && c->use_wide) rc = c->wide_act.reserve(c, 2L * c->n * newcap);
+    if (!rc && newcap > c->cap) { rc = c->stash_s.release(c); if (!rc) rc = c->stash_p.release(c); if (!rc) rc = c->wide_stash.release(c); }      // (their slot strides follow cap)
+    if (!rc && train && c->use_wide) {      // sin and cos of every layer's phase; the ShapeNet's 32-point stash does not exist
+      c->slot_p = (long)c->NSTB * 32 * newcap;
+      rc = c->wide_stash.reserve(c, 2L * (c->nh + 1) * c->n * newcap);
+      if (!rc) rc = c->stash_p.reserve(c, c->slot_p * (2 * c->nm + 2));
+    } else if (!rc && train) {
       c->slot_s = (long)c->NB * 32 * newcap;
       c->slot_p = (long)c->NSTB * 32 * newcap;
       // r6 (fuzz case 606/16): k_snet6 keeps its private h ring in this buffer -- [workgroups][8 waves][nh][64 features][16 points],
@@ -419,7 +437,7 @@ static int ensure_capacity(nif_ctx* c, long B, bool train) {
     }
     if (rc) {
       for (DevBuf<float>* b : ws) b->drop();
-      c->stash_s.drop(); c->stash_p.drop();
+      c->stash_s.drop(); c->stash_p.drop(); c->wide_act.drop(); c->wide_stash.drop();
       c->cap = 0;
       return rc;
     }
@@ -633,6 +651,62 @@ static int ensure_packed(nif_ctx* c) {
   return NIF_OK;
 }
 
+// ---- last-layer class at 129..512 units: the shared SIREN ShapeNet layer by layer (k_wide.hip) -----------------------
+// Layer l of the ShapeNet as the three roles see it: 0 the first layer (si -> n), 1 .. nh the hidden matrices, nh + 1 the linear
+// bottleneck (n -> r so).  omega_0 multiplies the product of the sine layers only
+static WideArgs wide_layer(const nif_ctx* c, int l, long B) {
+  WideArgs a; memset(&a, 0, sizeof(a));
+  a.theta = c->theta; a.B = B; a.ntiles = (B + 31) / 32;
+  if (l == 0) { a.w_off = c->s_first_w; a.b_off = c->s_first_b; a.nin = c->si; a.nout = c->n; }
+  else if (l <= c->nh) { snet_mat(c, l - 1, &a.w_off, &a.b_off); a.nin = c->n; a.nout = c->n; }
+  else { a.w_off = c->s_bott_w; a.b_off = c->s_bott_b; a.nin = c->n; a.nout = c->r * c->so; }
+  a.ld = a.nout;
+  a.sine = l <= c->nh; a.scale = a.sine ? c->cfg.s_omega0 : 1.0f;
+  return a;
+}
+// slot s of a buffer of n-row tiles sized for c->cap points
+static float* wide_slot(const nif_ctx* c, const DevBuf<float>& buf, int s) { return buf.p + (long)s * c->n * c->cap; }
+// x (columns col0 .. of xin [B][ncol]) -> c->PHI.  train: sin and cos of every layer's phase stay in wide_stash for the adjoint and the
+// weight gradients; else the layers alternate between the halves of wide_act
+static void wide_forward(nif_ctx* c, const float* xin, int ncol, int col0, long B, bool train) {
+  const float* in = nullptr;
+  for (int l = 0; l <= c->nh + 1; ++l) {
+    WideArgs a = wide_layer(c, l, B);
+    a.IN = in; a.xin = xin; a.ncol = ncol; a.col0 = col0;
+    if (l == c->nh + 1) a.OUT = c->PHI;
+    else if (train) { a.OUT = wide_slot(c, c->wide_stash, l); a.COS = wide_slot(c, c->wide_stash, c->nh + 1 + l); }
+    else a.OUT = wide_slot(c, c->wide_act, l & 1);
+    launch_wide_fwd(a, c->st);
+    in = a.OUT;
+  }
+}
+// Behind wide_forward(train) and the head (c->DPHI): the adjoint sweep and every ShapeNet weight gradient into `rows` partial rows.
+// dL/da of layer l sits in half l & 1 of wide_act: the gradient of a layer is launched before the sweep overwrites its dL/da
+static void wide_backward(nif_ctx* c, const float* xin, int ncol, int col0, long B, int rows) {
+  const int nh = c->nh;
+  const float* da = c->DPHI;
+  for (int l = nh + 1; l >= 0; --l) {
+    WideArgs a = wide_layer(c, l, B);
+    a.DA = da; a.partial = c->partial; a.pstride = c->pstride;
+    if (l > 0) {      // dL/da of the layer below, through this layer's matrix and that layer's cosine
+      ProfScope p_(c, NIF_PROF_SNET);
+      a.OUT = wide_slot(c, c->wide_act, (l - 1) & 1); a.COS = wide_slot(c, c->wide_stash, nh + 1 + (l - 1));
+      launch_wide_adj(a, c->st);
+    }
+    {
+      ProfScope p_(c, NIF_PROF_GW);
+      a.IN = l > 0 ? wide_slot(c, c->wide_stash, l - 1) : nullptr; a.xin = xin; a.ncol = ncol; a.col0 = col0;
+      launch_wide_gw(a, rows, c->st);
+    }
+    da = a.OUT;
+  }
+}
+static int wide_refused(const nif_ctx* c, const char* who) {
+  if (!c->use_wide) return NIF_OK;
+  return fail(NIF_ERR_INVALID, std::string(who) + ": the derivative kernels take ShapeNets of up to 128 units (this one has " +
+                                   std::to_string(c->n) + ")");
+}
+
 // The forward of B rows behind ensure_packed / ensure_capacity.  with_pnet: xin [B][pi + si], the ParameterNet fills Z; without (the
 // snapshot entries): Z already holds every point's latent and the coordinates are columns col0 .. col0 + si of xin [B][ncol]
 static int forward_rows(nif_ctx* c, const float* xin, int ncol, int col0, long B, float* u, bool with_pnet) {
@@ -649,8 +723,8 @@ static int forward_rows(nif_ctx* c, const float* xin, int ncol, int col0, long B
       HIPCHK(hipGetLastError());
       return NIF_OK;
     }
-    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, col0, B);
-    launch_pnet(ma, c->NB, false, c->st);
+    if (c->use_wide) wide_forward(c, xin, ncol, col0, B, false);
+    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, col0, B); launch_pnet(ma, c->NB, false, c->st); }
     LLArgs la; fill_ll(c, la, B); la.u_out = u;
     launch_ll_out(la, false, c->st);
     HIPCHK(hipGetLastError());
@@ -816,8 +890,8 @@ extern "C" int nif_forward_snapshots_dev(nif_ctx* c, const float* rows, int32_t 
   if (combined) return snap_combined(c, c->snap + snap_r4(off_f + lat_f), tc_max, lat, T, x, sn.offsets, offsets, M, u);
   if (phi_dot) {      // one ShapeNet pass over the mesh for all snapshots
     ProfScope p_(c, NIF_PROF_SNET_FWD);
-    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, M);
-    launch_pnet(ma, c->NB, false, c->st);
+    if (c->use_wide) wide_forward(c, x, c->si, 0, M, false);
+    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, M); launch_pnet(ma, c->NB, false, c->st); }
     launch_phi_dot(c->PHI, lat, c->theta + c->ll_bias, T, M, c->r, c->so, u, c->st);
     HIPCHK(hipGetLastError());
     return NIF_OK;
@@ -851,6 +925,7 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
     if (y_idx[i] < 0 || y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
   for (int j = 0; j < nx; ++j)
     if (x_idx[j] < 0 || x_idx[j] >= c->pi + c->si) return fail(NIF_ERR_INVALID, "x_index out of range");
+  { const int rcw = wide_refused(c, "JacobianLayer"); if (rcw) return rcw; }
   NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   int rc = ensure_packed(c); if (rc) return rc;
@@ -1023,7 +1098,7 @@ static int hessian_check(nif_ctx* c, const void* xin, int64_t B, const int32_t* 
     if (y_idx[i] < 0 || y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
   for (int j = 0; j < nx; ++j)
     if (x_idx[j] < 0 || x_idx[j] >= c->pi + c->si) return fail(NIF_ERR_INVALID, "x_index out of range (0 <= i < pi_dim + si_dim)");
-  return NIF_OK;
+  return wide_refused(c, "HessianLayer");
 }
 extern "C" int nif_hessian_dev(nif_ctx* c, const float* xin_dev, int64_t B, const int32_t* y_idx, int32_t ny, const int32_t* x_idx,
                                int32_t nx, float* y_dev, float* dydx_dev, float* d2_dev) {
@@ -1078,8 +1153,8 @@ extern "C" int nif_x_to_phi(nif_ctx* c, const float* x, int64_t B, float* phi) {
   rc = ensure_capacity(c, B, false); if (rc) return rc;
   rc = stage(c, c->d_a, x, B * c->si); if (rc) return rc;
   rc = stage(c, c->d_d, nullptr, B * c->so * c->r); if (rc) return rc;
-  ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, c->d_a, c->si, 0, B);
-  launch_pnet(ma, c->NB, false, c->st);
+  if (c->use_wide) wide_forward(c, c->d_a, c->si, 0, B, false);
+  else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, c->d_a, c->si, 0, B); launch_pnet(ma, c->NB, false, c->st); }
   launch_tiles_to_rows(c->PHI, B, c->so * c->r, c->d_d, c->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(phi, c->d_d, sizeof(float) * (size_t)(B * c->so * c->r), hipMemcpyDeviceToHost, c->st));
@@ -1115,8 +1190,8 @@ extern "C" int nif_shapenet_given_w_dev(nif_ctx* c, const float* x, const float*
   if (c->kind == NIF_KIND_LASTLAYER) {   // u = Dot(phi(x), w) + bias with caller-supplied w [B, r]
     int rc = ensure_packed(c); if (rc) return rc;
     rc = ensure_capacity(c, B, false); if (rc) return rc;
-    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, B);
-    launch_pnet(ma, c->NB, false, c->st);
+    if (c->use_wide) wide_forward(c, x, c->si, 0, B, false);
+    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, B); launch_pnet(ma, c->NB, false, c->st); }
     launch_rows_to_tiles(w, B, c->r, c->Z, c->st);
     LLArgs la; fill_ll(c, la, B); la.u_out = u;
     launch_ll_out(la, false, c->st);
@@ -1269,7 +1344,8 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   const int ncol = c->pi + c->si;
   const int nsc = ns > 0 ? sp->nsc : 0, nhead = ns > 0 ? sp->ns - sp->nsc : 0;   // coordinate streams / parameter-column heads
   PNetArgs pa; fill_pnet(c, pa, xin, B);
-  ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, c->pi, B);
+  if (!c->use_wide) ensure_ll_mlp_planes(c);      // (a wide net has no plane image)
+  PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, c->pi, B);
   LLArgs la; fill_ll(c, la, B);
   la.y = y; la.sw = sw; la.inv_bg = 1.0f / (float)Bg;
   const bool fused_p = !pnet_force_stash() && pnet_bwg_supported(pa);
@@ -1299,6 +1375,10 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     }
     ProfScope p_(c, NIF_PROF_SNET);
     launch_sob(sa, true, nsc, sp->seeds, gt, wj, c->dring, nullptr, false, c->st, &spar);
+  } else if (c->use_wide) {      // layer by layer; the adjoint sweep runs next to the weight gradients below
+    ProfScope p_(c, NIF_PROF_SNET);
+    wide_forward(c, xin, ncol, c->pi, B, true);
+    launch_ll_out(la, true, c->st);
   } else if (c->use_ll4) {
     SNetArgs sa; fill_snet_ll(c, sa, xin, ncol, c->pi, B);
     sa.y = y; sa.sw = sw; sa.loss_partial = c->loss_partial; sa.inv_bg = 1.0f / (float)Bg;
@@ -1332,6 +1412,7 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
   { ProfScope p_(c, NIF_PROF_PNET_BWD);
     if (fused_p) launch_pnet_bwg(pa, c->partial, c->pstride, rows, c->st);
     else launch_pnet_bwd(pa, c->NSTB, c->st); }
+  if (c->use_wide) wide_backward(c, xin, ncol, c->pi, B, rows);      // adjoint sweep + first, hidden, bottleneck gradients (k_wide.hip)
   {
     ProfScope p_(c, NIF_PROF_GW);
     const GwArgs base = gw_base(c, ntiles, B, c->partial);
@@ -1341,22 +1422,24 @@ static int loss_grad_ll(nif_ctx* c, const float* xin, const float* y, const floa
     float* sST = c->stash_s;
     // ShapeNet (dense SIREN): first, hidden matrices, bottleneck (n -> r*so), last_layer_bias
     GwArgs g = sbase;
-    g.DA = sST + (long)(nms + 1) * c->slot_s; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.scale = ma.omega;
-    if (ns > 0 && sp->hess) g.ntiles = ntiles * 3;      // (the second-order stream has no first-layer input: a'' = 0 there)
-    g.W = dense_ref(c->s_first_w, c->si, c->n); g.Bv = vec_ref(c->s_first_b, c->n);
-    launch_gw_first(g, c->NB, rows, c->st);
-    for (int mi = 0; mi < nms; ++mi) {
-      g = sbase; g.IN = sST + (long)mi * c->slot_s; g.DA = sST + (long)(nms + 2 + mi) * c->slot_s; g.scale = ma.omega;
-      long w_off, b_off; snet_mat(c, mi, &w_off, &b_off);
-      g.W = dense_ref(w_off, c->n, c->n); g.Bv = vec_ref(b_off, c->n);
-      g.da_bf16 = ll_dab ? 1 : 0;
-      g.in_ph16 = ll_ph ? 1 : 0;
-      if (launch_gw_mfma(g, c->NB, c->NB, rows, c->st) < 0) return fail(NIF_ERR_STATE, "internal: bf16 dL/da stash rows without a reader of that form");
+    if (!c->use_wide) {      // (a wide net: wide_backward above)
+      g.DA = sST + (long)(nms + 1) * c->slot_s; g.xin = xin; g.ncol = ncol; g.col0 = c->pi; g.nd = c->si; g.scale = ma.omega;
+      if (ns > 0 && sp->hess) g.ntiles = ntiles * 3;      // (the second-order stream has no first-layer input: a'' = 0 there)
+      g.W = dense_ref(c->s_first_w, c->si, c->n); g.Bv = vec_ref(c->s_first_b, c->n);
+      launch_gw_first(g, c->NB, rows, c->st);
+      for (int mi = 0; mi < nms; ++mi) {
+        g = sbase; g.IN = sST + (long)mi * c->slot_s; g.DA = sST + (long)(nms + 2 + mi) * c->slot_s; g.scale = ma.omega;
+        long w_off, b_off; snet_mat(c, mi, &w_off, &b_off);
+        g.W = dense_ref(w_off, c->n, c->n); g.Bv = vec_ref(b_off, c->n);
+        g.da_bf16 = ll_dab ? 1 : 0;
+        g.in_ph16 = ll_ph ? 1 : 0;
+        if (launch_gw_mfma(g, c->NB, c->NB, rows, c->st) < 0) return fail(NIF_ERR_STATE, "internal: bf16 dL/da stash rows without a reader of that form");
+      }
+      g = sbase; g.IN = sST + (long)nms * c->slot_s; g.SM = c->DPHI; g.nc = c->r * c->so;
+      g.W = dense_ref(c->s_bott_w, c->n, c->r * c->so); g.Bv = vec_ref(c->s_bott_b, c->r * c->so);
+      launch_gw_out(g, c->NB, rows, c->st);
     }
-    g = sbase; g.IN = sST + (long)nms * c->slot_s; g.SM = c->DPHI; g.nc = c->r * c->so;
-    g.W = dense_ref(c->s_bott_w, c->n, c->r * c->so); g.Bv = vec_ref(c->s_bott_b, c->r * c->so);
-    launch_gw_out(g, c->NB, rows, c->st);
-    g = base; g.IN = sST + (long)nms * c->slot_s; g.SM = c->DU; g.nc = c->so;   // only the bias part: W.nin = 0
+    g = base; g.IN = c->use_wide ? nullptr : sST + (long)nms * c->slot_s; g.SM = c->DU; g.nc = c->so;   // only the bias part: W.nin = 0 (k_gw_bias reads SM alone)
     g.W = dense_ref(0, 0, c->so); g.Bv = vec_ref(c->ll_bias, c->so);
     launch_gw_out(g, c->NB, rows, c->st);
     // ParameterNet: first, hidden matrices, bottleneck, last (r x r)
@@ -1760,6 +1843,7 @@ static int sobolev_plan(nif_ctx* c, const int32_t* x_idx, int32_t nx, SobPlan* s
 // (gradient.py:207-231).  dydx rows are [so][nx] either way (rows of unlisted outputs are not read into the loss).
 static int sobolev_check(nif_ctx* c, const int32_t* x_idx, int32_t nx, const int32_t* y_idx, int32_t ny, unsigned* ymask, int* ny_out) {
   if (!x_idx || nx < 1 || nx > 16) return fail(NIF_ERR_INVALID, "Sobolev training takes 1..16 input columns in x_index");
+  { const int rcw = wide_refused(c, "Sobolev step / forward"); if (rcw) return rcw; }
   for (int d = 0; d < nx; ++d) {
     if (x_idx[d] < 0 || x_idx[d] >= c->pi + c->si) return fail(NIF_ERR_INVALID, "Sobolev x_index out of range (0 <= i < pi_dim + si_dim)");
     for (int e = 0; e < d; ++e)

@@ -134,6 +134,11 @@ struct nif_ctx {
   DevBuf<float> sob_acc;             // [grad | loss] summed over the column groups of a Sobolev step with more than three x_index columns
   float act_l1 = 0.f, act_l2 = 0.f; DevBuf<float> act_part, act_loss;
   DevBuf<float> PHI, DPHI, DA, DZL;
+  // last-layer class at 129..512 units (k_wide.hip, decided at nif_create): the layers' activations of a forward pass / dL/da of an
+  // adjoint sweep alternate between the two halves of wide_act [2][n][cap]; a training step keeps sin and cos of every layer's phase
+  // in wide_stash [2 (nh + 1)][n][cap] (slot l: sin of layer l, slot nh + 1 + l: its cos).  Both grow in ensure_capacity
+  bool use_wide = false;
+  DevBuf<float> wide_act, wide_stash;
   // profiling: (group id, start, stop) event triples recorded on st
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;

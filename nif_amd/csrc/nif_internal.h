@@ -398,6 +398,25 @@ struct LLArgs {
   float* loss_partial;  // [gridDim.x]
 };
 void launch_ll_out(const LLArgs& a, bool train, hipStream_t st);
+// last-layer class at 129..512 units: one dense layer of the shared SIREN ShapeNet per launch, tiled over a workgroup (k_wide.hip).
+// Every activation / adjoint buffer is [tiles][features][32] with exactly `features` rows per tile (the layout of PHI / DPHI)
+struct WideArgs {
+  const float* theta;
+  long w_off; int ld;           // W[in][out] at theta + w_off + in * ld + out, row-major as Keras keeps it
+  long b_off;                   // bias [out] (forward: read; gradient: where db goes in a partial row)
+  int nin, nout;
+  const float* IN;              // forward / gradient: the layer's input [tiles][nin][32]; null: the first layer, read from xin
+  const float* DA;              // adjoint / gradient: dL/d(pre-activation of this layer) [tiles][nout][32]
+  const float* xin; int ncol, col0;     // first layer: input rows [B][ncol], columns col0 .. col0 + nin
+  float* OUT;                   // forward [tiles][nout][32]; adjoint [tiles][nin][32]
+  float* COS;                   // forward, training: cos of the phase [tiles][nout][32] (null: not kept); adjoint: the factor READ [tiles][nin][32]
+  float scale; int sine;        // forward: phase = scale acc + b, OUT = sine ? sin(phase) : phase; adjoint / gradient: the factor on acc
+  long B, ntiles;
+  float* partial; long pstride; // gradient: partial row blockIdx.x
+};
+void launch_wide_fwd(const WideArgs& a, hipStream_t st);
+void launch_wide_adj(const WideArgs& a, hipStream_t st);
+void launch_wide_gw(const WideArgs& a, int rows, hipStream_t st);      // writes W's and the bias' columns of `rows` partial rows
 // latent Jacobian regulariser (k_pjac.hip): tangents of the ParameterNet + their adjoint; operand pairs into the stash
 bool pjac_supported(const PNetArgs& a);
 int launch_pjac(const PNetArgs& a, float coef, float* MU, float* loss_partial, int c0, int nd, hipStream_t st);   // columns [c0, c0 + nd), nd <= pjac_group()
