@@ -197,6 +197,24 @@ SNAPSHOT_SIGNATURES = {
 }
 
 
+NIF_ENCODE_ABI_VERSION = 1
+
+
+class nif_encode_args(C.Structure):
+    """include/nif_hip_encode.h, field for field"""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("reserved0", C.c_int32), ("ctx", _CTX), ("latents", _VP), ("T", C.c_int64), ("x", _VP),
+        ("offsets_host", C.POINTER(C.c_int64)), ("M", C.c_int64), ("y", _VP), ("w", _VP), ("S_out", _VP), ("reserved", C.c_int64 * 4),
+    ]
+
+
+# include/nif_hip_encode.h, one to one (bound by load() with the tables above)
+ENCODE_SIGNATURES = {
+    "nif_snapshot_normal_eq": (C.c_int, [C.POINTER(nif_encode_args)]),
+    "nif_snapshot_normal_eq_dev": (C.c_int, [C.POINTER(nif_encode_args)]),
+}
+
+
 def load():
     """dlopen libnif_hip.so and bind every symbol of include/nif_hip.h.  Raises if it is absent."""
     global _lib
@@ -207,7 +225,7 @@ def load():
             "libnif_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-    for name, (res, args) in list(SIGNATURES.items()) + list(SNAPSHOT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SNAPSHOT_SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -14,6 +14,7 @@
 
 #include "nif_ctx.h"
 #include "../../include/nif_hip_snapshots.h"
+#include "../../include/nif_hip_encode.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
 static inline bool act_on(const nif_ctx* c) { return c->act_l1 != 0.f || c->act_l2 != 0.f; }
@@ -913,6 +914,157 @@ extern "C" int nif_forward_snapshots(nif_ctx* c, const float* rows, int32_t rows
   rc = stage(c, c->d_d, nullptr, n * c->so); if (rc) return rc;
   rc = nif_forward_snapshots_dev(c, c->d_a, rows_are_latent, T, c->d_b, offsets, M, c->d_d); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(u, c->d_d, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+
+// ---- per-snapshot normal equations in the latent (k_encode.hip, include/nif_hip_encode.h) --------------------------
+static int enc_check(const nif_encode_args* a, long* n) {
+  if (!a) return fail(NIF_ERR_INVALID, "null");
+  if (a->abi_version != NIF_ENCODE_ABI_VERSION)
+    return fail(NIF_ERR_INVALID, "nif_encode_args: abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(NIF_ENCODE_ABI_VERSION));
+  if (a->reserved0 || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
+    return fail(NIF_ERR_INVALID, "nif_encode_args: reserved fields must be zero");
+  const nif_ctx* c = a->ctx;
+  const int64_t* off = a->offsets_host;
+  if (!c || !a->latents || !a->S_out || a->T <= 0 || (off ? off[0] != 0 : a->M < 0)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (off) for (int64_t t = 0; t < a->T; ++t) if (off[t + 1] < off[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
+  *n = off ? (long)off[a->T] : (long)(a->T * a->M);
+  if (*n > 0 && (!a->x || !a->y)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
+    return fail(NIF_ERR_INVALID, std::string("nif_snapshot_normal_eq: not built for the ") +
+                                     (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
+                                     " policy (the tangent kernels run exact products, the policy's forward does not)");
+  if (c->r > 64) return fail(NIF_ERR_INVALID, "nif_snapshot_normal_eq: latent_dim " + std::to_string(c->r) + " > 64");
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_snapshot_normal_eq: not capturable (inside nif_graph_begin / nif_graph_end)");
+  return NIF_OK;
+}
+// floats per padded point of a chunk: what encode holds in c->enc, and for the last-layer class what ensure_capacity holds besides
+static long enc_point_floats(const nif_ctx* c) {
+  if (c->kind == NIF_KIND_LASTLAYER) return c->si + 2L * c->r * c->so + 3L * c->r + c->so + (c->use_wide ? 2L * c->n : 0);
+  return 2L * c->r + c->si + (long)c->so * c->r + c->so;
+}
+extern "C" int nif_snapshot_normal_eq_dev(const nif_encode_args* a) {
+  long n = 0;
+  int rc = enc_check(a, &n); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  rc = ensure_packed(c); if (rc) return rc;
+  const bool ll = c->kind == NIF_KIND_LASTLAYER;
+  if (!ll) {
+    if (!c->jac_ok) return fail(NIF_ERR_INVALID, "nif_snapshot_normal_eq: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU (the JacobianLayer kernels do not take it)");
+    rc = ensure_packed32(c); if (rc) return rc;
+  }
+  const long T = a->T, M = a->M;
+  const int r = c->r, so = c->so, si = c->si;
+  if (n == 0) {
+    HIPCHK(hipMemsetAsync(a->S_out, 0, sizeof(double) * (size_t)(T * (r + 1) * (r + 1)), c->st));
+    return NIF_OK;
+  }
+  const int64_t* off = a->offsets_host;
+  const bool shared_phi = ll && !off;      // one ShapeNet pass over the mesh for all snapshots, no padded copy of anything
+  // the padded layout: snapshot t owns the tiles tile_start[t] .. tile_start[t + 1]
+  static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
+  std::vector<long> meta(2 * (T + 1));
+  long* tile_start = meta.data();
+  long* offs = tile_start + T + 1;
+  tile_start[0] = 0;
+  for (long t = 0; t < T; ++t) {
+    offs[t] = off ? off[t] : t * M;
+    tile_start[t + 1] = tile_start[t] + ((off ? off[t + 1] - off[t] : M) + 31) / 32;
+  }
+  offs[T] = n;
+  // chunks of whole snapshots within the budget of nif_forward_snapshots' images (at least one snapshot each)
+  const long ppf = enc_point_floats(c);
+  const long budget = c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES;
+  long tiles_budget = budget / (long)(sizeof(float) * 32 * ppf);
+  if (tiles_budget < 1) tiles_budget = 1;
+  std::vector<long> cuts{0};
+  long tiles_max = 0;
+  if (shared_phi) cuts.push_back(T);
+  else
+    for (long t = 0; t < T;) {
+      long t1 = t + 1;
+      while (t1 < T && tile_start[t1 + 1] - tile_start[t] <= tiles_budget) ++t1;
+      if (tile_start[t1] - tile_start[t] > tiles_max) tiles_max = tile_start[t1] - tile_start[t];
+      cuts.push_back(t1);
+      t = t1;
+    }
+  const long meta_f = snap_r4(2 * (long)meta.size());
+  const long pts_max = tiles_max * 32;
+  const long f_z = ll ? 0 : pts_max * r, f_unit = ll ? 0 : pts_max * r + 32L * r, f_x = pts_max * si;
+  const long f_dydx = ll ? 0 : pts_max * so * r, f_u = ll ? 0 : pts_max * so;
+  rc = c->enc.reserve(c, meta_f + f_z + f_unit + f_x + f_dydx + f_u + 4); if (rc) return rc;
+  if (ll) { rc = ensure_capacity(c, shared_phi ? M : pts_max, false); if (rc) return rc; }
+  HIPCHK(hipMemcpyAsync(c->enc.p, meta.data(), sizeof(long) * meta.size(), hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));      // (host memory of this call: consumed before it returns)
+  EncArgs ea; memset(&ea, 0, sizeof(ea));
+  ea.tile_start = reinterpret_cast<const long*>(c->enc.p);
+  ea.offsets = off ? ea.tile_start + T + 1 : nullptr;
+  ea.M = M; ea.lat = a->latents; ea.x = a->x; ea.r = r; ea.si = si; ea.so = so;
+  ea.y = a->y; ea.w = a->w; ea.S = a->S_out;
+  float* Z = c->enc + meta_f;
+  float* unit = Z + f_z;
+  float* xpad = unit + f_unit;
+  float* dydx = xpad + f_x;
+  float* u = dydx + f_dydx;
+  if (ll) { ea.PHI = c->PHI; ea.bias = c->theta + c->ll_bias; ea.phi_shared = shared_phi; }
+  else { ea.dydx = dydx; ea.u = u; }
+  auto phi_pass = [&](const float* xs, long B) {      // x -> phi of B points into c->PHI, as nif_x_to_phi runs it
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    if (c->use_wide) wide_forward(c, xs, si, 0, B, false);
+    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xs, si, 0, B); launch_pnet(ma, c->NB, false, c->st); }
+  };
+  if (shared_phi) phi_pass(a->x, M);
+  for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
+    ea.t0 = cuts[ci]; ea.t1 = cuts[ci + 1];
+    const long ntiles = shared_phi ? 0 : tile_start[ea.t1] - tile_start[ea.t0];
+    if (!shared_phi && ntiles > 0) {
+      EncArgs ex = ea;
+      ex.xpad = xpad;
+      if (!ll) { ex.Z = Z; ex.unit = unit; }
+      { ProfScope p_(c, NIF_PROF_PACK); launch_encode_expand(ex, ntiles, c->st); }
+      if (ll) phi_pass(xpad, ntiles * 32);
+      else {
+        // du/dz_k = k_jac's parameter-seed stream seeded with the unit tile e_k: three latents per launch, the primal with the first
+        ProfScope p_(c, NIF_PROF_SNET_FWD);
+        SNetArgs sa; fill_snet(c, sa, xpad, si, 0, ntiles * 32);
+        sa.Z = Z;
+        for (int k0 = 0; k0 < r; k0 += 3) {
+          int seeds[3] = {-1, -1, -1};
+          const float* zd[3] = {nullptr, nullptr, nullptr};
+          const int ns = r - k0 < 3 ? r - k0 : 3;
+          for (int d = 0; d < ns; ++d) zd[d] = unit + (long)((r - (k0 + d)) % r) * 32;
+          sa.u_out = k0 == 0 ? u : nullptr;
+          launch_jac(sa, ns, seeds, zd, r, k0, dydx, c->st);
+        }
+      }
+    }
+    ProfScope p_(c, NIF_PROF_REDUCE);
+    launch_encode_gram(ea, c->st);
+  }
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_snapshot_normal_eq(const nif_encode_args* a) {
+  long n = 0;
+  int rc = enc_check(a, &n); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  const long T = a->T, e = (long)(c->r + 1) * (c->r + 1);
+  rc = stage(c, c->d_a, a->latents, T * c->r); if (rc) return rc;
+  rc = c->enc_S.reserve(c, T * e); if (rc) return rc;
+  nif_encode_args d = *a;
+  d.latents = c->d_a; d.S_out = c->enc_S;
+  if (n > 0) {
+    rc = stage(c, c->d_b, a->x, (a->offsets_host ? n : (long)a->M) * c->si); if (rc) return rc;
+    rc = stage(c, c->d_d, a->y, n * c->so); if (rc) return rc;
+    if (a->w) { rc = stage(c, c->d_c, a->w, n); if (rc) return rc; }
+    d.x = c->d_b; d.y = c->d_d; d.w = a->w ? c->d_c.p : nullptr;
+  }
+  rc = nif_snapshot_normal_eq_dev(&d); if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(a->S_out, c->enc_S, sizeof(double) * (size_t)(T * e), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }

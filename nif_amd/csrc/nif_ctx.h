@@ -153,6 +153,10 @@ struct nif_ctx {
   // slot vectors, plane scales, packed planes] of one call, rebuilt by every call.  opt_snap_bytes: the chunk's budget
   // (nif_set_option "snapshot_image_bytes", 0 = the default)
   DevBuf<float> snap; long opt_snap_bytes = 0;
+  // per-snapshot normal equations (nif_snapshot_normal_eq*, k_encode.hip): [tile_start | offsets] of one call and the padded operands
+  // [Z | unit pattern | xpad | dydx | u] of one chunk of snapshots (bounded by the same budget), rebuilt by every call; enc_S stages
+  // the host-pointer entry's result
+  DevBuf<float> enc; DevBuf<double> enc_S;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

@@ -464,6 +464,26 @@ void launch_snap_expand(const SnapArgs& a, hipStream_t st);
 // last-layer class, shared mesh: u [T][M][so] = Dot(PHI [tiles][so r][32], a [T][r]) + bias [so]
 bool phi_dot_supported(int r, int so);
 void launch_phi_dot(const float* PHI, const float* a, const float* bias, long T, long M, int r, int so, float* u, hipStream_t st);
+// per-snapshot normal equations in the latent (k_encode.hip, nif_snapshot_normal_eq*).  The snapshots t0 .. t1 of a call in
+// the padded layout: snapshot t owns the 32-point tiles tile_start[t] .. tile_start[t + 1] (whole tiles: no tile straddles two
+// snapshots; padding points repeat the snapshot's last point and weigh 0), its points are offsets[t] .. offsets[t + 1] of x / y / w
+// (offsets null: a shared mesh x [M][si], y [T][M][so], w [T][M]).  Tiles and padded points below count from tile_start[t0].
+struct EncArgs {
+  const long* tile_start; const long* offsets; long M;      // device [T + 1] each
+  long t0, t1;
+  const float* lat; const float* x; int r, si, so;          // lat [T][r]
+  // launch_encode_expand writes (where set): the latent tiles Z [tiles][r][32]; the unit pattern [tiles r + r][32], row j all ones where
+  // j % r == 0 -- `unit + ((r - k) % r) * 32` read as [tiles][r][32] is the unit tile e_k, k_jac's parameter seed of latent k; the
+  // padded coordinates xpad [tiles 32][si]
+  float* Z; float* unit; float* xpad;
+  // launch_encode_gram reads J and u from k_jac's outputs dydx [tiles 32][so][r], u [tiles 32][so]; or, PHI set (last-layer class),
+  // J = phi [tile][so r][32] and u = phi . lat + bias [so] (phi_shared: tile j of every snapshot is tile j of the mesh)
+  const float* dydx; const float* u;
+  const float* PHI; const float* bias; int phi_shared;
+  const float* y; const float* w; double* S;                // S [T][r + 1][r + 1]
+};
+void launch_encode_expand(const EncArgs& a, long ntiles, hipStream_t st);
+void launch_encode_gram(const EncArgs& a, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------
 // device helpers

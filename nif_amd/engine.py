@@ -101,6 +101,42 @@ class PinnedArray(object):
             pass
 
 
+class SnapshotSamples(object):
+    """Engine.snapshot_samples: coordinates, targets and weights of T snapshots, resident on the device"""
+
+    def __init__(self, engine, x, y, w, offsets, t, m, n):
+        self.engine, self.offsets, self.t, self.m, self.n = engine, offsets, int(t), int(m), int(n)
+        self.d_x = self.d_y = self.d_w = None
+        try:
+            if n:
+                self.d_x, self.d_y = DeviceArray(engine, x.size), DeviceArray(engine, y.size)
+                self.d_x.upload(x); self.d_y.upload(y)
+                if w is not None:
+                    self.d_w = DeviceArray(engine, w.size)
+                    self.d_w.upload(w)
+        except Exception:
+            self.free()
+            raise
+
+    def args(self, d_latents, d_s):
+        """the nif_encode_args of one call on these samples"""
+        a = _lib.nif_encode_args()
+        a.abi_version, a.ctx, a.T, a.M = _lib.NIF_ENCODE_ABI_VERSION, self.engine.ctx, self.t, self.m
+        a.latents, a.S_out = d_latents.at(0), d_s.at(0)
+        a.x = self.d_x.at(0) if self.d_x else None
+        a.y = self.d_y.at(0) if self.d_y else None
+        a.w = self.d_w.at(0) if self.d_w else None
+        if self.offsets is not None:
+            a.offsets_host = self.offsets.ctypes.data_as(C.POINTER(C.c_int64))
+        return a
+
+    def free(self):
+        for d in (self.d_x, self.d_y, self.d_w):
+            if d is not None:
+                d.free()
+        self.d_x = self.d_y = self.d_w = None
+
+
 class Engine(object):
     def __init__(self, spec, device_id=0):
         self.spec = spec
@@ -229,11 +265,11 @@ class Engine(object):
         check(self.lib.nif_forward_dev(self.ctx, d_x, int(b), d_u))
 
     # ---- snapshot-wise inference (include/nif_hip_snapshots.h; Model.predict_snapshots plans the chunks) ----------
-    def _not_capturing(self):
-        # nif_forward_snapshots* refuse a capture themselves (NIF_ERR_STATE); the staging around them (allocations, synchronous
-        # copies) would break the capture before they are reached
+    def _not_capturing(self, who="nif_forward_snapshots"):
+        # nif_forward_snapshots* and nif_snapshot_normal_eq* refuse a capture themselves (NIF_ERR_STATE); the staging around them
+        # (allocations, synchronous copies) would break the capture before they are reached
         if getattr(self, "_capturing", False):
-            raise _lib.NifError("libnif_hip error -4: nif_forward_snapshots: not capturable (inside nif_graph_begin / nif_graph_end)")
+            raise _lib.NifError("libnif_hip error -4: %s: not capturable (inside nif_graph_begin / nif_graph_end)" % who)
 
     def snapshot_mesh(self, x):
         """a shared mesh [M, si] uploaded once: the handle that forward_snapshots reads slices of (free() it when done)"""
@@ -282,6 +318,53 @@ class Engine(object):
             return self._snapshots(rows, is_latent, d_x, 0, offsets, 0, n)
         finally:
             d_x.free()
+
+    # ---- encoding (include/nif_hip_encode.h; nif_amd/encode.py runs the Levenberg-Marquardt loop around these two) ----------
+    def snapshot_samples(self, x, y, w=None, counts=None):
+        """The samples of T snapshots on the device, uploaded once for all snapshot_normal_eq calls of one encode.  counts None: a
+        shared mesh x [M, si] with y [T, M, so] (w [T, M]); else counts [T] (zeros allowed) with x [sum, si], y [sum, so] (w [sum])
+        concatenated snapshot after snapshot.  free() it when done"""
+        self._not_capturing("nif_snapshot_normal_eq")
+        s = self.spec
+        x = self._rows(x, s.si_dim, "coordinates")
+        if counts is None:
+            y = np.ascontiguousarray(y, dtype=np.float32)
+            if y.ndim != 3 or y.shape[1:] != (x.shape[0], s.so_dim):
+                raise ValueError("snapshot_samples: expected targets of shape (T, %d, %d), got %s" % (x.shape[0], s.so_dim, y.shape))
+            t, m, n, offsets = y.shape[0], x.shape[0], y.shape[0] * x.shape[0], None
+        else:
+            counts = np.asarray(counts, dtype=np.int64)
+            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            t, m, n = counts.size, 0, int(offsets[-1])
+            y = self._rows(y, s.so_dim, "targets")
+            if x.shape[0] != n or y.shape[0] != n:
+                raise ValueError("snapshot_samples: %d coordinates and %d targets for %d points" % (x.shape[0], y.shape[0], n))
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.size != n:
+                raise ValueError("snapshot_samples: %d weights for %d points" % (w.size, n))
+        return SnapshotSamples(self, x, y, w, offsets, t, m, n)
+
+    def snapshot_normal_eq(self, latents, samples):
+        """latents [T, r] -> float64 [T, r + 1, r + 1]: every snapshot's Gram matrix of the augmented rows [du/dz, u - y] at its
+        latent (A = J^T W J | g = J^T W e | c = sum w |e|^2), one device pass (nif_snapshot_normal_eq_dev)"""
+        self._not_capturing("nif_snapshot_normal_eq")
+        r = self.spec.pi_hidden
+        lat = self._rows(latents, r, "latent")
+        if lat.shape[0] != samples.t:
+            raise ValueError("snapshot_normal_eq: %d latents for %d snapshots" % (lat.shape[0], samples.t))
+        out = np.zeros((samples.t, r + 1, r + 1), dtype=np.float64)
+        if not samples.t:
+            return out
+        d_l, d_s = DeviceArray(self, lat.size), DeviceArray64(self, out.size)
+        try:
+            d_l.upload(lat)
+            a = samples.args(d_l, d_s)
+            check(self.lib.nif_snapshot_normal_eq_dev(C.byref(a)))
+            out[...] = d_s.download().reshape(out.shape)
+        finally:
+            d_l.free(); d_s.free()
+        return out
 
     def p_to_lr(self, p):
         p = self._rows(p, self.spec.pi_dim, "parameter inputs")

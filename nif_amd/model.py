@@ -327,6 +327,72 @@ class Model(object):
             flush()
         return outs
 
+    def encode_snapshots(self, x, u, latent0=None, p0=None, sample_weight=None, max_iter=20, tol=1e-8):
+        """The inverse of predict_snapshots(x, latent=...): for each of T snapshots the latent whose field fits the samples u best in
+        weighted least squares, by Levenberg-Marquardt from latent0 [T, r] (or from the ParameterNet's latents of p0 [T, pi]; exactly
+        one of the two).  x [M, si] shared with u [T, M, so] (sample_weight [T, M]), or x and u lists / tuples of T arrays [M_t, si] and
+        [M_t, so] (sample_weight a list of [M_t]); M_t = 0 is allowed and leaves that snapshot's latent as given.  The device forms every
+        snapshot's normal equations in one pass per iteration (at most max_iter + 1 passes); the r x r solves and the accept / reject
+        logic run on the host in float64 (nif_amd/encode.py).  With fewer samples than latent dimensions the normal matrix is
+        singular: the damping keeps the step in the directions the samples see, the rest of the latent stays at its start value.
+        On the device the loss bottoms out at the fp32 floor of the forward pass: with the default tol (below float32 resolution)
+        later trials are rejected until max_iter and `converged` stays False although the latent has settled; a tol of about 1e-5
+        stops there.
+        Returns EncodeResult(latent [T, r] float32, loss [T] -- Keras' mse of each snapshot --, iterations [T], converged [T])."""
+        from .encode import lm_encode
+        if self._role != "full":
+            raise ValueError("encode_snapshots exists on the full model only (%s is a sub-model view)" % self._role)
+        if (latent0 is None) == (p0 is None):
+            raise ValueError("encode_snapshots: exactly one of latent0 [T, r] and p0 [T, pi]")
+        s = self._owner._spec
+        from_p = p0 is not None
+        width = s.pi_dim if from_p else s.pi_hidden
+        rows = np.asarray(p0 if from_p else latent0, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != width:
+            raise ValueError("encode_snapshots: expected %s of shape (T, %d), got %s" % ("p0" if from_p else "latent0", width, rows.shape))
+        T, so, si = rows.shape[0], s.so_dim, s.si_dim
+        e = self._engine
+
+        def arr(a, ncol, what):
+            a = np.asarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != ncol:
+                raise ValueError("encode_snapshots: expected %s of shape (M, %d), got %s" % (what, ncol, a.shape))
+            return a
+
+        if not isinstance(x, (list, tuple)):
+            x = arr(x, si, "coordinates")
+            y = np.asarray(u, dtype=np.float32)
+            if y.shape != (T, x.shape[0], so):
+                raise ValueError("encode_snapshots: expected samples of shape (%d, %d, %d), got %s" % (T, x.shape[0], so, y.shape))
+            w = None if sample_weight is None else np.asarray(sample_weight, dtype=np.float32)
+            if w is not None and w.shape != (T, x.shape[0]):
+                raise ValueError("encode_snapshots: expected sample_weight of shape (%d, %d), got %s" % (T, x.shape[0], w.shape))
+            counts, kcounts = np.full(T, x.shape[0], dtype=np.int64), None
+        else:
+            if not isinstance(u, (list, tuple)) or len(x) != T or len(u) != T:
+                raise ValueError("encode_snapshots: %d meshes and samples for %d snapshots" % (len(x), T))
+            xs, ys = [arr(a, si, "coordinates") for a in x], [arr(a, so, "samples") for a in u]
+            counts = np.array([a.shape[0] for a in xs], dtype=np.int64)
+            if [a.shape[0] for a in ys] != list(counts):
+                raise ValueError("encode_snapshots: samples and coordinates of a snapshot differ in length")
+            w = None
+            if sample_weight is not None:
+                ws = [np.asarray(a, dtype=np.float32).reshape(-1) for a in sample_weight]
+                if [a.size for a in ws] != list(counts):
+                    raise ValueError("encode_snapshots: sample_weight and coordinates of a snapshot differ in length")
+                w = np.concatenate(ws) if T else np.empty((0,), np.float32)
+            x = np.concatenate(xs, axis=0) if T else np.empty((0, si), np.float32)
+            y = np.concatenate(ys, axis=0) if T else np.empty((0, so), np.float32)
+            kcounts = counts
+        z0 = e.p_to_lr(rows) if from_p else rows
+        if T == 0 or not counts.any():
+            return lm_encode(None, z0, counts, so, max_iter, tol)
+        samples = e.snapshot_samples(x, y, w, kcounts)
+        try:
+            return lm_encode(lambda lat: e.snapshot_normal_eq(lat, samples), z0, counts, so, max_iter, tol)
+        finally:
+            samples.free()
+
     # ---- training --------------------------------------------------------------------------------
     # Keras' compile(metrics=[...]): names / metric objects -> (history key, kind).  Unweighted (Keras applies sample_weight to
     # `weighted_metrics` only); the value of an epoch is the running mean over every sample the epoch saw, evaluated with the weights
