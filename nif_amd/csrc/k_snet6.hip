@@ -23,6 +23,7 @@
 // Built for: NIFMultiScale without resblocks, fp32 results, 49..64 units (NBL = 4), latent_dim 1, 1..4 hidden matrices, si, so <= 3.
 // Everything else keeps k_snet4 + k_gw_*.  nif_set_option("fuse_gw", 0) / NIF_FUSE_GW=0 switches back (A/B, tests).
 #include "k_fuse_dev.h"
+#include <type_traits>
 
 #define ZERO_T6(x) _Pragma("unroll") for (int b_ = 0; b_ < NBL; ++b_) { (x)[b_][0] = 0.f; (x)[b_][1] = 0.f; (x)[b_][2] = 0.f; (x)[b_][3] = 0.f; }
 
@@ -53,6 +54,43 @@ __device__ __forceinline__ void ring_load16(const float* __restrict__ slot, f32x
 #define S6_TL(id) do { } while (0)
 #define S6_TL_FLUSH() do { } while (0)
 #endif
+// ---- the vector blocks' helpers in the form hipcc turns into the fewest instructions (profiles/s6_adjoint_isa.md); each computes bit for
+// bit what the shared form (k_snet3_dev.h tag_cos, __shfl_xor) computes.  (split2 stays as it is: its residual x - hi is an FMA wherever x
+// is a product hipcc contracts, for the 12 of 16 elements it pairs -- another pairing is another result: profiles/s6_adjoint_diet.md) ------
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// tag_cos with the tag's shift and OR written over the whole f32x4: inside the adjoint layer loop the element-wise form reaches the
+// back end as <2 x i32> shl / or, which it splits AFTER its v_lshl_or_b32 patterns ran -- v_lshlrev + v_or per element where the same
+// source behind the loop gets one v_lshl_or_b32 (16 instructions per adjoint layer)
+template <int NBL>
+__device__ __forceinline__ void tag_cos4(const f32x4 (&sn)[NBL], f32x4 (&d)[NBL]) {
+#pragma unroll
+  for (int b = 0; b < NBL; ++b) {
+    f32x4 c;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const float s = sn[b][v];
+      c[v] = __builtin_amdgcn_sqrtf(__builtin_amdgcn_fmed3f(fmaf(-s, s, 1.0f), 0.0f, 1.0f));
+    }
+    d[b] = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, c) | (__builtin_bit_cast(u32x4, sn[b]) << 31));
+  }
+}
+// x (+) x[lane ^ 16] (+) x[lane ^ 32] on every lane -- the sum or maximum over the four 16-lane groups of a point.  v_permlane16_swap /
+// v_permlane32_swap of a value with itself leave the even and the odd rows (halves) in the two results: one VALU instruction and the
+// operation per step, where __shfl_xor is a ds_bpermute_b32 with six instructions of lane arithmetic in front and an LDS round trip
+// behind.  Both operations commute, so every lane gets the bits the shuffle form gave it
+__device__ __forceinline__ float s6_sum_groups(float x) {
+  auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  x = __uint_as_float(q[0]) + __uint_as_float(q[1]);
+  q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
+}
+__device__ __forceinline__ float s6_max_groups(float x) {
+  auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  x = fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
+  q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
+}
+
 struct S6Args {
   SNetArgs s;
   float* partial; long pstride;     // partial-gradient rows [gridDim.x][pstride] (the ShapeNet = hypernetwork columns of them)
@@ -515,27 +553,35 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
 
     f32x4 h[NBL], acc[NBL];
     // ---- first layer ----------------------------------------------------------------------------------------------------
+    // the plane rows of the first layer, bias + sum_dd x_dd w_dd: plane r into a_ (when BOTH), plane 0 into s_.  The coordinates are a
+    // ROLLED loop of si trips around the blocks (s6: with `if (dd < si)` inside the unrolled block loops hipcc made a basic block of
+    // every (plane, block, coordinate) -- 40 branches per evaluation and an exposed LDS round trip in front of every FMA pair, three
+    // evaluations per tile); every element's sum keeps its order: bias, x_0 w_0, x_1 w_1, x_2 w_2.  (Without BOTH a_ is not touched)
+    auto first_rows = [&](f32x4 (&a_)[NBL], f32x4 (&s_)[NBL], auto both) __attribute__((always_inline)) {
+      constexpr bool BOTH = decltype(both)::value;
+      const float* s1 = sm + r * nsm + 4 * g;
+      const float* s0 = sm + 4 * g;
+#pragma unroll
+      for (int b = 0; b < NBL; ++b) {
+        if (BOTH) a_[b] = *reinterpret_cast<const f32x4*>(s1 + o_b1 + 16 * b);
+        s_[b] = *reinterpret_cast<const f32x4*>(s0 + o_b1 + 16 * b);
+      }
+#pragma clang loop unroll(disable)
+      for (int dd = 0; dd < si; ++dd) {
+        const float x = xs[dd * 16];
+#pragma unroll
+        for (int b = 0; b < NBL; ++b) {
+          if (BOTH) a_[b] += x * *reinterpret_cast<const f32x4*>(s1 + o_w1 + dd * NP + 16 * b);
+          s_[b] += x * *reinterpret_cast<const f32x4*>(s0 + o_w1 + dd * NP + 16 * b);
+        }
+      }
+    };
     auto first_layer = [&](f32x4 (&out)[NBL]) __attribute__((always_inline)) {
-      f32x4 a_[NBL];
-      {
-        const float* s0 = sm + r * nsm + 4 * g;
+      f32x4 a_[NBL], s_[NBL];
+      first_rows(a_, s_, std::true_type{});
+      const float zt = zt_base[0];
 #pragma unroll
-        for (int b = 0; b < NBL; ++b) {
-          f32x4 s = *reinterpret_cast<const f32x4*>(s0 + o_b1 + 16 * b);
-          _Pragma("unroll") for (int dd = 0; dd < 3; ++dd) if (dd < si) s += xs[dd * 16] * *reinterpret_cast<const f32x4*>(s0 + o_w1 + dd * NP + 16 * b);
-          a_[b] = s;
-        }
-      }
-      {
-        const float zt = zt_base[0];
-        const float* s0 = sm + 4 * g;
-#pragma unroll
-        for (int b = 0; b < NBL; ++b) {
-          f32x4 s = *reinterpret_cast<const f32x4*>(s0 + o_b1 + 16 * b);
-          _Pragma("unroll") for (int dd = 0; dd < 3; ++dd) if (dd < si) s += xs[dd * 16] * *reinterpret_cast<const f32x4*>(s0 + o_w1 + dd * NP + 16 * b);
-          a_[b] += zt * s;
-        }
-      }
+      for (int b = 0; b < NBL; ++b) a_[b] += zt * s_[b];
       sine16_tag<NBL>(a_, out);
     };
     first_layer(h);
@@ -606,8 +652,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         bias = fmaf(zt, s0[o_bl + o], bias);
         if (k < r) sks[k * 64 + lane] = sk;
       }
-      part += __shfl_xor(part, 16);
-      part += __shfl_xor(part, 32);
+      part = s6_sum_groups(part);
       const float uo = part + bias;
       const float e = uo - ys[o * 16];
       NIF_LOSS_ACC(A.loss_kind, e, se, dfac)
@@ -663,7 +708,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
       // BIG: the chunk DMA of the layer's second step goes out at the TOP of its vector block instead of inside its first chunk step (an
       // LDS-DMA piece costs 25-60 cycles to issue in a VALU-only stretch, 100-185 inside a phase with matrix and LDS traffic: MI355X_MICROARCH.md)
       if (BIG) { cs_next(nbuf, true); dma_early = true; }
-      tag_cos<NBL>(hin, dnext);
+      tag_cos4<NBL>(hin, dnext);
 #pragma unroll
       for (int b = 0; b < NBL; ++b) ga[b] = dnext[b] * gh[b];
       {
@@ -686,8 +731,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
         float mx = 0.f;
 #pragma unroll
         for (int b = 0; b < NBL; ++b) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(ga[b][0]), fabsf(ga[b][1]))), fmaxf(fabsf(ga[b][2]), fabsf(ga[b][3])));
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mx = s6_max_groups(mx);
         const unsigned ef = (__float_as_uint(mx) >> 23) & 0xFFu;
         const unsigned sf = 268u - ef < 227u ? 268u - ef : 227u;
         ils = __uint_as_float((254u - sf) << 23);
@@ -762,21 +806,19 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
     // ---- first layer (the consumer waves take deposit 0 meanwhile) ------------------------------------------------------------
     {
       f32x4 ga[NBL];
-      tag_cos<NBL>(hin, dnext);
+      tag_cos4<NBL>(hin, dnext);
 #pragma unroll
       for (int b = 0; b < NBL; ++b) ga[b] = dnext[b] * gh[b];
       {
-        const float* s0 = sm + 4 * g;
+        f32x4 t[NBL];
+        first_rows(t, t, std::false_type{});
         float s = 0.f, s2 = 0.f;
 #pragma unroll
         for (int b = 0; b < NBL; ++b) {
-          f32x4 t = *reinterpret_cast<const f32x4*>(s0 + o_b1 + 16 * b);
-          _Pragma("unroll") for (int dd = 0; dd < 3; ++dd) if (dd < si) t += xs[dd * 16] * *reinterpret_cast<const f32x4*>(s0 + o_w1 + dd * NP + 16 * b);
-          s = fmaf(ga[b][0], t[0], s); s2 = fmaf(ga[b][1], t[1], s2); s = fmaf(ga[b][2], t[2], s); s2 = fmaf(ga[b][3], t[3], s2);
+          s = fmaf(ga[b][0], t[b][0], s); s2 = fmaf(ga[b][1], t[b][1], s2); s = fmaf(ga[b][2], t[b][2], s); s2 = fmaf(ga[b][3], t[b][3], s2);
         }
         float tot = dzs[lane] + (s + s2);
-        tot += __shfl_xor(tot, 16);
-        tot += __shfl_xor(tot, 32);
+        tot = s6_sum_groups(tot);
         if (active && g == 0) A.DZ[(tile32 * r) * 32 + poff] = tot;
       }
       bf16x8 b0[NCH], b1[NCH];

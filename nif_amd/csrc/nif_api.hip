@@ -1685,7 +1685,7 @@ static int ensure_pipe(nif_ctx* c, int nchunk) {
 static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const float* sw0, long off, long B, long Bg, int ns,
                       const int* seeds, const float* gt, float wj, hipStream_t sa_st, hipStream_t sb_st, hipStream_t pb_st,
                       float* partial, float* loss_partial, int* nloss_out, int chunk_idx, bool whole, SNetArgs* sa_out = nullptr,
-                      const SobPlan* sp = nullptr) {
+                      const SobPlan* sp = nullptr, bool* pb_aside = nullptr) {
   int rc;
   const int ncol = c->pi + c->si;
   const long ntiles = (B + 31) / 32, t0 = off / 32;       // off is a multiple of 32 points
@@ -1712,6 +1712,11 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
                         snet6_rows(sa) == rows_for(c, ntiles);
   if (fused_gw) nloss = snet6_rows(sa);
   *nloss_out = nloss;
+  // the ParameterNet adjoint goes aside (pb_st) to run NEXT TO the ShapeNet's weight-gradient reductions.  The fused step has none: the
+  // adjoint stays behind k_snet6 on its stream -- no event, no stream wait, launch order = execution order.  *pb_aside tells the
+  // caller whether there is a second stream to join
+  if (fused_gw) pb_st = sb_st;
+  if (pb_aside) *pb_aside = pb_st != sa_st;
   {   // mixed_bfloat16: the hidden layers' dL/da stash rows in bf16 when both the producer of this step (k_snet4<PR> / k_sobw<PR>)
       // and the consumer (k_gw_lds) have the form -- half the bytes of that operand on either side
     const int nbl = snet3_nbl(c->n);
@@ -1883,10 +1888,11 @@ static int loss_grad_core(nif_ctx* c, const float* xin, const float* y, const fl
     // the ShapeNet (both only need the fused kernel's outputs); joined in front of the row reduction
     const bool side = c->opt_side_pnet && B >= 65536;
     if (side) { rc = ensure_pipe(c, 1); if (rc) return rc; }
+    bool aside = false;
     rc = step_chunk(c, xin, y, sw, 0, B, Bg, ns, seeds, gt, wj, c->st, c->st, side ? c->st2 : c->st, c->partial, c->loss_partial,
-                    &nloss, 0, true, &sae, sp);
+                    &nloss, 0, true, &sae, sp, &aside);
     if (rc) return rc;
-    if (side) {
+    if (aside) {
       HIPCHK(hipEventRecord(c->ev_done, c->st2));
       HIPCHK(hipStreamWaitEvent(c->st, c->ev_done, 0));
     }
