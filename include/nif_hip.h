@@ -450,6 +450,9 @@ int nif_f64_grad_read(nif_ctx* ctx, double* loss_out_or_null, double* grad_host_
  * one-launch small-batch step, the row reduction deferred to nif_adam_step_dev (which then runs it fused with the update: the
  * [grad | loss] buffer is complete after ANY other call of this library on the context -- nif_grad_dev included -- and after the
  * update; a caller that reads the buffer through a pointer it cached earlier, without such a call, sets "fuse_tail" to 0).
+ * "s6_shape_generic" (default 0, no environment variable): 1 runs the fused-gradient kernel's run-time-shape form k_snet6<4, PR, 0, 0>
+ * on a net with one coordinate and one output too, instead of the form that knows both counts at compile time (k_snet6<4, PR, 1, 1>);
+ * the results are the same bits, nets of other shapes run the run-time form either way.
  * "snapshot_image_bytes": device bytes of combined per-snapshot nets that nif_forward_snapshots* holds at once (it walks the snapshots
  * in chunks of that many; 0, the default: 256 MiB; at least one snapshot per chunk; the results do not depend on it).
  * Weight averaging (Keras' use_ema; restated from Keras 2.11's documentation, unpinned by TensorFlow) is context state set here:

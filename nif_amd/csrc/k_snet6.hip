@@ -112,8 +112,14 @@ constexpr int s6_ring(int NBL) { return 16 * NBL * 16; }
 // untouched: the deposits stay bf16 (hi, lo) pairs of the fp32 rows and the weight-gradient sums three products, i.e. the policy's
 // weight gradients here are those of fp32 stash rows (the tests emulate it with stash_bf16 = False).  (r4's first policy form also cut the consumers
 // to one MFMA per tile and hipcc answered with 327 spilled registers; with the consumer code unchanged the allocation holds.)
-template <int NBL, int PR = 0>
+// SI, SO: the net's coordinate and output counts at compile time, 0 = run time (A.si, A.so in 1..3).  <1, 1> is the one other form
+// instantiated -- every 1-D field fit with one output, the benchmark's net among them: the last layer's output loop, the first layer's
+// coordinate loop, the consumers' `so > 1` / `si > 1` branches, the input rows' clamps and the mean over the outputs are gone from it
+// (x / 1.0f is x), every LDS offset made of o or dd is an immediate; every element's sum keeps its order.  nh, the sample weights, the
+// loss kind and the tile's activity stay run-time values (profiles/s6_shape_spec.md)
+template <int NBL, int PR = 0, int SI = 0, int SO = 0>
 __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
+  static_assert((SI == 0 && SO == 0) || (SI == 1 && SO == 1), "k_snet6: run-time shape or the 1 / 1 form");
   extern __shared__ __attribute__((aligned(256))) char smem6[];
   const SNetArgs& A = F.s;
   constexpr int NT = 512, WAVES = S6_WAVES, r = 1;             // producer threads / waves (= tiles per round); 8 consumer waves behind them
@@ -145,7 +151,7 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
   constexpr int NVL = 5, NVF = 8, WVLT = NVL * 64, WVFT = NVF * 64;
   const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, p = lane & 15, g = lane >> 4;
-  const int n = A.n, nh = A.nh, si = A.si, so = A.so;
+  const int n = A.n, nh = A.nh, si = SI ? SI : A.si, so = SO ? SO : A.so;
   const long nt16 = 2 * ((A.B + 31) / 32);
   const long ngroups = (nt16 + WAVES - 1) / WAVES;
 
@@ -488,13 +494,13 @@ __global__ __launch_bounds__(1024, 4) void k_snet6(S6Args F) {
     if (ptn >= A.B) ptn = A.B - 1;
     float* dst = inp + set * NI;
     {     // rows 0..3: x_g (g < 3, clamped to the net's coordinates) | z
-      const int c = g < si ? g : si - 1;
+      const int c = SI == 1 ? 0 : (g < si ? g : si - 1);
       const float* src = g < 3 ? A.xin + ptn * A.ncol + A.col0 + c : A.Z + (tile32n * r) * 32 + poffn;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
     }
     {     // rows 4..7: y_g (g < 3, clamped) | sample weight (or a target where there is none: never read then)
-      const int c = g < so ? g : so - 1;
+      const int c = SO == 1 ? 0 : (g < so ? g : so - 1);
       const float* src = (g < 3 || !A.sw) ? A.y + ptn * so + c : A.sw + ptn;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(dst + 4 * 16), 4, 0, 0);
@@ -886,18 +892,27 @@ int snet6_rows(const SNetArgs& a) { return (int)s6_workgroups(a.B); }
 // floats of the h rings of a launch over B points (the kernel writes them into the ShapeNet stash): EVERY producer wave of a workgroup
 // writes its slice, active or not
 long snet6_ring_floats(long B, int nh) { return s6_workgroups(B) * S6_WAVES * nh * s6_ring(4); }
-int launch_snet6(const SNetArgs& a, float* partial, long pstride, hipStream_t st) {
+// shape_generic (nif_set_option "s6_shape_generic"): the run-time si / so form on a one-coordinate, one-output net too
+int launch_snet6(const SNetArgs& a, float* partial, long pstride, hipStream_t st, bool shape_generic) {
   const int nblk = snet6_rows(a);
   S6Args f; f.s = a; f.partial = partial; f.pstride = pstride;
   const size_t shm = snet6_shmem(a, 4);
-#define S6L(PR_)                                                                                                  \
-  {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)k_snet6<4, PR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-    hipLaunchKernelGGL((k_snet6<4, PR_>), dim3(nblk), dim3(1024), shm, st, f);                                    \
+#define S6L(...)                                                                                                          \
+  {                                                                                                                       \
+    (void)hipFuncSetAttribute((const void*)k_snet6<4, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
+    hipLaunchKernelGGL((k_snet6<4, __VA_ARGS__>), dim3(nblk), dim3(1024), shm, st, f);                                    \
   }
-  if (a.prec == 2) { f.s.WF4 = a.WF4h; f.s.WB4 = a.WB4h; S6L(2) }      // the policy's compact plane set (k_pack16b mode 2 / 1)
-  else if (a.prec == 1) { f.s.WF4 = a.WF4h; f.s.WB4 = a.WB4h; S6L(1) }
-  else { f.s.WF4 = a.WF4x; f.s.WB4 = a.WB4x; S6L(0) }      // the exact-product half planes (k_pack16b mode 3)
+  const bool s11 = a.si == 1 && a.so == 1 && !shape_generic;
+  if (a.prec == 2) {      // the policy's compact plane set (k_pack16b mode 2 / 1)
+    f.s.WF4 = a.WF4h; f.s.WB4 = a.WB4h;
+    if (s11) S6L(2, 1, 1) else S6L(2)
+  } else if (a.prec == 1) {
+    f.s.WF4 = a.WF4h; f.s.WB4 = a.WB4h;
+    if (s11) S6L(1, 1, 1) else S6L(1)
+  } else {      // the exact-product half planes (k_pack16b mode 3)
+    f.s.WF4 = a.WF4x; f.s.WB4 = a.WB4x;
+    if (s11) S6L(0, 1, 1) else S6L(0)
+  }
 #undef S6L
   return nblk;
 }

@@ -1741,7 +1741,7 @@ static int step_chunk(nif_ctx* c, const float* xin0, const float* y0, const floa
       if (sp && sp->any_par) { spar.ZT = c->zt_par; spar.DZT = c->dzt_par; }
       launch_sob(sa, true, ns, seeds, gt, wj, c->dring, nullptr, false, sa_st, sp ? &spar : nullptr);
     }
-    else if (fused_gw) launch_snet6(sa, partial, c->pstride, sa_st);
+    else if (fused_gw) launch_snet6(sa, partial, c->pstride, sa_st, c->opt_s6_shape_generic);
     else if (c->use_snet4) { if (launch_snet4(sa, true, false, sa_st) < 0) return fail(NIF_ERR_STATE, "internal: no k_snet4 form for this net (SIREN planes not packed as half pairs)"); }
     else if (c->use_snet3) launch_snet3(sa, true, false, nullptr, sa_st);
     else launch_snet(sa, c->NB, true, sa_st);
@@ -2839,6 +2839,7 @@ extern "C" int nif_device_pci_bus_id(int32_t dev, char* out, int32_t cap) {
 extern "C" int nif_set_option(nif_ctx* c, const char* key, int32_t value) {
   if (!c || !key) return fail(NIF_ERR_INVALID, "null");
   if (strcmp(key, "fuse_gw") == 0) { c->opt_fuse_gw = value != 0; return NIF_OK; }   // 0: k_snet4 + k_gw_* instead of the fused-gradient kernel
+  if (strcmp(key, "s6_shape_generic") == 0) { c->opt_s6_shape_generic = value != 0; return NIF_OK; }   // 1: k_snet6<.., 0, 0> on a si = so = 1 net too (A/B, tests)
   if (strcmp(key, "fuse_tail") == 0) { c->opt_fuse_tail = value != 0; return NIF_OK; }     // 0: the row reduction runs inside nif_loss_grad_dev (A/B, tests)
   if (strcmp(key, "small_step") == 0) { c->opt_small_step = value != 0; return NIF_OK; }   // 0: small batches on the tile kernels too (A/B, tests)
   if (strcmp(key, "fp32_mfma") == 0) {      // 1: every product on the f32-input MFMAs (k_snet3) instead of the bf16 splits

@@ -176,6 +176,7 @@ struct nif_ctx {
   bool tail_pending = false; int tail_rows = 0, tail_nloss = 0; bool opt_fuse_tail = true;
   bool opt_small_step = true;      // nif_set_option("small_step"): batches <= NIF_SMALL_MAX_B points of a net k_small takes run on it (one launch for loss + gradient); default from NIF_SMALL_STEP
   bool opt_fuse_gw = true;         // nif_set_option("fuse_gw"): ShapeNet weight gradients inside the training kernel (k_snet6) where it has the shape; default from NIF_FUSE_GW
+  bool opt_s6_shape_generic = false;      // nif_set_option("s6_shape_generic"): k_snet6's run-time si / so form on a one-coordinate, one-output net too (A/B, tests)
   // the invalidations, each the one statement of what it clears
   void planes_stale() { packed = false; packed32 = false; packed_p32 = false; }      // theta (or what the planes are packed for) changed
   void theta_stepped() { planes_stale(); reg_applied = false; }      // an optimizer step or replay: the regulariser term belongs to ONE gradient

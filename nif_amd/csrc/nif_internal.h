@@ -213,7 +213,7 @@ bool sob_writes_da_bf16(const SNetArgs& a, int ns, bool any_par);   // same for 
 bool snet6_supported(const SNetArgs& a);
 int snet6_rows(const SNetArgs& a);
 long snet6_ring_floats(long B, int nh);
-int launch_snet6(const SNetArgs& a, float* partial, long pstride, hipStream_t st);
+int launch_snet6(const SNetArgs& a, float* partial, long pstride, hipStream_t st, bool shape_generic = false);
 int snet4_nsm_ll(int si, int sop, int nh, int n, int sou, int rl);
 // Sobolev step (k_sob.hip): primal + tangents w.r.t. `ns` coordinate seeds, loss mse(u,y) + wj*mse(du/dx,gt), adjoint
 long sob_ring_floats_per_wave(int n, int nh);

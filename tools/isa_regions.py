@@ -7,7 +7,8 @@ every instruction of the code object is attributed to the k_snet6.hip line of it
 --inlines on a -gline-tables-only build: the line tables change no instruction), and the lines to regions by the section comments
 of the source.  A basic block that holds fp64 instructions is the large-argument sine fallback: counted apart as "cold".
 
-usage: tools/isa_regions.py [--kernel MANGLED] [--lines] [source.hip]      (default: nif_amd/csrc/k_snet6.hip, k_snet6<4,0>)"""
+usage: tools/isa_regions.py [--kernel MANGLED] [--lines] [source.hip]      (default: nif_amd/csrc/k_snet6.hip, k_snet6<4,0,0,0>;
+the one-coordinate, one-output form: --kernel _Z7k_snet6ILi4ELi0ELi1ELi1EEv6S6Args)"""
 import os
 import re
 import subprocess
@@ -78,7 +79,7 @@ def regions_of(src):
 
 
 def main():
-    kern = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else "_Z7k_snet6ILi4ELi0EEv6S6Args"
+    kern = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else "_Z7k_snet6ILi4ELi0ELi0ELi0EEv6S6Args"
     args = [a for a in sys.argv[1:] if not a.startswith("--") and a != kern]
     src = os.path.abspath(args[0]) if args else os.path.join(ROOT, "nif_amd", "csrc", "k_snet6.hip")
     regs = regions_of(src)
