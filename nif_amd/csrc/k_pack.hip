@@ -100,26 +100,40 @@ __global__ void k_pack_phi(const float* __restrict__ theta, long w_off, int n, i
   }
 }
 // the fp32 planes: one loop for both tile sizes.  T32 = false: 16-row blocks (k_snet3, k_jac, k_sob); true: 32-row blocks (k_snet, k_pnet)
+// element idx of the forward (fwd) or adjoint image of all r + 1 planes
+template <bool T32>
+__device__ __forceinline__ float pack_f32_elem(const float* __restrict__ theta, const MatRef& m, int NBI, int NBO, long idx, bool fwd) {
+  const long per_plane = (long)NBI * NBO * (T32 ? 1024 : 256);
+  const int k = (int)(idx / per_plane);
+  const long rem = idx - (long)k * per_plane;
+  const int lane = (rem >> 2) & 63, blk = (int)(rem >> (T32 ? 10 : 8));
+  const int v = T32 ? 4 * (int)((rem >> 8) & 3) + (int)(rem & 3) : (int)(rem & 3);
+  const int kk = T32 ? fmap(v, lane >> 5) : 4 * (lane >> 4) + v, rr = T32 ? lane & 31 : lane & 15, W = T32 ? 32 : 16;
+  if (fwd) {  // forward plane: blk = ob*NBI + ib
+    const int ob = blk / NBI, ib = blk % NBI;
+    return pack_theta(theta, m, k, W * ib + kk, W * ob + rr, 1.0f);
+  }
+  // adjoint plane: blk = ib*NBO + ob   (output blocks of U are the in-feature blocks)
+  const int ib = blk / NBO, ob = blk % NBO;
+  return pack_theta(theta, m, k, W * ib + rr, W * ob + kk, 1.0f);
+}
 template <bool T32>
 __device__ __forceinline__ void pack_f32(const float* __restrict__ theta, const MatRef& m, int NBI, int NBO, float* __restrict__ WF,
                                          float* __restrict__ WB) {
-  const long per_plane = (long)NBI * NBO * (T32 ? 1024 : 256);
-  const long total = per_plane * (m.r + 1);
+  const long total = (long)NBI * NBO * (T32 ? 1024 : 256) * (m.r + 1);
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(idx / per_plane);
-    const long rem = idx - (long)k * per_plane;
-    const int lane = (rem >> 2) & 63, blk = (int)(rem >> (T32 ? 10 : 8));
-    const int v = T32 ? 4 * (int)((rem >> 8) & 3) + (int)(rem & 3) : (int)(rem & 3);
-    const int kk = T32 ? fmap(v, lane >> 5) : 4 * (lane >> 4) + v, rr = T32 ? lane & 31 : lane & 15, W = T32 ? 32 : 16;
-    {  // forward plane: blk = ob*NBI + ib
-      const int ob = blk / NBI, ib = blk % NBI;
-      WF[idx] = pack_theta(theta, m, k, W * ib + kk, W * ob + rr, 1.0f);
-    }
-    {  // adjoint plane: blk = ib*NBO + ob   (output blocks of U are the in-feature blocks)
-      const int ib = blk / NBO, ob = blk % NBO;
-      WB[idx] = pack_theta(theta, m, k, W * ib + rr, W * ob + kk, 1.0f);
-    }
+    WF[idx] = pack_f32_elem<T32>(theta, m, NBI, NBO, idx, true);
+    WB[idx] = pack_f32_elem<T32>(theta, m, NBI, NBO, idx, false);
   }
+}
+// The forward tiles16 image alone of matrix m of gridDim.y parameter vectors `tstride` floats apart (the combined nets of k_jac_snap:
+// slot vectors w_t, m dense): entry y -> WF + y dstride floats
+__global__ void k_pack16_fwd_batch(const float* __restrict__ theta, MatRef m, long tstride, int NBL, float* __restrict__ WF, long dstride) {
+  const float* th = theta + (long)blockIdx.y * tstride;
+  float* wf = WF + (long)blockIdx.y * dstride;
+  const long total = plane_elems(PLANES_T16, PLANE_FWD, NBL) * (m.r + 1);
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x)
+    wf[idx] = pack_f32_elem<false>(th, m, NBL, NBL, idx, true);
 }
 __global__ void k_pack16(const float* __restrict__ theta, MatRef m, int NBL, float* __restrict__ WF, float* __restrict__ WB) {
   pack_f32<false>(theta, m, NBL, NBL, WF, WB);
@@ -160,6 +174,11 @@ void launch_pack_phi(const float* theta, long w_off, int n, int sop, void* WPF, 
 void launch_pack16(const float* theta, const MatRef& m, int NBL, f32x4* WF, f32x4* WB, hipStream_t st) {
   const int grid = pack_grid(plane_elems(PLANES_T16, PLANE_FWD, NBL) * (m.r + 1), 2048);
   hipLaunchKernelGGL(k_pack16, dim3(grid), dim3(256), 0, st, theta, m, NBL, (float*)WF, (float*)WB);
+}
+void launch_pack16_fwd_batch(const float* theta, const MatRef& m, long tstride, int nbatch, int NBL, f32x4* WF, long dstride_f32x4,
+                             hipStream_t st) {
+  const int grid = pack_grid(plane_elems(PLANES_T16, PLANE_FWD, NBL) * (m.r + 1), 64);
+  hipLaunchKernelGGL(k_pack16_fwd_batch, dim3(grid, nbatch), dim3(256), 0, st, theta, m, tstride, NBL, (float*)WF, dstride_f32x4 * 4);
 }
 void launch_pack(const float* theta, const MatRef& m, int NBI, int NBO, f32x4* WF, f32x4* WB, hipStream_t st) {
   const int grid = pack_grid((long)NBI * NBO * 1024 * (m.r + 1), 2048);

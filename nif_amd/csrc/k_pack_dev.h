@@ -113,4 +113,7 @@ struct PackJob {
 void launch_pack_planes(const PackJob& job, hipStream_t st);
 void launch_pack_phi(const float* theta, long w_off, int n, int sop, void* WPF, void* WPB, hipStream_t st);
 void launch_pack16(const float* theta, const MatRef& m, int NBL, f32x4* WF, f32x4* WB, hipStream_t st);
+// forward image alone of matrix m of `nbatch` (<= 65535) parameter vectors `tstride` floats apart: entry y -> WF + y dstride_f32x4
+void launch_pack16_fwd_batch(const float* theta, const MatRef& m, long tstride, int nbatch, int NBL, f32x4* WF, long dstride_f32x4,
+                             hipStream_t st);
 void launch_pack(const float* theta, const MatRef& m, int NBI, int NBO, f32x4* WF, f32x4* WB, hipStream_t st);

@@ -9,6 +9,8 @@
 //                  table and / or the latent tiles Z [tile][r][32] with every point of snapshot t carrying latent t.  No host table.
 //   k_phi_dot:     last-layer class on a shared mesh: u[t][m][s] = sum_c phi[m][s][c] a[t][c] + bias[s], phi of a 32-point tile held
 //                  in LDS and reused over all T snapshots (one ShapeNet pass for the whole call).
+//   k_phi_dot_d2:  the same with the ShapeNet's first- and second-order tangents: u, du/dx, d2u/dx2 of nif_snapshot_derivatives* (whose
+//                  hypernetwork route is k_jac<.., SNAP>, k_jac_snap.hip); k_jac_gather takes the rows y_idx of that route's order 1.
 #include "k_snet4_dev.h"
 
 // the snapshot of point i: shared mesh i / M; ragged the last t with offsets[t] <= i (empty snapshots own no point)
@@ -74,6 +76,78 @@ bool phi_dot_supported(int r, int so) { return (long)r * so * 32 * sizeof(float)
 void launch_phi_dot(const float* PHI, const float* a, const float* bias, long T, long M, int r, int so, float* u, hipStream_t st) {
   const long ntiles = (M + 31) / 32;
   hipLaunchKernelGGL(k_phi_dot, dim3((unsigned)ntiles), dim3(256), sizeof(float) * (size_t)r * so * 32, st, PHI, a, bias, T, M, r, so, u);
+}
+
+// ---- snapshot-wise derivatives (include/nif_hip_snapderiv.h) ------------------------------------------------------------
+// order 1 on the combined path: rows y_idx of k_jac<.., SNAP>'s [n][so][nx] -> [n][ny][nx] (order 2 gathers with k_hess_gather)
+__global__ __launch_bounds__(256) void k_jac_gather(const float* __restrict__ fj, long n, int so, int nx, HessIdx I, float* __restrict__ dydx) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;      // (point, i)
+  if (e >= n * I.ny) return;
+  const long a = e / I.ny; const int i = (int)(e - a * I.ny);
+  const long src = a * so + I.y_idx[i];
+  for (int j = 0; j < nx; ++j) dydx[e * nx + j] = fj[src * nx + j];
+}
+void launch_jac_gather(const float* fj, long n, int so, int nx, const HessIdx& I, float* dydx, hipStream_t st) {
+  hipLaunchKernelGGL(k_jac_gather, dim3((unsigned)((n * I.ny + 255) / 256)), dim3(256), 0, st, fj, n, so, nx, I, dydx);
+}
+
+// Last-layer class on a shared mesh: k_phi_dot with the ShapeNet's tangents.  One workgroup per 32-point tile of the mesh: the tile's
+// rows [phi | phi' | phi''] of the second-order tangent kernel (point-major, as hessian_core leaves them: f0 [M][so r], fj [M][so r][nx],
+// fh [M][so r][nx][nx]; fh null: order 1) go to LDS once, one row per point at an odd stride, then the 8 point groups of the workgroup
+// walk the snapshots t = g, g + 8, ...  Every sum runs in k_ll_hess' order (u: bias first; then c = 0 .. r - 1 by fma), so a
+// snapshot's values are the ones the point-wise epilogue gives for the same tangents and coefficients.
+__device__ __host__ inline int phi_dot_d2_stride(int r, int so, int nx, bool order2) { return (so * r * (1 + nx + (order2 ? nx * nx : 0))) | 1; }
+__global__ __launch_bounds__(256) void k_phi_dot_d2(const float* __restrict__ f0, const float* __restrict__ fj, const float* __restrict__ fh,
+                                                    const float* __restrict__ a, const float* __restrict__ bias, long T, long M, int r, int so,
+                                                    int nx, HessIdx I, float* __restrict__ u, float* __restrict__ dudx, float* __restrict__ d2) {
+  extern __shared__ float rows[];
+  const long m0 = (long)blockIdx.x * 32;
+  const int sop = so * r, e1 = sop * nx, e2 = fh ? e1 * nx : 0;
+  const int stride = phi_dot_d2_stride(r, so, nx, fh != nullptr);
+  const int np = M - m0 < 32 ? (int)(M - m0) : 32;
+  for (int idx = threadIdx.x; idx < np * sop; idx += 256) { const int p = idx / sop; rows[p * stride + (idx - p * sop)] = f0[m0 * sop + idx]; }
+  for (int idx = threadIdx.x; idx < np * e1; idx += 256) { const int p = idx / e1; rows[p * stride + sop + (idx - p * e1)] = fj[m0 * e1 + idx]; }
+  for (int idx = threadIdx.x; idx < np * e2; idx += 256) { const int p = idx / e2; rows[p * stride + sop + e1 + (idx - p * e2)] = fh[m0 * e2 + idx]; }
+  __syncthreads();
+  const int p = threadIdx.x & 31;
+  if (p >= np) return;
+  const float* g0 = rows + p * stride;
+  const float* gj = g0 + sop;
+  const float* gh = gj + e1;
+  const int ny = I.ny;
+  for (long t = threadIdx.x >> 5; t < T; t += 8) {
+    const float* at = a + t * r;
+    const long pt = t * M + m0 + p;
+    for (int o = 0; o < so; ++o) {
+      float acc = bias[o];
+      for (int c = 0; c < r; ++c) acc = fmaf(g0[o * r + c], at[c], acc);
+      u[pt * so + o] = acc;
+    }
+    for (int i = 0; i < ny; ++i) {
+      const int src = I.y_idx[i] * r;
+      float* dy = dudx + (pt * ny + i) * nx;
+      for (int j = 0; j < nx; ++j) {
+        float t1 = 0.f;
+        for (int c = 0; c < r; ++c) t1 = fmaf(gj[(src + c) * nx + j], at[c], t1);
+        dy[j] = t1;
+        if (fh) {
+          float* h = d2 + ((pt * ny + i) * nx + j) * nx;
+          for (int k = 0; k < nx; ++k) {
+            float t2 = 0.f;
+            for (int c = 0; c < r; ++c) t2 = fmaf(gh[((src + c) * nx + j) * nx + k], at[c], t2);
+            h[k] = t2;
+          }
+        }
+      }
+    }
+  }
+}
+bool phi_dot_d2_supported(int r, int so, int nx, bool order2) { return (long)phi_dot_d2_stride(r, so, nx, order2) * 32 * sizeof(float) <= 64 * 1024; }
+void launch_phi_dot_d2(const float* f0, const float* fj, const float* fh, const float* a, const float* bias, long T, long M, int r,
+                       int so, int nx, const HessIdx& I, float* u, float* dudx, float* d2, hipStream_t st) {
+  const size_t shm = sizeof(float) * 32 * (size_t)phi_dot_d2_stride(r, so, nx, fh != nullptr);
+  if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_phi_dot_d2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  hipLaunchKernelGGL(k_phi_dot_d2, dim3((unsigned)((M + 31) / 32)), dim3(256), shm, st, f0, fj, fh, a, bias, T, M, r, so, nx, I, u, dudx, d2);
 }
 
 // ---- the combined-net forward: launch_snet4's grid and instantiation choice for the SNAP forms -------------------------------------

@@ -14,6 +14,7 @@
 
 #include "nif_ctx.h"
 #include "../../include/nif_hip_snapshots.h"
+#include "../../include/nif_hip_snapderiv.h"
 #include "../../include/nif_hip_encode.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
@@ -1147,18 +1148,22 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
 // x_idx: one launch of the second-order tangent kernel per column pair (j <= k), then the gather of the rows y_idx -- and, for the
 // last-layer class, the contraction with the ParameterNet output -- ON THE DEVICE (r3; r2 did both in host loops).  Everything is
 // enqueued on the context's stream; the outputs are device pointers.
+// The snapshot entries (nif_snapshot_derivatives*) run it behind latents of their own: with_pnet false, c->Z already holds every point's
+// latent, xin_dev is [B][si] (coordinate columns only in x_idx, still numbered from pi_dim).  ll_tangents_only (last-layer class):
+// stop behind the ShapeNet tangents phi, phi', phi'' of the B points in c->d_d, c->d_b, c->d_c; the caller contracts them.
 static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32_t* y_idx, int32_t ny, const int32_t* x_idx,
-                        int32_t nx, float* y_dev, float* dydx_dev, float* d2_dev) {
+                        int32_t nx, float* y_dev, float* dydx_dev, float* d2_dev, bool with_pnet = true, bool ll_tangents_only = false) {
   bool anyp = false;
   for (int j = 0; j < nx; ++j) anyp = anyp || x_idx[j] < c->pi;
+  if (anyp && !with_pnet) return fail(NIF_ERR_INVALID, "internal: parameter columns need the ParameterNet");
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_capacity(c, B, false); if (rc) return rc;
-  const int ncol = c->pi + c->si;
+  const int ncol = with_pnet ? c->pi + c->si : c->si, col0 = with_pnet ? c->pi : 0;
   const long ntl = (B + 31) / 32;
   HessIdx I; I.ny = ny;
   for (int i = 0; i < 16; ++i) I.y_idx[i] = i < ny ? y_idx[i] : 0;
   PNetArgs pa; fill_pnet(c, pa, xin_dev, B);
-  launch_pnet(pa, c->NSTB, false, c->st);
+  if (with_pnet) launch_pnet(pa, c->NSTB, false, c->st);
   // parameter columns: z' = dz/dp of every parameter column once (k_pjac, forward mode), z'' per pair of them (k_pjac2)
   std::vector<int> xc, xp;                         // positions (in x_idx) of the coordinate / parameter columns
   for (int j = 0; j < nx; ++j) (x_idx[j] >= c->pi ? xc : xp).push_back(j);
@@ -1184,12 +1189,14 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
     rc = stage(c, c->d_b, nullptr, B * sop * nxc); if (rc) return rc;
     rc = stage(c, c->d_c, nullptr, B * sop * nxc * nxc); if (rc) return rc;
     SNetArgs sa; rc = fill_snet_ll_sob(c, sa, xin_dev, B, true); if (rc) return rc;
+    sa.ncol = ncol; sa.col0 = col0;
     if (xc.empty()) { sa.u_out = c->d_d; launch_hess(sa, 0, 0, 0, 0, 1, c->d_b, c->d_c, c->st); }     // phi alone
     for (size_t j = 0; j < xc.size(); ++j)
       for (size_t k = j; k < xc.size(); ++k) {
         sa.u_out = (j == 0 && k == 0) ? c->d_d : nullptr;
         launch_hess(sa, x_idx[xc[j]] - c->pi, x_idx[xc[k]] - c->pi, (int)j, (int)k, nxc, c->d_b, c->d_c, c->st);
       }
+    if (ll_tangents_only) { HIPCHK(hipGetLastError()); return NIF_OK; }
     // a'_j = z'_j last_w and a''_jk = z''_jk last_w: one k_pjac2 launch per parameter pair, ONE k_through_lw over all of them
     const int nvec = np_ + np_ * np_;
     float* ap = nullptr;
@@ -1224,7 +1231,7 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
   if (!c->jac_ok) return fail(NIF_ERR_INVALID, "HessianLayer: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
   rc = stage(c, c->d_b, nullptr, B * c->so * nx); if (rc) return rc;
   rc = stage(c, c->d_c, nullptr, B * c->so * nx * nx); if (rc) return rc;
-  SNetArgs sa; fill_snet(c, sa, xin_dev, ncol, c->pi, B);
+  SNetArgs sa; fill_snet(c, sa, xin_dev, ncol, col0, B);
   std::vector<int> ppos(nx, -1);                    // position among the parameter columns of x_idx
   for (int j = 0; j < np_; ++j) ppos[xp[j]] = j;
   for (int j = 0; j < nx; ++j)
@@ -1276,6 +1283,202 @@ extern "C" int nif_hessian(nif_ctx* c, const float* xin, int64_t B, const int32_
     if (e != hipSuccess) rc = fail(NIF_ERR_HIP, hipGetErrorString(e));
   } else (void)hipStreamSynchronize(c->st);
   return rc;
+}
+
+// ---- snapshot-wise derivatives (include/nif_hip_snapderiv.h) ---------------------------------------------------------
+static int sd_check(const nif_snapderiv_args* a, long* n) {
+  if (!a) return fail(NIF_ERR_INVALID, "null");
+  if (a->abi_version != NIF_SNAPDERIV_ABI_VERSION)
+    return fail(NIF_ERR_INVALID, "nif_snapderiv_args: abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(NIF_SNAPDERIV_ABI_VERSION));
+  if (a->reserved0 || a->reserved1 || a->reserved2 || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
+    return fail(NIF_ERR_INVALID, "nif_snapderiv_args: reserved fields must be zero");
+  const nif_ctx* c = a->ctx;
+  const int64_t* off = a->offsets_host;
+  if (!c || !a->rows || !a->y_idx || !a->x_idx || a->T <= 0 || a->ny <= 0 || a->nx <= 0 || (off ? off[0] != 0 : a->M < 0))
+    return fail(NIF_ERR_INVALID, "bad argument");
+  if (a->order != 1 && a->order != 2) return fail(NIF_ERR_INVALID, "nif_snapshot_derivatives: order must be 1 or 2");
+  if (off) for (int64_t t = 0; t < a->T; ++t) if (off[t + 1] < off[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
+  *n = off ? (long)off[a->T] : (long)(a->T * a->M);
+  if (*n > 0 && (!a->x || !a->u || !a->dudx || (a->order == 2 && !a->d2udx2))) return fail(NIF_ERR_INVALID, "bad argument");
+  if (a->ny > 16) return fail(NIF_ERR_INVALID, "y_index: at most 16 entries");
+  for (int i = 0; i < a->ny; ++i)
+    if (a->y_idx[i] < 0 || a->y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
+  for (int j = 0; j < a->nx; ++j) {
+    if (a->x_idx[j] < 0 || a->x_idx[j] >= c->si) return fail(NIF_ERR_INVALID, "x_index out of range (0 <= j < si_dim: coordinates only)");
+    for (int k = 0; k < j; ++k) if (a->x_idx[k] == a->x_idx[j]) return fail(NIF_ERR_INVALID, "x_index: an index is repeated");
+  }
+  if (a->nx > 16) return fail(NIF_ERR_INVALID, "HessianLayer: at most 16 coordinate and 16 parameter columns in x_index");
+  { const int rcw = wide_refused(c, "nif_snapshot_derivatives"); if (rcw) return rcw; }
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_snapshot_derivatives: not capturable (inside nif_graph_begin / nif_graph_end)");
+  return NIF_OK;
+}
+// one snapshot of the combined path: its slot vector and the forward f32 planes of its hidden matrices (the format k_jac reads)
+static long sd_plane_f32x4(const nif_ctx* c) { return plane_f32x4(PLANES_T16, snet3_nbl(c->n)); }
+static long sd_chunk(const nif_ctx* c, long T) {
+  const long per = (long)sizeof(float) * c->po + (long)c->nh * sd_plane_f32x4(c) * (long)sizeof(f32x4);
+  long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
+  if (tc > 65535) tc = 65535;
+  if (tc > T) tc = T;
+  return tc < 1 ? 1 : tc;
+}
+static long sd_combined_floats(const nif_ctx* c, long tc) { return snap_r4(tc * c->po) + tc * c->nh * sd_plane_f32x4(c) * 4 + 4; }
+// Hypernetwork classes on k_jac_snap.  Per chunk of snapshots: the slot vectors w_t in fp32 from theta, their hidden matrices packed
+// from w_t (one launch per hidden matrix over the chunk), then one launch per seed group over the chunk.  The kernels leave every
+// output row [n][so][nx] / [n][so][nx][nx] in c->d_b / c->d_c; the rows y_idx are gathered behind the last chunk.
+static int sd_combined(nif_ctx* c, const nif_snapderiv_args* a, float* buf, long tc_max, const float* lat, const long* off_dev, long n,
+                       const HessIdx& I) {
+  const long T = a->T, M = a->M;
+  const int64_t* off_host = a->offsets_host;
+  const int nx = a->nx, so = c->so, NBL = snet3_nbl(c->n);
+  const bool hess = a->order == 2;
+  int rc = stage(c, c->d_b, nullptr, n * so * nx); if (rc) return rc;
+  if (hess) { rc = stage(c, c->d_c, nullptr, n * so * nx * nx); if (rc) return rc; }
+  float* w = buf;
+  f32x4* WF = reinterpret_cast<f32x4*>(w + snap_r4(tc_max * c->po));
+  const long plane_s = sd_plane_f32x4(c);
+  for (long t0 = 0; t0 < T; t0 += tc_max) {
+    const long tc = T - t0 < tc_max ? T - t0 : tc_max;
+    long mmax = M, n_pts = tc * M;
+    if (off_host) {
+      mmax = 0; n_pts = off_host[t0 + tc] - off_host[t0];
+      for (long t = t0; t < t0 + tc; ++t) if (off_host[t + 1] - off_host[t] > mmax) mmax = off_host[t + 1] - off_host[t];
+    }
+    if (n_pts == 0) continue;
+    {
+      ProfScope p_(c, NIF_PROF_PACK);
+      launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
+      for (int j = 0; j < c->nh; ++j)
+        launch_pack16_fwd_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + (long)j * plane_s, c->nh * plane_s, c->st);
+    }
+    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, mmax);
+    sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr; sa.WF = WF; sa.WB = nullptr;
+    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * plane_s; sa.snap_T = (int)tc;
+    // (ragged: the kernel rebases by the call's own offsets; shared mesh: by t M inside the chunk)
+    const long pb = off_dev ? 0 : t0 * M;
+    float* u = a->u + pb * so;
+    float* fj = c->d_b + pb * so * nx;
+    float* fh = hess ? c->d_c + pb * so * nx * nx : nullptr;
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    if (hess) {
+      for (int j = 0; j < nx; ++j)
+        for (int k = j; k < nx; ++k) {
+          sa.u_out = (j == 0 && k == 0) ? u : nullptr;
+          launch_hess_snap(sa, tc, a->x_idx[j], a->x_idx[k], j, k, nx, fj, fh, c->st);
+        }
+    } else {
+      for (int x0 = 0; x0 < nx; x0 += 3) {
+        int seeds[3] = {0, 0, 0};
+        const int ns = nx - x0 < 3 ? nx - x0 : 3;
+        for (int d = 0; d < ns; ++d) seeds[d] = a->x_idx[x0 + d];
+        sa.u_out = x0 == 0 ? u : nullptr;
+        launch_jac_snap(sa, tc, ns, seeds, nx, x0, fj, c->st);
+      }
+    }
+  }
+  if (hess) launch_hess_gather(c->d_b, c->d_c, n, so, nx, I, a->dudx, a->d2udx2, c->st);
+  else launch_jac_gather(c->d_b, n, so, nx, I, a->dudx, c->st);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_snapshot_derivatives_dev(const nif_snapderiv_args* a) {
+  long n = 0;
+  int rc = sd_check(a, &n); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  rc = ensure_packed(c); if (rc) return rc;
+  const bool lat_in = a->rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
+  if (lat_in && c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
+    return fail(NIF_ERR_INVALID, std::string("nif_snapshot_derivatives: latents are not built for the ") +
+                                     (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
+                                     " policy (the tangent kernels run exact products, the policy's ParameterNet does not; pass p)");
+  if (!ll && !c->jac_ok) return fail(NIF_ERR_INVALID, "HessianLayer: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
+  if (n == 0) return NIF_OK;
+  const long T = a->T, M = a->M;
+  const int64_t* offsets = a->offsets_host;
+  const int nx = a->nx, ny = a->ny, si = c->si;
+  const bool hess = a->order == 2;
+  HessIdx I; I.ny = ny;
+  for (int i = 0; i < 16; ++i) I.y_idx[i] = i < ny ? a->y_idx[i] : 0;
+  int32_t xi[16];      // HessianLayer's numbering of the same columns
+  for (int j = 0; j < nx; ++j) xi[j] = c->pi + a->x_idx[j];
+  // the routes: the point-wise layers on the device-built [p_t | x] table; k_jac_snap on combined nets; the last-layer
+  // class' tangents once per shared mesh; else the point-wise kernels behind latent tiles built on the device
+  const bool pointwise = snap_pointwise(c) && !lat_in;
+  const bool combined = !ll && !snap_pointwise(c);
+  const bool phi_dot = ll && !offsets && !snap_pointwise(c) && phi_dot_d2_supported(c->r, c->so, nx, hess);
+  const long tc_max = combined ? sd_chunk(c, T) : 0;
+  // one buffer, one growth: [offsets (ragged) | latent rows (from p) | the table, or the combined nets of one chunk of snapshots]
+  const long off_f = offsets ? 2 * (T + 1) : 0, lat_f = (pointwise || lat_in) ? 0 : T * c->r;
+  const bool table = pointwise || (!offsets && !phi_dot && !combined);
+  const int tcol = pointwise ? c->pi + si : si;
+  const long tab_f = table ? n * tcol : (combined ? sd_combined_floats(c, tc_max) : 0);
+  rc = c->snap.reserve(c, snap_r4(off_f + lat_f) + tab_f + 1); if (rc) return rc;
+  rc = ensure_capacity(c, combined ? T : (phi_dot ? (T > M ? T : M) : (n > T ? n : T)), false); if (rc) return rc;
+  float* d2 = a->d2udx2;
+  if (!hess && !combined) {      // these routes run the second-order kernels at either order
+    rc = c->sd_tmp.reserve(c, (phi_dot ? 0 : n * ny * nx * nx) + 1); if (rc) return rc;
+    d2 = phi_dot ? nullptr : c->sd_tmp.p;
+  }
+  SnapArgs sn; memset(&sn, 0, sizeof(sn));
+  sn.T = T; sn.M = M; sn.n = n; sn.pi = pointwise ? c->pi : 0; sn.si = si; sn.r = c->r; sn.x = a->x;
+  if (offsets) {      // (host memory of the caller: consumed before this returns)
+    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
+    HIPCHK(hipMemcpyAsync(c->snap.p, offsets, sizeof(int64_t) * (size_t)(T + 1), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
+  }
+  if (table) sn.table = c->snap + snap_r4(off_f + lat_f);
+  if (pointwise) {
+    sn.p = a->rows;
+    launch_snap_expand(sn, c->st);
+    return hessian_core(c, sn.table, n, a->y_idx, ny, xi, nx, a->u, a->dudx, d2);
+  }
+  const float* lat = a->rows;
+  if (!lat_in) {      // the ParameterNet over the T rows, its output back as rows [T][r]
+    PNetArgs pa; fill_pnet(c, pa, a->rows, T); pa.ncol = c->pi;
+    { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st); }
+    launch_tiles_to_rows(c->Z, T, c->r, c->snap + off_f, c->st);
+    lat = c->snap + off_f;
+  }
+  if (combined) return sd_combined(c, a, c->snap + snap_r4(off_f + lat_f), tc_max, lat, sn.offsets, n, I);
+  if (phi_dot) {      // phi, phi', phi'' of the mesh once, contracted with every snapshot's coefficients
+    rc = hessian_core(c, a->x, M, a->y_idx, ny, xi, nx, nullptr, nullptr, nullptr, false, true); if (rc) return rc;
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    launch_phi_dot_d2(c->d_d, c->d_b, hess ? c->d_c.p : nullptr, lat, c->theta + c->ll_bias, T, M, c->r, c->so, nx, I, a->u, a->dudx, d2, c->st);
+    HIPCHK(hipGetLastError());
+    return NIF_OK;
+  }
+  sn.lat = lat; sn.Z = c->Z;
+  launch_snap_expand(sn, c->st);
+  return hessian_core(c, table ? sn.table : a->x, n, a->y_idx, ny, xi, nx, a->u, a->dudx, d2, false);
+}
+extern "C" int nif_snapshot_derivatives(const nif_snapderiv_args* a) {
+  long n = 0;
+  int rc = sd_check(a, &n); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  const long T = a->T;
+  const long f_rows = snap_r4(T * (a->rows_are_latent ? c->r : c->pi)), f_x = snap_r4((a->offsets_host ? n : (long)a->M) * c->si);
+  const long f_u = snap_r4(n * c->so), f_d = snap_r4(n * a->ny * a->nx), f_h = a->order == 2 ? f_d * a->nx : 0;
+  rc = c->sd_io.reserve(c, f_rows + f_x + f_u + f_d + f_h + 4); if (rc) return rc;
+  nif_snapderiv_args d = *a;
+  float* q = c->sd_io.p;
+  d.rows = q; q += f_rows;
+  d.x = q; q += f_x;
+  d.u = q; q += f_u;
+  d.dudx = q; q += f_d;
+  d.d2udx2 = q;
+  HIPCHK(hipMemcpyAsync(const_cast<float*>(d.rows), a->rows, sizeof(float) * (size_t)(T * (a->rows_are_latent ? c->r : c->pi)), hipMemcpyHostToDevice, c->st));
+  if (n > 0) HIPCHK(hipMemcpyAsync(const_cast<float*>(d.x), a->x, sizeof(float) * (size_t)((a->offsets_host ? n : (long)a->M) * c->si), hipMemcpyHostToDevice, c->st));
+  rc = nif_snapshot_derivatives_dev(&d); if (rc) return rc;
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(a->u, d.u, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(a->dudx, d.dudx, sizeof(float) * (size_t)(n * a->ny * a->nx), hipMemcpyDeviceToHost, c->st));
+    if (a->order == 2) HIPCHK(hipMemcpyAsync(a->d2udx2, d.d2udx2, sizeof(float) * (size_t)(n * a->ny * a->nx * a->nx), hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
 }
 
 extern "C" int nif_pnet_latent(nif_ctx* c, const float* p, int64_t B, float* lr) {

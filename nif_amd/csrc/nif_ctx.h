@@ -157,6 +157,9 @@ struct nif_ctx {
   // [Z | unit pattern | xpad | dydx | u] of one chunk of snapshots (bounded by the same budget), rebuilt by every call; enc_S stages
   // the host-pointer entry's result
   DevBuf<float> enc; DevBuf<double> enc_S;
+  // snapshot-wise derivatives (nif_snapshot_derivatives*): sd_tmp takes the second-order output of an order-1 call on the routes that
+  // run the second-order kernels anyway; sd_io stages the host-pointer entry's [rows | x | u | dudx | d2udx2]
+  DevBuf<float> sd_tmp, sd_io;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

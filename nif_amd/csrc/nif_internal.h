@@ -127,7 +127,8 @@ struct SNetArgs {
   int h_ph16;                             // prec == 1, 128-wide plain SIREN training: the hidden matrices' INPUT stash rows as 16-bit phases (k_snet3_dev.h;
                                           // the readers are k_snet4's own adjoint sweep and k_gw8<R, true, true>: snet4_writes_h_ph16)
   int wg_cap;                             // k_snet4: at most this many workgroups (0 = fill the device); the chunk pipeline leaves room for stream B
-  // snapshot-wise inference (k_snap.hip; read by the SNAP instantiations of k_snet4 alone).  Workgroup (x, y) is tile-group slot x of
+  // snapshot-wise inference (k_snap.hip; read by the SNAP instantiations of k_snet4 and of k_jac, which takes WF where k_snet4 takes
+  // WF4, alone).  Workgroup (x, y) is tile-group slot x of
   // snapshot y: its points are snap_off[y] .. snap_off[y + 1] of xin / u_out (snap_off null: a mesh of snap_M points in xin shared by all,
   // u_out rows y snap_M ..), its net the dense r = 0 net whose slot vector is theta + off_bh + y po, whose packed hidden planes are
   // WF4 + y snap_wstride 16-byte units and whose plane scales are wscale[(j snap_T + y) 2 ..] for hidden matrix j
@@ -244,6 +245,11 @@ void launch_jac(const SNetArgs& a, int ns, const int* seeds, const float* const*
 // zdd = d2z/dp_j dp_k when both are parameter columns)
 void launch_hess(const SNetArgs& a, int seed_j, int seed_k, int hj, int hk, int nx_total, float* dydx, float* d2ydx2, hipStream_t st,
                  const float* zd_j = nullptr, const float* zd_k = nullptr, const float* zdd = nullptr);
+// the snapshot forms (k_jac<.., SNAP>, k_jac_snap.hip): T <= 65535 combined r = 0 nets in one launch, a.B = the longest snapshot's points,
+// a.snap_off / snap_M / snap_wstride (f32x4 units between the snapshots' plane sets) set, a.theta the slot vectors [T][po]
+void launch_jac_snap(const SNetArgs& a, long T, int ns, const int* seeds, int nx_total, int x0, float* dydx, hipStream_t st);
+void launch_hess_snap(const SNetArgs& a, long T, int seed_j, int seed_k, int hj, int hk, int nx_total, float* dydx, float* d2ydx2,
+                      hipStream_t st);
 void launch_mlp_jac(const PNetArgs& a, int NB, int seed, float* ZD, hipStream_t st);
 void launch_ll_jac_out(const float* PHI, const float* Z, const float* PHID, const float* ZD, long B, int r, int so,
                        int nx_total, int xcol, float* dydx, hipStream_t st);
@@ -461,6 +467,13 @@ struct SnapArgs {
   float* table; float* Z;
 };
 void launch_snap_expand(const SnapArgs& a, hipStream_t st);
+// rows y_idx of the tangent kernels' [n][so][nx] result -> dydx [n][ny][nx] (order 1 of nif_snapshot_derivatives*; order 2: launch_hess_gather)
+void launch_jac_gather(const float* fj, long n, int so, int nx, const HessIdx& I, float* dydx, hipStream_t st);
+// last-layer class on a shared mesh (k_phi_dot_d2): u [T][M][so], dudx [T][M][ny][nx] and, fh set, d2 [T][M][ny][nx][nx] from the
+// ShapeNet tangents f0 [M][so r], fj [M][so r][nx], fh [M][so r][nx][nx] and the coefficient vectors a [T][r], in k_ll_hess' order
+bool phi_dot_d2_supported(int r, int so, int nx, bool order2);
+void launch_phi_dot_d2(const float* f0, const float* fj, const float* fh, const float* a, const float* bias, long T, long M, int r,
+                       int so, int nx, const HessIdx& I, float* u, float* dudx, float* d2, hipStream_t st);
 // last-layer class, shared mesh: u [T][M][so] = Dot(PHI [tiles][so r][32], a [T][r]) + bias [so]
 bool phi_dot_supported(int r, int so);
 void launch_phi_dot(const float* PHI, const float* a, const float* bias, long T, long M, int r, int so, float* u, hipStream_t st);

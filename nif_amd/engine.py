@@ -319,6 +319,64 @@ class Engine(object):
         finally:
             d_x.free()
 
+    # ---- snapshot-wise derivatives (include/nif_hip_snapderiv.h; Model.predict_snapshot_derivatives plans the chunks) ----------
+    def _snapshot_derivs(self, rows, is_latent, d_x, x_off, offsets, m, n, y_index, x_index, order):
+        self._not_capturing("nif_snapshot_derivatives")
+        s = self.spec
+        rows = self._rows(rows, s.pi_hidden if is_latent else s.pi_dim, "latent" if is_latent else "parameter inputs")
+        yi = np.ascontiguousarray(list(y_index), dtype=np.int32)
+        xi = np.ascontiguousarray(list(x_index), dtype=np.int32)
+        ny, nx = yi.size, xi.size
+        u = np.empty((n, s.so_dim), dtype=np.float32)
+        d = np.empty((n, ny, nx), dtype=np.float32)
+        h = np.empty((n, ny, nx, nx), dtype=np.float32) if order == 2 else None
+        if not n:
+            return (u, d) if h is None else (u, d, h)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        d_r, d_o = DeviceArray(self, rows.size), DeviceArray(self, u.size + d.size + (0 if h is None else h.size))
+        try:
+            d_r.upload(rows)
+            a = _lib.nif_snapderiv_args()
+            a.abi_version, a.order, a.ctx = _lib.NIF_SNAPDERIV_ABI_VERSION, int(order), self.ctx
+            a.rows, a.rows_are_latent, a.T = d_r.at(0), 1 if is_latent else 0, rows.shape[0]
+            a.x, a.M = d_x.at(x_off), int(m)
+            a.offsets_host = None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64))
+            a.y_idx, a.ny = yi.ctypes.data_as(C.POINTER(C.c_int32)), ny
+            a.x_idx, a.nx = xi.ctypes.data_as(C.POINTER(C.c_int32)), nx
+            a.u, a.dudx = d_o.at(0), d_o.at(u.size)
+            a.d2udx2 = None if h is None else d_o.at(u.size + d.size)
+            check(self.lib.nif_snapshot_derivatives_dev(C.byref(a)))
+            check(self.lib.nif_d2h(self.ctx, ptr(u), d_o.at(0), u.size * 4))
+            check(self.lib.nif_d2h(self.ctx, ptr(d), d_o.at(u.size), d.size * 4))
+            if h is not None:
+                check(self.lib.nif_d2h(self.ctx, ptr(h), d_o.at(u.size + d.size), h.size * 4))
+        finally:
+            d_r.free(); d_o.free()
+        return (u, d) if h is None else (u, d, h)
+
+    def snapshot_derivatives(self, rows, is_latent, mesh, lo, hi, y_index, x_index, order):
+        """rows [T, pi] (or [T, r] latents) on the points lo .. hi of a snapshot_mesh handle -> (u [T, hi - lo, so],
+        dudx [T, hi - lo, ny, nx][, d2udx2 [T, hi - lo, ny, nx, nx]]); x_index counts coordinates from 0"""
+        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
+        outs = self._snapshot_derivs(rows, is_latent, mesh, int(lo) * self.spec.si_dim, None, m, t * m, y_index, x_index, order)
+        return tuple(o.reshape((t, m) + o.shape[1:]) for o in outs)
+
+    def snapshot_derivatives_ragged(self, rows, is_latent, xs, y_index, x_index, order):
+        """rows [T, .] and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> the same outputs [sum M_t, ...], snapshot after snapshot"""
+        self._not_capturing("nif_snapshot_derivatives")
+        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
+        if len(xs) != int(np.shape(rows)[0]):
+            raise ValueError("snapshot_derivatives_ragged: %d rows for %d meshes" % (int(np.shape(rows)[0]), len(xs)))
+        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
+        n = int(offsets[-1])
+        d_x = DeviceArray(self, max(n, 1) * self.spec.si_dim)
+        try:
+            if n:
+                d_x.upload(np.concatenate(xs, axis=0))
+            return self._snapshot_derivs(rows, is_latent, d_x, 0, offsets, 0, n, y_index, x_index, order)
+        finally:
+            d_x.free()
+
     # ---- encoding (include/nif_hip_encode.h; nif_amd/encode.py runs the Levenberg-Marquardt loop around these two) ----------
     def snapshot_samples(self, x, y, w=None, counts=None):
         """The samples of T snapshots on the device, uploaded once for all snapshot_normal_eq calls of one encode.  counts None: a

@@ -264,33 +264,43 @@ class Model(object):
         the ShapeNet once per mesh chunk.  Device staging is bounded by _SNAPSHOT_CHUNK_BYTES (snapshots, and the points of a long
         snapshot, go through in chunks; a shared mesh is uploaded once); the result does not depend on it nor on batch_size, which
         only raises the points per chunk."""
+        s = self._owner._spec
+        e = self._engine
+        per_point = 4 * (s.pi_dim + s.si_dim + s.so_dim + s.pi_hidden * (1 + (s.so_dim if s.connectivity == "last_layer" else 0)))
+        out = self._snapshot_run("predict_snapshots", x, p, latent, batch_size, per_point, [(s.so_dim,)],
+                                 lambda *a: (e.forward_snapshots(*a),), lambda *a: (e.forward_snapshots_ragged(*a),))
+        return out[0]
+
+    def _snapshot_run(self, who, x, p, latent, batch_size, per_point, tails, shared_call, ragged_call):
+        """What the snapshot-wise calls share: the checks of x, p | latent, and the chunk plan.  tails: the trailing shape of every
+        output; shared_call(rows, is_latent, mesh, lo, hi) -> arrays [T', hi - lo, *tail]; ragged_call(rows, is_latent, xs) -> arrays
+        [sum M_t, *tail].  Returns a tuple of arrays [T, M, *tail] (shared mesh) or of lists of [M_t, *tail]."""
         if self._role != "full":
-            raise ValueError("predict_snapshots exists on the full model only (%s is a sub-model view)" % self._role)
+            raise ValueError("%s exists on the full model only (%s is a sub-model view)" % (who, self._role))
         if (p is None) == (latent is None):
-            raise ValueError("predict_snapshots: exactly one of p [T, pi] and latent [T, r]")
+            raise ValueError("%s: exactly one of p [T, pi] and latent [T, r]" % who)
         s = self._owner._spec
         is_latent = latent is not None
         width = s.pi_hidden if is_latent else s.pi_dim
         rows = np.asarray(latent if is_latent else p, dtype=np.float32)
         if rows.ndim != 2 or rows.shape[1] != width:
-            raise ValueError("predict_snapshots: expected %s of shape (T, %d), got %s" % ("latent" if is_latent else "p", width, rows.shape))
-        T, so = rows.shape[0], s.so_dim
+            raise ValueError("%s: expected %s of shape (T, %d), got %s" % (who, "latent" if is_latent else "p", width, rows.shape))
+        T = rows.shape[0]
 
         def mesh_of(a):
             a = np.asarray(a, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != s.si_dim:
-                raise ValueError("predict_snapshots: expected coordinates of shape (M, %d), got %s" % (s.si_dim, a.shape))
+                raise ValueError("%s: expected coordinates of shape (M, %d), got %s" % (who, s.si_dim, a.shape))
             return a
 
-        per_point = 4 * (s.pi_dim + s.si_dim + so + s.pi_hidden * (1 + (so if s.connectivity == "last_layer" else 0)))
         pts = max(1, int(self._SNAPSHOT_CHUNK_BYTES) // per_point, int(batch_size or 0))
         e = self._engine
         if not isinstance(x, (list, tuple)):
             x = mesh_of(x)
             M = x.shape[0]
-            out = np.empty((T, M, so), dtype=np.float32)
+            outs = tuple(np.empty((T, M) + tuple(tail), dtype=np.float32) for tail in tails)
             if T == 0 or M == 0:
-                return out
+                return outs
             mc = min(M, pts)
             tc = max(1, pts // mc)
             mesh = e.snapshot_mesh(x)
@@ -298,22 +308,24 @@ class Model(object):
                 for lo in range(0, M, mc):
                     hi = min(M, lo + mc)
                     for t0 in range(0, T, tc):
-                        out[t0:t0 + tc, lo:hi] = e.forward_snapshots(rows[t0:t0 + tc], is_latent, mesh, lo, hi)
+                        for out, part in zip(outs, shared_call(rows[t0:t0 + tc], is_latent, mesh, lo, hi)):
+                            out[t0:t0 + tc, lo:hi] = part
             finally:
                 mesh.free()
-            return out
+            return outs
         xs = [mesh_of(a) for a in x]
         if len(xs) != T:
-            raise ValueError("predict_snapshots: %d meshes for %d snapshots" % (len(xs), T))
-        outs = [np.empty((a.shape[0], so), dtype=np.float32) for a in xs]
+            raise ValueError("%s: %d meshes for %d snapshots" % (who, len(xs), T))
+        outs = tuple([np.empty((a.shape[0],) + tuple(tail), dtype=np.float32) for a in xs] for tail in tails)
         group, held = [], 0
 
         def flush():
-            u = e.forward_snapshots_ragged(rows[[t for t, _, _ in group]], is_latent, [xs[t][lo:hi] for t, lo, hi in group])
-            at = 0
-            for t, lo, hi in group:
-                outs[t][lo:hi] = u[at:at + hi - lo]
-                at += hi - lo
+            parts = ragged_call(rows[[t for t, _, _ in group]], is_latent, [xs[t][lo:hi] for t, lo, hi in group])
+            for out, u in zip(outs, parts):
+                at = 0
+                for t, lo, hi in group:
+                    out[t][lo:hi] = u[at:at + hi - lo]
+                    at += hi - lo
 
         for t, a in enumerate(xs):
             for lo in range(0, a.shape[0], pts):
@@ -326,6 +338,40 @@ class Model(object):
         if group:
             flush()
         return outs
+
+    def predict_snapshot_derivatives(self, x, p=None, latent=None, x_index=None, y_index=None, order=1, batch_size=None):
+        """predict_snapshots with the field's first (order=1) and second (order=2) derivatives in the coordinates: x, p | latent and
+        batch_size as there.  x_index: distinct coordinate indices 0 <= j < si (JacobianLayer's x_index minus pi_dim; default: every
+        coordinate); y_index: outputs, any order, repeats allowed, at most 16 (default: every output).  Shared mesh: returns
+        (u [T, M, so], dudx [T, M, ny, nx]) and for order=2 also d2udx2 [T, M, ny, nx, nx]; a list / tuple of meshes: a tuple of lists
+        of [M_t, ...] arrays.  For snapshot t they are what HessianLayer(model, y_index, [pi + j for j in x_index]) returns on
+        hstack([tile(p[t], M_t), x_t]), without that table: the ParameterNet runs once per snapshot and the hypernetwork classes run
+        one set of hidden products per layer and tangent stream on the snapshot's combined matrices.  Device staging is
+        bounded by _SNAPSHOT_CHUNK_BYTES as in predict_snapshots; the result does not depend on it."""
+        who = "predict_snapshot_derivatives"
+        s = self._owner._spec
+        if self._role != "full":
+            raise ValueError("%s exists on the full model only (%s is a sub-model view)" % (who, self._role))
+        if order not in (1, 2):
+            raise ValueError("%s: order must be 1 or 2, got %r" % (who, order))
+        xi = list(range(s.si_dim)) if x_index is None else [int(j) for j in x_index]
+        yi = list(range(s.so_dim)) if y_index is None else [int(i) for i in y_index]
+        if not xi or any(j < 0 or j >= s.si_dim for j in xi):
+            raise ValueError("%s: x_index lists coordinates 0 <= j < %d (parameter columns are not built), got %r" % (who, s.si_dim, xi))
+        if len(set(xi)) != len(xi):
+            raise ValueError("%s: x_index repeats an index: %r" % (who, xi))
+        if not yi or len(yi) > 16 or any(i < 0 or i >= s.so_dim for i in yi):
+            raise ValueError("%s: y_index lists 1 to 16 outputs 0 <= i < %d, got %r" % (who, s.so_dim, yi))
+        ny, nx = len(yi), len(xi)
+        tails = [(s.so_dim,), (ny, nx)] + ([(ny, nx, nx)] if order == 2 else [])
+        e = self._engine
+        # what a point holds on the device: the forward's operands, its result rows and the kernels' rows over every output
+        # (so of them; last-layer class: the so * r rows of phi)
+        krows = s.so_dim * (s.pi_hidden if s.connectivity == "last_layer" else 1)
+        per_point = 4 * (s.pi_dim + s.si_dim + s.so_dim + s.pi_hidden + krows + (ny + krows) * (nx + nx * nx))
+        return self._snapshot_run(who, x, p, latent, batch_size, per_point, tails,
+                                  lambda rows, il, mesh, lo, hi: e.snapshot_derivatives(rows, il, mesh, lo, hi, yi, xi, order),
+                                  lambda rows, il, xs: e.snapshot_derivatives_ragged(rows, il, xs, yi, xi, order))
 
     def encode_snapshots(self, x, u, latent0=None, p0=None, sample_weight=None, max_iter=20, tol=1e-8):
         """The inverse of predict_snapshots(x, latent=...): for each of T snapshots the latent whose field fits the samples u best in
