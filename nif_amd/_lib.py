@@ -235,6 +235,26 @@ SNAPDERIV_SIGNATURES = {
 }
 
 
+NIF_SNAPPARAM_ABI_VERSION = 1
+
+
+class nif_snapparam_args(C.Structure):
+    """include/nif_hip_snapparam.h, field for field"""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("rows_are_latent", C.c_int32), ("ctx", _CTX), ("rows", _VP), ("drows", _VP), ("nd", C.c_int32),
+        ("np", C.c_int32), ("p_idx", C.POINTER(C.c_int32)), ("T", C.c_int64), ("x", _VP), ("offsets_host", C.POINTER(C.c_int64)),
+        ("M", C.c_int64), ("y_idx", C.POINTER(C.c_int32)), ("ny", C.c_int32), ("reserved0", C.c_int32), ("u", _VP), ("dudp", _VP),
+        ("reserved", C.c_int64 * 4),
+    ]
+
+
+# include/nif_hip_snapparam.h, one to one (bound by load() with the tables above)
+SNAPPARAM_SIGNATURES = {
+    "nif_snapshot_param_derivatives": (C.c_int, [C.POINTER(nif_snapparam_args)]),
+    "nif_snapshot_param_derivatives_dev": (C.c_int, [C.POINTER(nif_snapparam_args)]),
+}
+
+
 def load():
     """dlopen libnif_hip.so and bind every symbol of include/nif_hip.h.  Raises if it is absent."""
     global _lib
@@ -245,7 +265,7 @@ def load():
             "libnif_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-    for name, (res, args) in list(SIGNATURES.items()) + list(SNAPSHOT_SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(SNAPDERIV_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SNAPSHOT_SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(SNAPDERIV_SIGNATURES.items()) + list(SNAPPARAM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

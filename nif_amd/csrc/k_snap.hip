@@ -11,6 +11,9 @@
 //                  in LDS and reused over all T snapshots (one ShapeNet pass for the whole call).
 //   k_phi_dot_d2:  the same with the ShapeNet's first- and second-order tangents: u, du/dx, d2u/dx2 of nif_snapshot_derivatives* (whose
 //                  hypernetwork route is k_jac<.., SNAP>, k_jac_snap.hip); k_jac_gather takes the rows y_idx of that route's order 1.
+//   k_dlatent_to_w, k_dir_rows, k_snapparam_gather: the small kernels of nif_snapshot_param_derivatives*  -- the tangent slot
+//                  vectors of a combined net along latent directions (the bias-free companion of k_latent_to_w; the route's tangent
+//                  kernel is k_jac_wt, k_jac_wtan.hip), the directions as direction-major rows, and the last-layer route's gather.
 #include "k_snet4_dev.h"
 
 // the snapshot of point i: shared mesh i / M; ragged the last t with offsets[t] <= i (empty snapshots own no point)
@@ -148,6 +151,48 @@ void launch_phi_dot_d2(const float* f0, const float* fj, const float* fh, const 
   const size_t shm = sizeof(float) * 32 * (size_t)phi_dot_d2_stride(r, so, nx, fh != nullptr);
   if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_phi_dot_d2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   hipLaunchKernelGGL(k_phi_dot_d2, dim3((unsigned)((M + 31) / 32)), dim3(256), shm, st, f0, fj, fh, a, bias, T, M, r, so, nx, I, u, dudx, d2);
+}
+
+// ---- snapshot-wise parameter derivatives (include/nif_hip_snapparam.h) --------------------------------------------------
+// The bias-free companion of k_latent_to_w: wd[a][s] = sum_k d[a][k] Wh[k][s] for `rows` direction rows d [rows][r] -- the tangent
+// slot vector of a combined net along a latent direction (same slot layout as w_t; the hyper bias does not move).  The sum runs
+// k = 0 .. r - 1 by fma from 0: scaling a direction by a power of two scales its row exactly.
+__global__ __launch_bounds__(256) void k_dlatent_to_w(const float* __restrict__ theta, long off_Wh, int r, long po, const float* __restrict__ d,
+                                                      float* __restrict__ wd) {
+  const long s = (long)blockIdx.x * 256 + threadIdx.x;
+  if (s >= po) return;
+  const float* dr = d + (long)blockIdx.y * r;
+  float acc = 0.f;
+  for (int k = 0; k < r; ++k) acc = fmaf(dr[k], theta[off_Wh + (long)k * po + s], acc);
+  wd[(long)blockIdx.y * po + s] = acc;
+}
+void launch_dlatent_to_w(const float* theta, long off_Wh, int r, long po, const float* d, long rows, float* wd, hipStream_t st) {
+  hipLaunchKernelGGL(k_dlatent_to_w, dim3((unsigned)((po + 255) / 256), (unsigned)rows), dim3(256), 0, st, theta, off_Wh, r, po, d, wd);
+}
+// the caller's directions [T][nd][r] -> direction-major rows [nd][T][r] (the layout the ParameterNet's tangents arrive in)
+__global__ __launch_bounds__(256) void k_dir_rows(const float* __restrict__ drows, long T, int nd, int r, float* __restrict__ D) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= T * nd * r) return;
+  const int k = (int)(e % r);
+  const long td = e / r;
+  const int d = (int)(td % nd);
+  const long t = td / nd;
+  D[((long)d * T + t) * r + k] = drows[e];
+}
+void launch_dir_rows(const float* drows, long T, int nd, int r, float* D, hipStream_t st) {
+  hipLaunchKernelGGL(k_dir_rows, dim3((unsigned)((T * nd * r + 255) / 256)), dim3(256), 0, st, drows, T, nd, r, D);
+}
+// last-layer class on a shared mesh: k_phi_dot's result over the direction-major tangent coefficient rows, f [nd][T][M][so], ->
+// rows y_idx of dudp [T][M][ny][nd]
+__global__ __launch_bounds__(256) void k_snapparam_gather(const float* __restrict__ f, long T, long M, int so, int nd, HessIdx I,
+                                                          float* __restrict__ dudp) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;      // (snapshot, point, i)
+  if (e >= T * M * I.ny) return;
+  const long a = e / I.ny; const int i = (int)(e - a * I.ny);
+  for (int d = 0; d < nd; ++d) dudp[e * nd + d] = f[((long)d * T * M + a) * so + I.y_idx[i]];
+}
+void launch_snapparam_gather(const float* f, long T, long M, int so, int nd, const HessIdx& I, float* dudp, hipStream_t st) {
+  hipLaunchKernelGGL(k_snapparam_gather, dim3((unsigned)((T * M * I.ny + 255) / 256)), dim3(256), 0, st, f, T, M, so, nd, I, dudp);
 }
 
 // ---- the combined-net forward: launch_snet4's grid and instantiation choice for the SNAP forms -------------------------------------

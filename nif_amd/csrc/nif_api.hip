@@ -15,6 +15,7 @@
 #include "nif_ctx.h"
 #include "../../include/nif_hip_snapshots.h"
 #include "../../include/nif_hip_snapderiv.h"
+#include "../../include/nif_hip_snapparam.h"
 #include "../../include/nif_hip_encode.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
@@ -1070,17 +1071,9 @@ extern "C" int nif_snapshot_normal_eq(const nif_encode_args* a) {
   return NIF_OK;
 }
 
-extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32_t* y_idx, int32_t ny,
-                            const int32_t* x_idx, int32_t nx, float* y_out, float* dydx_out) {
-  if (!c || !xin || !y_idx || !x_idx || !y_out || !dydx_out || B <= 0 || ny <= 0 || nx <= 0)
-    return fail(NIF_ERR_INVALID, "bad argument");
-  for (int i = 0; i < ny; ++i)
-    if (y_idx[i] < 0 || y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
-  for (int j = 0; j < nx; ++j)
-    if (x_idx[j] < 0 || x_idx[j] >= c->pi + c->si) return fail(NIF_ERR_INVALID, "x_index out of range");
-  { const int rcw = wide_refused(c, "JacobianLayer"); if (rcw) return rcw; }
-  NIF_ENTER(c, NIF_FLUSH_TAIL)
-  HIPCHK(hipStreamSynchronize(c->st));
+// The device core of nif_jacobian: xin_dev [B][pi + si] -> y [B][so] in c->d_d and dy/dx of EVERY output, [B][so][nx], in c->d_b, all
+// enqueued on the context's stream.  The snapshot entries (nif_snapshot_param_derivatives*) run it on a table built on the device.
+static int jacobian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32_t* x_idx, int32_t nx) {
   int rc = ensure_packed(c); if (rc) return rc;
   rc = ensure_packed32(c); if (rc) return rc;
   rc = ensure_packed_p32(c); if (rc) return rc;
@@ -1089,17 +1082,16 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
   rc = ensure_capacity(c, B, false); if (rc) return rc;
   const long ntiles = (B + 31) / 32;
   const int ncol = c->pi + c->si;
-  rc = stage(c, c->d_a, xin, B * ncol); if (rc) return rc;
   rc = stage(c, c->d_d, nullptr, B * c->so); if (rc) return rc;
   rc = stage(c, c->d_b, nullptr, B * c->so * nx); if (rc) return rc;
   // tangent buffers: dz/dp for up to 3 parameter seeds (and d phi / dx for the last-layer class)
   const long zd_sz = ntiles * 32 * (long)c->r * (ll ? c->so : 1);
   rc = c->d_c.reserve(c, 3 * zd_sz); if (rc) return rc;
-  PNetArgs pa; fill_pnet(c, pa, c->d_a, B);
+  PNetArgs pa; fill_pnet(c, pa, xin_dev, B);
   if (ll) {
     // u = Dot(phi(x), a(p)) + bias: coordinate columns move phi, parameter columns move a
-    rc = nif_forward_dev(c, c->d_a, B, c->d_d); if (rc) return rc;     // leaves Z (= a) on the device
-    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, c->d_a, ncol, c->pi, B);
+    rc = nif_forward_dev(c, xin_dev, B, c->d_d); if (rc) return rc;     // leaves Z (= a) on the device
+    ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin_dev, ncol, c->pi, B);
     if (c->use_ll4) launch_pnet(ma, c->NB, false, c->st);               // the fused forward keeps phi on chip: compute it here
     for (int j = 0; j < nx; ++j) {
       if (x_idx[j] >= c->pi) {
@@ -1114,7 +1106,7 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
     }
   } else {
     launch_pnet(pa, c->NSTB, false, c->st);
-    SNetArgs sa; fill_snet(c, sa, c->d_a, ncol, c->pi, B);
+    SNetArgs sa; fill_snet(c, sa, xin_dev, ncol, c->pi, B);
     for (int x0 = 0; x0 < nx; x0 += 3) {
       int seeds[3] = {0, 0, 0};
       const float* zd[3] = {nullptr, nullptr, nullptr};
@@ -1134,6 +1126,21 @@ extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32
     }
   }
   HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_jacobian(nif_ctx* c, const float* xin, int64_t B, const int32_t* y_idx, int32_t ny,
+                            const int32_t* x_idx, int32_t nx, float* y_out, float* dydx_out) {
+  if (!c || !xin || !y_idx || !x_idx || !y_out || !dydx_out || B <= 0 || ny <= 0 || nx <= 0)
+    return fail(NIF_ERR_INVALID, "bad argument");
+  for (int i = 0; i < ny; ++i)
+    if (y_idx[i] < 0 || y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
+  for (int j = 0; j < nx; ++j)
+    if (x_idx[j] < 0 || x_idx[j] >= c->pi + c->si) return fail(NIF_ERR_INVALID, "x_index out of range");
+  { const int rcw = wide_refused(c, "JacobianLayer"); if (rcw) return rcw; }
+  NIF_ENTER(c, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  int rc = stage(c, c->d_a, xin, B * (c->pi + c->si)); if (rc) return rc;
+  rc = jacobian_core(c, c->d_a, B, x_idx, nx); if (rc) return rc;
   std::vector<float> full((size_t)B * c->so * nx);
   HIPCHK(hipMemcpyAsync(y_out, c->d_d, sizeof(float) * (size_t)(B * c->so), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(full.data(), c->d_b, sizeof(float) * full.size(), hipMemcpyDeviceToHost, c->st));
@@ -1476,6 +1483,263 @@ extern "C" int nif_snapshot_derivatives(const nif_snapderiv_args* a) {
     HIPCHK(hipMemcpyAsync(a->u, d.u, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipMemcpyAsync(a->dudx, d.dudx, sizeof(float) * (size_t)(n * a->ny * a->nx), hipMemcpyDeviceToHost, c->st));
     if (a->order == 2) HIPCHK(hipMemcpyAsync(a->d2udx2, d.d2udx2, sizeof(float) * (size_t)(n * a->ny * a->nx * a->nx), hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+
+// ---- snapshot-wise parameter derivatives (include/nif_hip_snapparam.h) ------------------------------------------------
+static int sp_check(const nif_snapparam_args* a, long* n) {
+  if (!a) return fail(NIF_ERR_INVALID, "null");
+  if (a->abi_version != NIF_SNAPPARAM_ABI_VERSION)
+    return fail(NIF_ERR_INVALID, "nif_snapparam_args: abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(NIF_SNAPPARAM_ABI_VERSION));
+  if (a->reserved0 || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
+    return fail(NIF_ERR_INVALID, "nif_snapparam_args: reserved fields must be zero");
+  const nif_ctx* c = a->ctx;
+  const int64_t* off = a->offsets_host;
+  if (!c || !a->rows || !a->y_idx || a->T <= 0 || a->ny <= 0 || (off ? off[0] != 0 : a->M < 0)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (a->rows_are_latent) {
+    if (!a->drows) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: latent rows need drows [T, nd, r]");
+    if (a->p_idx || a->np) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: p_idx / np go with rows [T, pi], not with latents");
+    if (a->nd < 1 || a->nd > 16) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: 1 to 16 directions (nd)");
+  } else {
+    if (a->drows || a->nd) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: drows / nd go with latent rows (rows_are_latent = 1)");
+    if (!a->p_idx || a->np < 1 || a->np > 16) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: 1 to 16 parameter columns (p_idx, np)");
+    for (int j = 0; j < a->np; ++j) {
+      if (a->p_idx[j] < 0 || a->p_idx[j] >= c->pi) return fail(NIF_ERR_INVALID, "p_index out of range (0 <= c < pi_dim)");
+      for (int k = 0; k < j; ++k) if (a->p_idx[k] == a->p_idx[j]) return fail(NIF_ERR_INVALID, "p_index: an index is repeated");
+    }
+  }
+  if (off) for (int64_t t = 0; t < a->T; ++t) if (off[t + 1] < off[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
+  *n = off ? (long)off[a->T] : (long)(a->T * a->M);
+  if (*n > 0 && (!a->x || !a->u || !a->dudp)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (a->ny > 16) return fail(NIF_ERR_INVALID, "y_index: at most 16 entries");
+  for (int i = 0; i < a->ny; ++i)
+    if (a->y_idx[i] < 0 || a->y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
+  if (c->capturing) return fail(NIF_ERR_STATE, "nif_snapshot_param_derivatives: not capturable (inside nif_graph_begin / nif_graph_end)");
+  return NIF_OK;
+}
+constexpr int SP_GROUP = 3;      // direction streams of one launch (the tangent kernels' NIF_JAC_MAXSEED)
+// one snapshot of the weight-tangent path: the slot vectors w_t, wd_t,0 .. wd_t,g-1 and, per hidden matrix, the 1 + g forward f32 planes
+// [W_j | W'_0,j | ..] (the format k_jac reads); g = the directions of a launch group
+static long sp_chunk(const nif_ctx* c, long T, int g) {
+  const long per = (1 + g) * ((long)sizeof(float) * c->po + (long)c->nh * sd_plane_f32x4(c) * (long)sizeof(f32x4));
+  long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
+  if (tc > 65535) tc = 65535;
+  if (tc > T) tc = T;
+  return tc < 1 ? 1 : tc;
+}
+static long sp_combined_floats(const nif_ctx* c, long tc, int g) { return snap_r4((1 + g) * tc * c->po) + (1 + g) * tc * c->nh * sd_plane_f32x4(c) * 4 + 4; }
+// Hypernetwork classes on k_jac_wt.  lat [T][r], D [nd][T][r] (direction-major).  Per chunk of snapshots: w_t and its planes once; per
+// group of g <= 3 directions the tangent slot vectors wd_t,d (k_dlatent_to_w), their planes beside W_j's, one launch.  The kernel leaves
+// every output row [n][so][nd] in c->d_b; the rows y_idx are gathered behind the last chunk.
+static int sp_combined(nif_ctx* c, const nif_snapparam_args* a, float* buf, long tc_max, int gmax, const float* lat, const float* D, int nd,
+                       const long* off_dev, long n, const HessIdx& I) {
+  const long T = a->T, M = a->M;
+  const int64_t* off_host = a->offsets_host;
+  const int so = c->so, NBL = snet3_nbl(c->n), ps = 1 + gmax;
+  int rc = stage(c, c->d_b, nullptr, n * so * nd); if (rc) return rc;
+  float* w = buf;                                   // [1 + gmax][tc_max][po]: w_t, then each stream's wd_t
+  f32x4* WF = reinterpret_cast<f32x4*>(w + snap_r4((long)ps * tc_max * c->po));
+  const long plane_s = sd_plane_f32x4(c);
+  for (long t0 = 0; t0 < T; t0 += tc_max) {
+    const long tc = T - t0 < tc_max ? T - t0 : tc_max;
+    long mmax = M, n_pts = tc * M;
+    if (off_host) {
+      mmax = 0; n_pts = off_host[t0 + tc] - off_host[t0];
+      for (long t = t0; t < t0 + tc; ++t) if (off_host[t + 1] - off_host[t] > mmax) mmax = off_host[t + 1] - off_host[t];
+    }
+    if (n_pts == 0) continue;
+    {
+      ProfScope p_(c, NIF_PROF_PACK);
+      launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
+      for (int j = 0; j < c->nh; ++j)
+        launch_pack16_fwd_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + (long)j * ps * plane_s, c->nh * ps * plane_s, c->st);
+    }
+    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, mmax);
+    sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr; sa.WF = WF; sa.WB = nullptr;
+    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * ps * plane_s; sa.snap_T = (int)tc;
+    const long pb = off_dev ? 0 : t0 * M;      // (ragged: the kernel rebases by the call's own offsets; shared mesh: by t M inside the chunk)
+    for (int d0 = 0; d0 < nd; d0 += gmax) {
+      const int g = nd - d0 < gmax ? nd - d0 : gmax;
+      const float* wd[SP_GROUP] = {nullptr, nullptr, nullptr};
+      {
+        ProfScope p_(c, NIF_PROF_PACK);
+        for (int d = 0; d < g; ++d) {
+          float* wdd = w + (long)(1 + d) * tc_max * c->po;
+          launch_dlatent_to_w(c->theta, c->last_w, c->r, c->po, D + ((long)(d0 + d) * T + t0) * c->r, tc, wdd, c->st);
+          for (int j = 0; j < c->nh; ++j)
+            launch_pack16_fwd_batch(wdd, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL,
+                                    WF + ((long)j * ps + 1 + d) * plane_s, c->nh * ps * plane_s, c->st);
+          wd[d] = wdd;
+        }
+      }
+      sa.u_out = d0 == 0 ? a->u + pb * so : nullptr;
+      ProfScope p_(c, NIF_PROF_SNET_FWD);
+      launch_jac_wt(sa, tc, g, wd, ps, nd, d0, c->d_b + pb * so * nd, c->st);
+    }
+  }
+  launch_jac_gather(c->d_b, n, so, nd, I, a->dudp, c->st);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_snapshot_param_derivatives_dev(const nif_snapparam_args* a) {
+  long n = 0;
+  int rc = sp_check(a, &n); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  rc = ensure_packed(c); if (rc) return rc;
+  const bool lat_in = a->rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
+  if (lat_in && c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
+    return fail(NIF_ERR_INVALID, std::string("nif_snapshot_param_derivatives: latents are not built for the ") +
+                                     (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
+                                     " policy (the tangent kernels run exact products, the policy's ParameterNet does not; pass p)");
+  const bool pointwise = snap_pointwise(c) && !lat_in;      // JacobianLayer's kernels on the device-built [p_t | x] table
+  if (pointwise) { const int rcw = wide_refused(c, "JacobianLayer"); if (rcw) return rcw; }
+  if (!ll && !c->jac_ok) return fail(NIF_ERR_INVALID, "JacobianLayer: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
+  const bool combined = !ll && !snap_pointwise(c);          // k_jac_wt on combined nets
+  if (combined) {
+    SNetArgs probe; fill_snet(c, probe, nullptr, 0, 0, 32);
+    if (!jac_wt_supported(probe))
+      return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: one weight plane and four images of the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
+  }
+  if (n == 0) return NIF_OK;
+  const long T = a->T, M = a->M;
+  const int64_t* offsets = a->offsets_host;
+  const int nd = lat_in ? a->nd : a->np, ny = a->ny, si = c->si, r = c->r, so = c->so;
+  HessIdx I; I.ny = ny;
+  for (int i = 0; i < 16; ++i) I.y_idx[i] = i < ny ? a->y_idx[i] : 0;
+  // the routes: JacobianLayer's kernels on the table; k_jac_wt on combined nets; the last-layer class' phi once per shared
+  // mesh; else the point-wise kernels behind latent and direction tiles built on the device
+  const bool phi_dot = ll && !pointwise && !offsets && phi_dot_supported(r, so);
+  const int gmax = nd < SP_GROUP ? nd : SP_GROUP;
+  const long tc_max = combined ? sp_chunk(c, T, gmax) : 0;
+  // one buffer, one growth: [offsets (ragged) | latent rows (from p) | direction rows [nd][T][r] | so zeros | the table, or the
+  // combined nets of one chunk of snapshots]
+  const long off_f = offsets ? 2 * (T + 1) : 0, lat_f = (pointwise || lat_in) ? 0 : T * r, dir_f = pointwise ? 0 : (long)nd * T * r;
+  const long head_f = snap_r4(off_f + lat_f + dir_f + so);
+  const bool table = pointwise || (!offsets && !phi_dot && !combined);
+  const int tcol = pointwise ? c->pi + si : si;
+  const long tab_f = table ? n * tcol : (combined ? sp_combined_floats(c, tc_max, gmax) : 0);
+  rc = c->snap.reserve(c, head_f + tab_f + 1); if (rc) return rc;
+  SnapArgs sn; memset(&sn, 0, sizeof(sn));
+  sn.T = T; sn.M = M; sn.n = n; sn.pi = pointwise ? c->pi : 0; sn.si = si; sn.r = r; sn.x = a->x;
+  if (offsets) {      // (host memory of the caller: consumed before this returns)
+    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
+    HIPCHK(hipMemcpyAsync(c->snap.p, offsets, sizeof(int64_t) * (size_t)(T + 1), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
+  }
+  if (table) sn.table = c->snap + head_f;
+  if (pointwise) {
+    sn.p = a->rows;
+    launch_snap_expand(sn, c->st);
+    rc = jacobian_core(c, sn.table, n, a->p_idx, nd); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(a->u, c->d_d, sizeof(float) * (size_t)(n * so), hipMemcpyDeviceToDevice, c->st));
+    launch_jac_gather(c->d_b, n, so, nd, I, a->dudp, c->st);
+    HIPCHK(hipGetLastError());
+    return NIF_OK;
+  }
+  // ---- the latent and the directions of every snapshot: lat [T][r], D [nd][T][r] ------------------------------------------------------
+  const long ttiles = (T + 31) / 32;
+  rc = ensure_capacity(c, combined ? T : (phi_dot ? (T > M ? T : M) : (n > T ? n : T)), false); if (rc) return rc;
+  const float* lat = a->rows;
+  float* D = c->snap + off_f + lat_f;
+  float* zero = D + dir_f;
+  if (lat_in) launch_dir_rows(a->drows, T, nd, r, D, c->st);
+  else {      // the ParameterNet over the T rows and, per column, its input tangent (k_mlp_jac, as nif_jacobian runs it): back as rows
+    rc = ensure_packed_p32(c); if (rc) return rc;
+    rc = c->d_c.reserve(c, ttiles * 32 * r); if (rc) return rc;
+    PNetArgs pa; fill_pnet(c, pa, a->rows, T); pa.ncol = c->pi;
+    ProfScope p_(c, NIF_PROF_PNET_FWD);
+    for (int j = 0; j < nd; ++j) {
+      PNetArgs pj = pa; pj.Z = ll ? c->DA : c->DZ;      // (primal again into a scratch)
+      launch_mlp_jac(pj, c->NSTB, a->p_idx[j], c->d_c, c->st);
+      launch_tiles_to_rows(c->d_c, T, r, D + (long)j * T * r, c->st);
+    }
+    launch_pnet(pa, c->NSTB, false, c->st);
+    launch_tiles_to_rows(c->Z, T, r, c->snap + off_f, c->st);
+    lat = c->snap + off_f;
+  }
+  if (combined) return sp_combined(c, a, c->snap + head_f, tc_max, gmax, lat, D, nd, sn.offsets, n, I);
+  if (phi_dot) {      // phi of the mesh once; u, and the same contraction over the nd T tangent coefficient rows without the bias
+    HIPCHK(hipMemsetAsync(zero, 0, sizeof(float) * (size_t)so, c->st));
+    rc = stage(c, c->d_b, nullptr, n * so * nd); if (rc) return rc;
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    if (c->use_wide) wide_forward(c, a->x, si, 0, M, false);
+    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, a->x, si, 0, M); launch_pnet(ma, c->NB, false, c->st); }
+    launch_phi_dot(c->PHI, lat, c->theta + c->ll_bias, T, M, r, so, a->u, c->st);
+    launch_phi_dot(c->PHI, D, zero, (long)nd * T, M, r, so, c->d_b, c->st);
+    launch_snapparam_gather(c->d_b, T, M, so, nd, I, a->dudp, c->st);
+    HIPCHK(hipGetLastError());
+    return NIF_OK;
+  }
+  // ---- point-wise kernels behind tiles: the latent of every point in c->Z, direction d's in a tile array of the same layout -----------
+  const long ntl = (n + 31) / 32, zd_sz = ntl * 32 * r;
+  rc = stage(c, c->d_b, nullptr, n * so * nd); if (rc) return rc;
+  rc = c->d_c.reserve(c, (ll ? 1 : SP_GROUP) * zd_sz); if (rc) return rc;
+  sn.lat = lat; sn.Z = c->Z;
+  launch_snap_expand(sn, c->st);
+  const float* xg = table ? sn.table : a->x;
+  sn.table = nullptr;
+  if (ll) {
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    if (c->use_wide) wide_forward(c, xg, si, 0, n, false);
+    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xg, si, 0, n); launch_pnet(ma, c->NB, false, c->st); }
+    LLArgs la; fill_ll(c, la, n); la.u_out = a->u;
+    launch_ll_out(la, false, c->st);
+    for (int d = 0; d < nd; ++d) {
+      sn.lat = D + (long)d * T * r; sn.Z = c->d_c;
+      launch_snap_expand(sn, c->st);
+      launch_ll_jac_out(c->PHI, c->Z, nullptr, c->d_c, n, r, so, nd, d, c->d_b, c->st);
+    }
+  } else {      // latents on a legacy float32 shape: the point-wise k_jac, its ZD operand exactly such a tile array
+    rc = ensure_packed32(c); if (rc) return rc;
+    SNetArgs sa; fill_snet(c, sa, xg, si, 0, n);
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    for (int d0 = 0; d0 < nd; d0 += SP_GROUP) {
+      const int ns = nd - d0 < SP_GROUP ? nd - d0 : SP_GROUP;
+      int seeds[SP_GROUP] = {-1, -1, -1};
+      const float* zd[SP_GROUP] = {nullptr, nullptr, nullptr};
+      for (int d = 0; d < ns; ++d) {
+        sn.lat = D + (long)(d0 + d) * T * r; sn.Z = c->d_c + d * zd_sz;
+        launch_snap_expand(sn, c->st);
+        zd[d] = sn.Z;
+      }
+      sa.u_out = d0 == 0 ? a->u : nullptr;
+      launch_jac(sa, ns, seeds, zd, nd, d0, c->d_b, c->st);
+    }
+  }
+  launch_jac_gather(c->d_b, n, so, nd, I, a->dudp, c->st);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_snapshot_param_derivatives(const nif_snapparam_args* a) {
+  long n = 0;
+  int rc = sp_check(a, &n); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  const long T = a->T;
+  const bool lat_in = a->rows_are_latent != 0;
+  const long nd = lat_in ? a->nd : a->np;
+  const long n_rows = T * (lat_in ? c->r : c->pi), n_dr = lat_in ? T * nd * c->r : 0, n_x = (a->offsets_host ? n : (long)a->M) * c->si;
+  const long f_rows = snap_r4(n_rows), f_dr = snap_r4(n_dr), f_x = snap_r4(n_x), f_u = snap_r4(n * c->so), f_d = snap_r4(n * a->ny * nd);
+  rc = c->sp_io.reserve(c, f_rows + f_dr + f_x + f_u + f_d + 4); if (rc) return rc;
+  nif_snapparam_args d = *a;
+  float* q = c->sp_io.p;
+  d.rows = q; q += f_rows;
+  d.drows = lat_in ? q : nullptr; q += f_dr;
+  d.x = q; q += f_x;
+  d.u = q; q += f_u;
+  d.dudp = q;
+  HIPCHK(hipMemcpyAsync(const_cast<float*>(d.rows), a->rows, sizeof(float) * (size_t)n_rows, hipMemcpyHostToDevice, c->st));
+  if (lat_in) HIPCHK(hipMemcpyAsync(const_cast<float*>(d.drows), a->drows, sizeof(float) * (size_t)n_dr, hipMemcpyHostToDevice, c->st));
+  if (n > 0) HIPCHK(hipMemcpyAsync(const_cast<float*>(d.x), a->x, sizeof(float) * (size_t)n_x, hipMemcpyHostToDevice, c->st));
+  rc = nif_snapshot_param_derivatives_dev(&d); if (rc) return rc;
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(a->u, d.u, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(a->dudp, d.dudp, sizeof(float) * (size_t)(n * a->ny * nd), hipMemcpyDeviceToHost, c->st));
   }
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;

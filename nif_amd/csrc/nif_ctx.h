@@ -160,6 +160,9 @@ struct nif_ctx {
   // snapshot-wise derivatives (nif_snapshot_derivatives*): sd_tmp takes the second-order output of an order-1 call on the routes that
   // run the second-order kernels anyway; sd_io stages the host-pointer entry's [rows | x | u | dudx | d2udx2]
   DevBuf<float> sd_tmp, sd_io;
+  // snapshot-wise parameter derivatives (nif_snapshot_param_derivatives*): sp_io stages the host-pointer entry's [rows | drows | x | u |
+  // dudp]; everything else of a call lives in `snap` and the point workspaces
+  DevBuf<float> sp_io;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

@@ -477,6 +477,17 @@ void launch_phi_dot_d2(const float* f0, const float* fj, const float* fh, const 
 // last-layer class, shared mesh: u [T][M][so] = Dot(PHI [tiles][so r][32], a [T][r]) + bias [so]
 bool phi_dot_supported(int r, int so);
 void launch_phi_dot(const float* PHI, const float* a, const float* bias, long T, long M, int r, int so, float* u, hipStream_t st);
+// snapshot-wise parameter derivatives (nif_snapshot_param_derivatives*).  k_snap.hip: the tangent slot vectors
+// wd [rows][po] = d [rows][r] . Wh (no hyper bias); the caller's directions [T][nd][r] as direction-major rows [nd][T][r]; rows y_idx
+// of k_phi_dot's result over those rows, f [nd][T][M][so] -> dudp [T][M][ny][nd].  k_jac_wtan.hip: the weight-tangent form of
+// k_jac<.., SNAP> -- ns <= 3 direction streams on T combined nets, columns d0 .. d0 + ns of dudp [n][so][nd_total]; wd[d] [T][po],
+// pstride planes per hidden layer in the image at a.WF ([W_j | W'_0,j | ..])
+void launch_dlatent_to_w(const float* theta, long off_Wh, int r, long po, const float* d, long rows, float* wd, hipStream_t st);
+void launch_dir_rows(const float* drows, long T, int nd, int r, float* D, hipStream_t st);
+void launch_snapparam_gather(const float* f, long T, long M, int so, int nd, const HessIdx& I, float* dudp, hipStream_t st);
+bool jac_wt_supported(const SNetArgs& a);
+void launch_jac_wt(const SNetArgs& a, long T, int ns, const float* const* wd, int pstride, int nd_total, int d0, float* dudp,
+                   hipStream_t st);
 // per-snapshot normal equations in the latent (k_encode.hip, nif_snapshot_normal_eq*).  The snapshots t0 .. t1 of a call in
 // the padded layout: snapshot t owns the 32-point tiles tile_start[t] .. tile_start[t + 1] (whole tiles: no tile straddles two
 // snapshots; padding points repeat the snapshot's last point and weigh 0), its points are offsets[t] .. offsets[t + 1] of x / y / w

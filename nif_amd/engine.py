@@ -377,6 +377,71 @@ class Engine(object):
         finally:
             d_x.free()
 
+    # ---- snapshot-wise parameter derivatives (include/nif_hip_snapparam.h; Model.predict_snapshot_parameter_derivatives plans the chunks) ----
+    def _snapshot_param_derivs(self, rows, drows, d_x, x_off, offsets, m, n, y_index, p_index):
+        self._not_capturing("nif_snapshot_param_derivatives")
+        s = self.spec
+        is_latent = drows is not None
+        rows = self._rows(rows, s.pi_hidden if is_latent else s.pi_dim, "latent" if is_latent else "parameter inputs")
+        yi = np.ascontiguousarray(list(y_index), dtype=np.int32)
+        if is_latent:
+            drows = np.ascontiguousarray(drows, dtype=np.float32)
+            if drows.ndim != 3 or drows.shape[0] != rows.shape[0] or drows.shape[2] != s.pi_hidden:
+                raise ValueError("dlatent: expected shape (%d, nd, %d), got %s" % (rows.shape[0], s.pi_hidden, drows.shape))
+            pi_, nd = None, drows.shape[1]
+        else:
+            pi_ = np.ascontiguousarray(list(p_index), dtype=np.int32)
+            nd = pi_.size
+        ny = yi.size
+        u = np.empty((n, s.so_dim), dtype=np.float32)
+        d = np.empty((n, ny, nd), dtype=np.float32)
+        if not n:
+            return u, d
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        d_r, d_o = DeviceArray(self, rows.size + (drows.size if is_latent else 0)), DeviceArray(self, u.size + d.size)
+        try:
+            d_r.upload(np.concatenate([rows.ravel(), drows.ravel()]) if is_latent else rows)
+            a = _lib.nif_snapparam_args()
+            a.abi_version, a.ctx = _lib.NIF_SNAPPARAM_ABI_VERSION, self.ctx
+            a.rows, a.rows_are_latent, a.T = d_r.at(0), 1 if is_latent else 0, rows.shape[0]
+            if is_latent:
+                a.drows, a.nd = d_r.at(rows.size), nd
+            else:
+                a.p_idx, a.np = pi_.ctypes.data_as(C.POINTER(C.c_int32)), nd
+            a.x, a.M = d_x.at(x_off), int(m)
+            a.offsets_host = None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64))
+            a.y_idx, a.ny = yi.ctypes.data_as(C.POINTER(C.c_int32)), ny
+            a.u, a.dudp = d_o.at(0), d_o.at(u.size)
+            check(self.lib.nif_snapshot_param_derivatives_dev(C.byref(a)))
+            check(self.lib.nif_d2h(self.ctx, ptr(u), d_o.at(0), u.size * 4))
+            check(self.lib.nif_d2h(self.ctx, ptr(d), d_o.at(u.size), d.size * 4))
+        finally:
+            d_r.free(); d_o.free()
+        return u, d
+
+    def snapshot_param_derivatives(self, rows, drows, mesh, lo, hi, y_index, p_index):
+        """rows [T, pi] with p_index (drows None), or latents [T, r] with directions drows [T, nd, r], on the points lo .. hi of a
+        snapshot_mesh handle -> (u [T, hi - lo, so], dudp [T, hi - lo, ny, nd])"""
+        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
+        outs = self._snapshot_param_derivs(rows, drows, mesh, int(lo) * self.spec.si_dim, None, m, t * m, y_index, p_index)
+        return tuple(o.reshape((t, m) + o.shape[1:]) for o in outs)
+
+    def snapshot_param_derivatives_ragged(self, rows, drows, xs, y_index, p_index):
+        """rows [T, .] (and drows) and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> the same outputs [sum M_t, ...], snapshot after snapshot"""
+        self._not_capturing("nif_snapshot_param_derivatives")
+        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
+        if len(xs) != int(np.shape(rows)[0]):
+            raise ValueError("snapshot_param_derivatives_ragged: %d rows for %d meshes" % (int(np.shape(rows)[0]), len(xs)))
+        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
+        n = int(offsets[-1])
+        d_x = DeviceArray(self, max(n, 1) * self.spec.si_dim)
+        try:
+            if n:
+                d_x.upload(np.concatenate(xs, axis=0))
+            return self._snapshot_param_derivs(rows, drows, d_x, 0, offsets, 0, n, y_index, p_index)
+        finally:
+            d_x.free()
+
     # ---- encoding (include/nif_hip_encode.h; nif_amd/encode.py runs the Levenberg-Marquardt loop around these two) ----------
     def snapshot_samples(self, x, y, w=None, counts=None):
         """The samples of T snapshots on the device, uploaded once for all snapshot_normal_eq calls of one encode.  counts None: a

@@ -271,10 +271,11 @@ class Model(object):
                                  lambda *a: (e.forward_snapshots(*a),), lambda *a: (e.forward_snapshots_ragged(*a),))
         return out[0]
 
-    def _snapshot_run(self, who, x, p, latent, batch_size, per_point, tails, shared_call, ragged_call):
+    def _snapshot_run(self, who, x, p, latent, batch_size, per_point, tails, shared_call, ragged_call, extra=None):
         """What the snapshot-wise calls share: the checks of x, p | latent, and the chunk plan.  tails: the trailing shape of every
         output; shared_call(rows, is_latent, mesh, lo, hi) -> arrays [T', hi - lo, *tail]; ragged_call(rows, is_latent, xs) -> arrays
-        [sum M_t, *tail].  Returns a tuple of arrays [T, M, *tail] (shared mesh) or of lists of [M_t, *tail]."""
+        [sum M_t, *tail].  extra: a second per-snapshot array [T, ...]; the calls then get the pair (rows, extra) of their snapshots in
+        the place of rows.  Returns a tuple of arrays [T, M, *tail] (shared mesh) or of lists of [M_t, *tail]."""
         if self._role != "full":
             raise ValueError("%s exists on the full model only (%s is a sub-model view)" % (who, self._role))
         if (p is None) == (latent is None):
@@ -286,6 +287,7 @@ class Model(object):
         if rows.ndim != 2 or rows.shape[1] != width:
             raise ValueError("%s: expected %s of shape (T, %d), got %s" % (who, "latent" if is_latent else "p", width, rows.shape))
         T = rows.shape[0]
+        take = (lambda idx: rows[idx]) if extra is None else (lambda idx: (rows[idx], extra[idx]))
 
         def mesh_of(a):
             a = np.asarray(a, dtype=np.float32)
@@ -308,7 +310,7 @@ class Model(object):
                 for lo in range(0, M, mc):
                     hi = min(M, lo + mc)
                     for t0 in range(0, T, tc):
-                        for out, part in zip(outs, shared_call(rows[t0:t0 + tc], is_latent, mesh, lo, hi)):
+                        for out, part in zip(outs, shared_call(take(slice(t0, t0 + tc)), is_latent, mesh, lo, hi)):
                             out[t0:t0 + tc, lo:hi] = part
             finally:
                 mesh.free()
@@ -320,7 +322,7 @@ class Model(object):
         group, held = [], 0
 
         def flush():
-            parts = ragged_call(rows[[t for t, _, _ in group]], is_latent, [xs[t][lo:hi] for t, lo, hi in group])
+            parts = ragged_call(take([t for t, _, _ in group]), is_latent, [xs[t][lo:hi] for t, lo, hi in group])
             for out, u in zip(outs, parts):
                 at = 0
                 for t, lo, hi in group:
@@ -372,6 +374,62 @@ class Model(object):
         return self._snapshot_run(who, x, p, latent, batch_size, per_point, tails,
                                   lambda rows, il, mesh, lo, hi: e.snapshot_derivatives(rows, il, mesh, lo, hi, yi, xi, order),
                                   lambda rows, il, xs: e.snapshot_derivatives_ragged(rows, il, xs, yi, xi, order))
+
+    def predict_snapshot_parameter_derivatives(self, x, p=None, p_index=None, latent=None, dlatent=None, y_index=None, batch_size=None):
+        """predict_snapshots with the field's first derivative in the other half of the input vector: x, p | latent and batch_size as
+        there.  With p [T, pi]: p_index lists distinct ParameterNet input columns 0 <= c < pi (default: all of them), and
+        dudp[t][m, i, c] = d u_{y_index[i]} / d p_{p_index[c]} -- for snapshot t what JacobianLayer(model, y_index, p_index) returns on
+        hstack([tile(p[t], M_t), x_t]), without that table.  With latent [T, r] and dlatent [T, nd, r], 1 <= nd <= 16 directions in
+        latent space per snapshot: dudp[t][m, i, d] = sum_k du_i/dz_k (latent[t]; x_m) dlatent[t, d, k] (last-layer class: the latent is
+        the coefficient vector a).  y_index: outputs, any order, repeats allowed, at most 16 (default: every output).  Shared mesh:
+        returns (u [T, M, so], dudp [T, M, ny, nd]); a list / tuple of meshes: a tuple of lists of [M_t, ...] arrays.  The ParameterNet
+        and its tangents run once per snapshot; the hypernetwork classes run 1 + 2 g hidden products per layer for a group of g <= 3
+        directions on the snapshot's combined matrices and their tangents.  Device staging is bounded by
+        _SNAPSHOT_CHUNK_BYTES as in predict_snapshots; the result does not depend on it."""
+        who = "predict_snapshot_parameter_derivatives"
+        s = self._owner._spec
+        if self._role != "full":
+            raise ValueError("%s exists on the full model only (%s is a sub-model view)" % (who, self._role))
+        if (p is None) == (latent is None):
+            raise ValueError("%s: exactly one of p [T, pi] and latent [T, r]" % who)
+        if (latent is None) != (dlatent is None):
+            raise ValueError("%s: latent [T, r] and dlatent [T, nd, r] go together" % who)
+        yi = list(range(s.so_dim)) if y_index is None else [int(i) for i in y_index]
+        if not yi or len(yi) > 16 or any(i < 0 or i >= s.so_dim for i in yi):
+            raise ValueError("%s: y_index lists 1 to 16 outputs 0 <= i < %d, got %r" % (who, s.so_dim, yi))
+        if latent is not None:
+            if p_index is not None:
+                raise ValueError("%s: p_index goes with p, not with latent" % who)
+            lat = np.asarray(latent, dtype=np.float32)
+            if lat.ndim != 2 or lat.shape[1] != s.pi_hidden:
+                raise ValueError("%s: expected latent of shape (T, %d), got %s" % (who, s.pi_hidden, lat.shape))
+            dl = np.ascontiguousarray(dlatent, dtype=np.float32)
+            if dl.ndim != 3 or dl.shape[0] != lat.shape[0] or dl.shape[2] != s.pi_hidden:
+                raise ValueError("%s: expected dlatent of shape (%d, nd, %d), got %s" % (who, lat.shape[0], s.pi_hidden, dl.shape))
+            if not 1 <= dl.shape[1] <= 16:
+                raise ValueError("%s: 1 to 16 directions in dlatent, got %d" % (who, dl.shape[1]))
+            pi_, nd = None, dl.shape[1]
+        else:
+            dl = None
+            pi_ = list(range(s.pi_dim)) if p_index is None else [int(c) for c in p_index]
+            if not pi_ or len(pi_) > 16 or any(c < 0 or c >= s.pi_dim for c in pi_):
+                raise ValueError("%s: p_index lists 1 to 16 ParameterNet input columns 0 <= c < %d, got %r" % (who, s.pi_dim, pi_))
+            if len(set(pi_)) != len(pi_):
+                raise ValueError("%s: p_index repeats an index: %r" % (who, pi_))
+            nd = len(pi_)
+        ny = len(yi)
+        e = self._engine
+        # what a point holds on the device: the forward's operands, its result rows and the kernels' rows over every output
+        # (last-layer class: also the so * r rows of phi)
+        per_point = 4 * (s.pi_dim + s.si_dim + s.so_dim + s.pi_hidden * (1 + min(nd, 3)) + (ny + s.so_dim) * nd +
+                         (s.so_dim * s.pi_hidden if s.connectivity == "last_layer" else 0))
+        if dl is None:
+            return self._snapshot_run(who, x, p, latent, batch_size, per_point, [(s.so_dim,), (ny, nd)],
+                                      lambda rows, il, mesh, lo, hi: e.snapshot_param_derivatives(rows, None, mesh, lo, hi, yi, pi_),
+                                      lambda rows, il, xs: e.snapshot_param_derivatives_ragged(rows, None, xs, yi, pi_))
+        return self._snapshot_run(who, x, p, latent, batch_size, per_point, [(s.so_dim,), (ny, nd)],
+                                  lambda rd, il, mesh, lo, hi: e.snapshot_param_derivatives(rd[0], rd[1], mesh, lo, hi, yi, None),
+                                  lambda rd, il, xs: e.snapshot_param_derivatives_ragged(rd[0], rd[1], xs, yi, None), extra=dl)
 
     def encode_snapshots(self, x, u, latent0=None, p0=None, sample_weight=None, max_iter=20, tol=1e-8):
         """The inverse of predict_snapshots(x, latent=...): for each of T snapshots the latent whose field fits the samples u best in
