@@ -265,10 +265,11 @@ def load():
             "libnif_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-    for name, (res, args) in list(SIGNATURES.items()) + list(SNAPSHOT_SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(SNAPDERIV_SIGNATURES.items()) + list(SNAPPARAM_SIGNATURES.items()):
-        fn = getattr(lib, name)  # AttributeError if the library does not export it
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, SNAPSHOT_SIGNATURES, ENCODE_SIGNATURES, SNAPDERIV_SIGNATURES, SNAPPARAM_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError if the library does not export it
+            fn.restype = res
+            fn.argtypes = args
     if lib.nif_abi_version() != NIF_ABI_VERSION:
         raise NifError("libnif_hip.so ABI version %d != %d" % (lib.nif_abi_version(), NIF_ABI_VERSION))
     _lib = lib

@@ -710,6 +710,13 @@ static int wide_refused(const nif_ctx* c, const char* who) {
                                    std::to_string(c->n) + ")");
 }
 
+// The last-layer class' ShapeNet alone: phi of B points (the coordinates are columns col0 .. col0 + si of x [B][ncol]) into c->PHI,
+// behind ensure_packed / ensure_capacity.  The caller holds the ProfScope, where it has one.
+static void ll_phi_pass(nif_ctx* c, const float* x, int ncol, int col0, long B) {
+  if (c->use_wide) wide_forward(c, x, ncol, col0, B, false);
+  else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, ncol, col0, B); launch_pnet(ma, c->NB, false, c->st); }
+}
+
 // The forward of B rows behind ensure_packed / ensure_capacity.  with_pnet: xin [B][pi + si], the ParameterNet fills Z; without (the
 // snapshot entries): Z already holds every point's latent and the coordinates are columns col0 .. col0 + si of xin [B][ncol]
 static int forward_rows(nif_ctx* c, const float* xin, int ncol, int col0, long B, float* u, bool with_pnet) {
@@ -726,8 +733,7 @@ static int forward_rows(nif_ctx* c, const float* xin, int ncol, int col0, long B
       HIPCHK(hipGetLastError());
       return NIF_OK;
     }
-    if (c->use_wide) wide_forward(c, xin, ncol, col0, B, false);
-    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xin, ncol, col0, B); launch_pnet(ma, c->NB, false, c->st); }
+    ll_phi_pass(c, xin, ncol, col0, B);
     LLArgs la; fill_ll(c, la, B); la.u_out = u;
     launch_ll_out(la, false, c->st);
     HIPCHK(hipGetLastError());
@@ -777,20 +783,168 @@ static bool snap_pointwise(const nif_ctx* c) {
   if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32) return true;
   return c->kind != NIF_KIND_LASTLAYER && !c->use_snet4 && !c->use_snet3;
 }
-static int snap_check(nif_ctx* c, const void* rows, int64_t T, const void* x, const int64_t* offsets, int64_t M, const void* u, long* n) {
+// ---- the front end the snapshot calls share: nif_forward_snapshots*, nif_snapshot_normal_eq*, nif_snapshot_derivatives*,
+// nif_snapshot_param_derivatives* ----
+// Call geometry: T snapshots on a shared mesh of M points (off null) or on ragged meshes, snapshot t the points off[t] .. off[t + 1]
+// (host memory of the caller); n points in all
+struct SnapGeom { long T, M; const int64_t* off; long n; };
+static int snap_geom_check(const nif_ctx* c, const void* rows, int64_t T, const void* x, const int64_t* offsets, int64_t M,
+                           bool outputs_present, SnapGeom* g) {
   if (!c || !rows || T <= 0 || (offsets ? offsets[0] != 0 : M < 0)) return fail(NIF_ERR_INVALID, "bad argument");
   if (offsets) for (int64_t t = 0; t < T; ++t) if (offsets[t + 1] < offsets[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
-  *n = offsets ? (long)offsets[T] : (long)(T * M);
-  if (*n > 0 && (!x || !u)) return fail(NIF_ERR_INVALID, "bad argument");
-  if (c->capturing) return fail(NIF_ERR_STATE, "nif_forward_snapshots: not capturable (inside nif_graph_begin / nif_graph_end)");
+  *g = SnapGeom{(long)T, (long)M, offsets, offsets ? (long)offsets[T] : (long)(T * M)};
+  if (g->n > 0 && (!x || !outputs_present)) return fail(NIF_ERR_INVALID, "bad argument");
   return NIF_OK;
 }
+// (the last check of every entry: the only refusal with NIF_ERR_STATE)
+static int snap_not_capturing(const nif_ctx* c, const char* who) {
+  if (c->capturing) return fail(NIF_ERR_STATE, std::string(who) + ": not capturable (inside nif_graph_begin / nif_graph_end)");
+  return NIF_OK;
+}
+// the versioned argument structs: each says whether one of its own reserved members is set
+static bool snap_reserved(const nif_encode_args& a) { return a.reserved0 != 0; }
+static bool snap_reserved(const nif_snapderiv_args& a) { return a.reserved0 || a.reserved1 || a.reserved2; }
+static bool snap_reserved(const nif_snapparam_args& a) { return a.reserved0 != 0; }
+template <class A>
+static int snap_args_check(const A* a, int version, const char* name) {
+  if (!a) return fail(NIF_ERR_INVALID, "null");
+  if (a->abi_version != version)
+    return fail(NIF_ERR_INVALID, std::string(name) + ": abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(version));
+  if (snap_reserved(*a) || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
+    return fail(NIF_ERR_INVALID, std::string(name) + ": reserved fields must be zero");
+  return NIF_OK;
+}
+// the output rows y_idx [ny] of a derivative call, as the gather kernels take them
+static int snap_y_index(const nif_ctx* c, const int32_t* y_idx, int ny, HessIdx* I) {
+  if (!y_idx || ny <= 0) return fail(NIF_ERR_INVALID, "bad argument");
+  if (ny > 16) return fail(NIF_ERR_INVALID, "y_index: at most 16 entries");
+  for (int i = 0; i < ny; ++i)
+    if (y_idx[i] < 0 || y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
+  I->ny = ny;
+  for (int i = 0; i < 16; ++i) I->y_idx[i] = i < ny ? y_idx[i] : 0;
+  return NIF_OK;
+}
+// The tangent kernels run exact products, a mixed policy's forward and ParameterNet do not: encode is refused under one, the derivative
+// calls when they are given latents.
+static int snap_policy_refusal(const nif_ctx* c, const char* who, bool latents) {
+  if (c->cfg.mixed_policy == NIF_POLICY_FLOAT32) return NIF_OK;
+  return fail(NIF_ERR_INVALID, std::string(who) + (latents ? ": latents are not built for the " : ": not built for the ") +
+                                   (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
+                                   " policy (the tangent kernels run exact products, the policy's " +
+                                   (latents ? "ParameterNet does not; pass p)" : "forward does not)"));
+}
+// What one chunk of snapshots may hold on the device (nif_set_option "snapshot_image_bytes", 0 = the default), and the snapshots of a
+// chunk at per_snapshot_bytes each: at least one, at most a launch grid's 65535
+#define NIF_SNAP_IMAGE_BYTES (256L << 20)
+static long snap_budget(const nif_ctx* c) { return c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES; }
+static long snap_chunk(const nif_ctx* c, long T, long per_snapshot_bytes) {
+  long tc = snap_budget(c) / per_snapshot_bytes;
+  if (tc > 65535) tc = 65535;
+  if (tc > T) tc = T;
+  return tc < 1 ? 1 : tc;
+}
+// The chunks of at most tc_max snapshots of a call, the empty ones skipped: for (SnapWalk k{g, tc_max}; k.next();) sees the snapshots
+// t0 .. t0 + tc, n_pts points in all and mmax in the longest
+struct SnapWalk {
+  SnapGeom g; long tc_max;
+  long t0 = 0, tc = 0, mmax = 0, n_pts = 0;
+  bool next() {
+    for (t0 += tc; t0 < g.T; t0 += tc) {
+      tc = g.T - t0 < tc_max ? g.T - t0 : tc_max;
+      mmax = g.M; n_pts = tc * g.M;
+      if (g.off) {
+        mmax = 0; n_pts = g.off[t0 + tc] - g.off[t0];
+        for (long t = t0; t < t0 + tc; ++t) if (g.off[t + 1] - g.off[t] > mmax) mmax = g.off[t + 1] - g.off[t];
+      }
+      if (n_pts) return true;
+    }
+    return false;
+  }
+};
+static long snap_r4(long f) { return (f + 3) & ~3L; }
+// The routes of a call and its slice of c->snap, one buffer with one growth: [offsets (ragged) | latent rows (from p) | the caller's extra
+// head floats | the table (the point-wise route, or a shared mesh in front of a point kernel) or the combined nets of one chunk]
+struct SnapPlan {
+  bool pointwise;      // the point-wise kernels on the device-built [p_t | x] table, the ParameterNet per point (snap_pointwise nets, from p)
+  bool combined;       // hypernetwork classes: the snapshot kernels on combined r = 0 nets, chunk by chunk
+  bool phi_dot;        // last-layer class on a shared mesh: the ShapeNet once over the mesh, contracted with every snapshot's coefficients
+  bool table;          // (else: the point kernels behind latent tiles built on the device)
+  long off_f, lat_f, head_f;
+  float *lat, *extra, *body;      // the latent rows, the extra head floats, the table or the combined nets
+  SnapArgs sn;         // k_snap's expansion arguments: the geometry, x, the offsets on the device and the table
+};
+// phi_dot_ok / combined_ok: whether the caller's kernels have that form for this net
+static void snap_routes(const nif_ctx* c, const SnapGeom& g, bool lat_in, bool phi_dot_ok, bool combined_ok, SnapPlan* P) {
+  const bool ll = c->kind == NIF_KIND_LASTLAYER;
+  P->pointwise = snap_pointwise(c) && !lat_in;        // (given latents never meet the ParameterNet: nothing of it to reproduce)
+  P->combined = !ll && !snap_pointwise(c) && combined_ok;
+  P->phi_dot = ll && !g.off && !snap_pointwise(c) && phi_dot_ok;
+  P->table = P->pointwise || (!g.off && !P->phi_dot && !P->combined);
+}
+// the tiles of c->Z (and of the other point workspaces) that a route fills
+static int snap_point_capacity(nif_ctx* c, const SnapGeom& g, const SnapPlan& P) {
+  return ensure_capacity(c, P.combined ? g.T : (P.phi_dot ? (g.T > g.M ? g.T : g.M) : (g.n > g.T ? g.n : g.T)), false);
+}
+// Behind snap_routes: grows c->snap (and, with reserve_points, the point workspaces: the parameter-derivative call sizes those behind
+// its point-wise return), uploads the offsets, lays out the slice.  tab_pi: the parameter columns in front of the table's coordinates
+static int snap_plan_reserve(nif_ctx* c, const SnapGeom& g, const float* x, bool lat_in, int tab_pi, long extra_f, long combined_f,
+                             bool reserve_points, SnapPlan* P) {
+  P->off_f = g.off ? 2 * (g.T + 1) : 0;
+  P->lat_f = (P->pointwise || lat_in) ? 0 : g.T * c->r;
+  P->head_f = snap_r4(P->off_f + P->lat_f + extra_f);
+  const long tab_f = P->table ? g.n * (tab_pi + c->si) : (P->combined ? combined_f : 0);
+  int rc = c->snap.reserve(c, P->head_f + tab_f + 1); if (rc) return rc;
+  if (reserve_points) { rc = snap_point_capacity(c, g, *P); if (rc) return rc; }
+  P->lat = c->snap + P->off_f; P->extra = P->lat + P->lat_f; P->body = c->snap + P->head_f;
+  SnapArgs& sn = P->sn;
+  memset(&sn, 0, sizeof(sn));
+  sn.T = g.T; sn.M = g.M; sn.n = g.n; sn.pi = tab_pi; sn.si = c->si; sn.r = c->r; sn.x = x;
+  if (g.off) {      // (host memory of the caller: consumed before this returns)
+    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
+    HIPCHK(hipMemcpyAsync(c->snap.p, g.off, sizeof(int64_t) * (size_t)(g.T + 1), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
+  }
+  if (P->table) sn.table = P->body;
+  return NIF_OK;
+}
+// rows p [T][pi] -> the latent rows dst [T][r]: the ParameterNet over the T rows, its output tiles back as rows
+static void snap_latents_from_p(nif_ctx* c, const float* rows, long T, float* dst) {
+  PNetArgs pa; fill_pnet(c, pa, rows, T); pa.ncol = c->pi;
+  { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st); }
+  launch_tiles_to_rows(c->Z, T, c->r, dst, c->st);
+}
+// A chunk's combined nets as the dense r = 0 nets the snapshot kernels read: slot vectors w [tc][po], snapshot y's planes wstride units
+// behind snapshot 0's (the caller sets the plane pointers of its kernel's format)
+static void snap_r0_net(SNetArgs& sa, const float* w, const SnapPlan& P, const SnapWalk& k, long wstride) {
+  sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr;
+  sa.snap_off = P.sn.offsets ? P.sn.offsets + k.t0 : nullptr; sa.snap_M = k.g.M; sa.snap_wstride = wstride; sa.snap_T = (int)k.tc;
+}
+// The staging of a host-pointer entry: segments of c->snap_io, each rounded to whole float4s.  in: uploaded by snap_stage_in, which
+// also assigns dev; out: downloaded by snap_stage_out (which waits for the stream); n floats
+struct SnapSeg { const float* in; float* out; long n; float* dev; };
+static int snap_stage_in(nif_ctx* c, SnapSeg* s, int k) {
+  long f = 4;
+  for (int i = 0; i < k; ++i) f += snap_r4(s[i].n);
+  int rc = c->snap_io.reserve(c, f); if (rc) return rc;
+  float* q = c->snap_io.p;
+  for (int i = 0; i < k; q += snap_r4(s[i].n), ++i) {
+    s[i].dev = q;
+    if (s[i].in && s[i].n) HIPCHK(hipMemcpyAsync(q, s[i].in, sizeof(float) * (size_t)s[i].n, hipMemcpyHostToDevice, c->st));
+  }
+  return NIF_OK;
+}
+static int snap_stage_out(nif_ctx* c, const SnapSeg* s, int k) {
+  for (int i = 0; i < k; ++i)
+    if (s[i].out && s[i].n) HIPCHK(hipMemcpyAsync(s[i].out, s[i].dev, sizeof(float) * (size_t)s[i].n, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+
 // Hypernetwork classes on k_snet4: every point of snapshot t sees the same combined matrices W_t = sum_k lat_k(t) M^(k), so the snapshot is a
 // dense r = 0 net.  Per chunk of snapshots: the slot vectors w_t in fp32 from theta (the latent-to-weights kernel), their hidden matrices
 // packed from w_t in the forward kernel's chunk format (one launch per hidden matrix over the whole chunk), one forward launch.
-// buf: what is left of c->snap (sized by snap_combined_floats for the same tc).
-#define NIF_SNAP_IMAGE_BYTES (256L << 20)
-static long snap_r4(long f) { return (f + 3) & ~3L; }
+// P.body is sized by snap_combined_floats for the same tc_max.
 // bytes of one combined hidden matrix's forward / adjoint image (SIREN nets: the half pairs, class NIF: the split groups), and of
 // one snapshot: [slot vector | per hidden matrix: both images + its scale pair]
 static void snap_combined_sizes(const nif_ctx* c, long* fb, long* bb, long* per_bytes) {
@@ -799,35 +953,21 @@ static void snap_combined_sizes(const nif_ctx* c, long* fb, long* bb, long* per_
   *bb = plane_mat_bytes(set, PLANE_BWD, c->n, 0);
   *per_bytes = sizeof(float) * c->po + (long)c->nh * (*fb + *bb + 2 * sizeof(float));
 }
-static long snap_chunk(const nif_ctx* c, long T) {
-  long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per);
-  long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
-  if (tc > 65535) tc = 65535;
-  if (tc > T) tc = T;
-  return tc < 1 ? 1 : tc;
-}
 static long snap_combined_floats(const nif_ctx* c, long tc) {
   long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per);
   return snap_r4(tc * c->po) + snap_r4(2L * c->nh * tc) + tc * c->nh * (fb + bb) / (long)sizeof(float) + 4;
 }
-static int snap_combined(nif_ctx* c, float* buf, long tc_max, const float* lat, long T, const float* x, const long* off_dev,
-                         const int64_t* off_host, long M, float* u) {
+static int snap_combined(nif_ctx* c, const SnapPlan& P, const SnapGeom& g, long tc_max, const float* lat, const float* x, float* u) {
   const bool siren = c->kind != NIF_KIND_NIF;
   long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per);
-  float* w = buf;
+  float* w = P.body;
   float* ws = w + snap_r4(tc_max * c->po);
   char* WF = reinterpret_cast<char*>(ws + snap_r4(2L * c->nh * tc_max));
   char* WB = WF + (size_t)tc_max * c->nh * fb;
   const int NBL = snet3_nbl(c->n);
-  for (long t0 = 0; t0 < T; t0 += tc_max) {
-    const long tc = T - t0 < tc_max ? T - t0 : tc_max;
-    long mmax = M, n_pts = tc * M;
-    if (off_host) {
-      mmax = 0; n_pts = off_host[t0 + tc] - off_host[t0];
-      for (long t = t0; t < t0 + tc; ++t) if (off_host[t + 1] - off_host[t] > mmax) mmax = off_host[t + 1] - off_host[t];
-    }
-    if (n_pts == 0) continue;
-    SNetArgs sa; fill_snet(c, sa, x, c->si, 0, n_pts);
+  for (SnapWalk k{g, tc_max}; k.next();) {
+    const long t0 = k.t0, tc = k.tc;
+    SNetArgs sa; fill_snet(c, sa, x, c->si, 0, k.n_pts);
     {
       ProfScope p_(c, NIF_PROF_PACK);
       launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
@@ -839,75 +979,61 @@ static int snap_combined(nif_ctx* c, float* buf, long tc_max, const float* lat, 
         launch_pack_planes(job, c->st);
       }
     }
-    sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr;
+    snap_r0_net(sa, w, P, k, c->nh * fb / PLANE_UNIT_BYTES);
     sa.WF4 = WF; sa.wscale = siren ? ws : nullptr;
-    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * fb / PLANE_UNIT_BYTES; sa.snap_T = (int)tc;
-    sa.u_out = off_dev ? u : u + t0 * M * c->so;
+    sa.u_out = g.off ? u : u + t0 * g.M * c->so;
     ProfScope p_(c, NIF_PROF_SNET_FWD);
-    if (launch_snet4_snap(sa, tc, mmax, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no snapshot form of k_snet4 for this net");
+    if (launch_snet4_snap(sa, tc, k.mmax, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no snapshot form of k_snet4 for this net");
   }
   HIPCHK(hipGetLastError());
   return NIF_OK;
 }
 
+static int snap_check(const nif_ctx* c, const void* rows, int64_t T, const void* x, const int64_t* offsets, int64_t M, const void* u,
+                      SnapGeom* g) {
+  int rc = snap_geom_check(c, rows, T, x, offsets, M, u != nullptr, g); if (rc) return rc;
+  return snap_not_capturing(c, "nif_forward_snapshots");
+}
 extern "C" int nif_forward_snapshots_dev(nif_ctx* c, const float* rows, int32_t rows_are_latent, int64_t T, const float* x,
                                          const int64_t* offsets, int64_t M, float* u) {
-  long n = 0;
-  int rc = snap_check(c, rows, T, x, offsets, M, u, &n); if (rc) return rc;
+  SnapGeom g;
+  int rc = snap_check(c, rows, T, x, offsets, M, u, &g); if (rc) return rc;
   NIF_ENTER(c, NIF_FLUSH_TAIL)
   rc = ensure_packed(c); if (rc) return rc;
-  if (n == 0) return NIF_OK;
-  const bool lat_in = rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
-  const bool pointwise = snap_pointwise(c) && !lat_in;        // (given latents never meet the ParameterNet: nothing of it to reproduce)
-  const bool phi_dot = ll && !offsets && !snap_pointwise(c) && phi_dot_supported(c->r, c->so);
-  // one buffer, one growth: [offsets (ragged) | latent rows (from p) | the table (pointwise, or a shared mesh in front of a point
-  // kernel) or the combined nets of one chunk of snapshots]
-  const long off_f = offsets ? 2 * (T + 1) : 0, lat_f = (pointwise || lat_in) ? 0 : T * c->r;
-  const bool combined = !ll && !snap_pointwise(c) && c->use_snet4;
-  const bool table = pointwise || (!offsets && !phi_dot && !combined);
-  const long tc_max = combined ? snap_chunk(c, T) : 0;
-  const long tab_f = table ? n * (c->pi + c->si) : (combined ? snap_combined_floats(c, tc_max) : 0);
-  rc = c->snap.reserve(c, snap_r4(off_f + lat_f) + tab_f + 1); if (rc) return rc;
-  rc = ensure_capacity(c, combined ? T : (phi_dot ? (T > M ? T : M) : (n > T ? n : T)), false); if (rc) return rc;
-  SnapArgs sn; memset(&sn, 0, sizeof(sn));
-  sn.T = T; sn.M = M; sn.n = n; sn.pi = c->pi; sn.si = c->si; sn.r = c->r; sn.x = x;
-  if (offsets) {      // (host memory of the caller: consumed before this returns)
-    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
-    HIPCHK(hipMemcpyAsync(c->snap.p, offsets, sizeof(int64_t) * (size_t)(T + 1), hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
-  }
-  if (table) sn.table = c->snap + snap_r4(off_f + lat_f);
-  if (pointwise) {
+  if (g.n == 0) return NIF_OK;
+  const bool lat_in = rows_are_latent != 0;
+  SnapPlan P;
+  snap_routes(c, g, lat_in, phi_dot_supported(c->r, c->so), c->use_snet4, &P);
+  long tc_max = 0;
+  if (P.combined) { long fb, bb, per; snap_combined_sizes(c, &fb, &bb, &per); tc_max = snap_chunk(c, g.T, per); }
+  // (the table always carries the parameter columns here: forward_rows reads it in the full model's layout on either route)
+  rc = snap_plan_reserve(c, g, x, lat_in, c->pi, 0, P.combined ? snap_combined_floats(c, tc_max) : 0, true, &P); if (rc) return rc;
+  SnapArgs& sn = P.sn;
+  if (P.pointwise) {
     sn.p = rows;
     launch_snap_expand(sn, c->st);
-    return forward_rows(c, sn.table, c->pi + c->si, c->pi, n, u, true);
+    return forward_rows(c, sn.table, c->pi + c->si, c->pi, g.n, u, true);
   }
   const float* lat = rows;
-  if (!lat_in) {      // the ParameterNet over the T rows, its output back as rows [T][r]
-    PNetArgs pa; fill_pnet(c, pa, rows, T); pa.ncol = c->pi;
-    { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st); }
-    launch_tiles_to_rows(c->Z, T, c->r, c->snap + off_f, c->st);
-    lat = c->snap + off_f;
-  }
-  if (combined) return snap_combined(c, c->snap + snap_r4(off_f + lat_f), tc_max, lat, T, x, sn.offsets, offsets, M, u);
-  if (phi_dot) {      // one ShapeNet pass over the mesh for all snapshots
+  if (!lat_in) { snap_latents_from_p(c, rows, g.T, P.lat); lat = P.lat; }
+  if (P.combined) return snap_combined(c, P, g, tc_max, lat, x, u);
+  if (P.phi_dot) {      // one ShapeNet pass over the mesh for all snapshots
     ProfScope p_(c, NIF_PROF_SNET_FWD);
-    if (c->use_wide) wide_forward(c, x, c->si, 0, M, false);
-    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, M); launch_pnet(ma, c->NB, false, c->st); }
-    launch_phi_dot(c->PHI, lat, c->theta + c->ll_bias, T, M, c->r, c->so, u, c->st);
+    ll_phi_pass(c, x, c->si, 0, g.M);
+    launch_phi_dot(c->PHI, lat, c->theta + c->ll_bias, g.T, g.M, c->r, c->so, u, c->st);
     HIPCHK(hipGetLastError());
     return NIF_OK;
   }
   sn.lat = lat; sn.Z = c->Z;
   launch_snap_expand(sn, c->st);
-  if (table) return forward_rows(c, sn.table, c->pi + c->si, c->pi, n, u, false);
-  return forward_rows(c, x, c->si, 0, n, u, false);
+  if (P.table) return forward_rows(c, sn.table, c->pi + c->si, c->pi, g.n, u, false);
+  return forward_rows(c, x, c->si, 0, g.n, u, false);
 }
 extern "C" int nif_forward_snapshots(nif_ctx* c, const float* rows, int32_t rows_are_latent, int64_t T, const float* x,
                                      const int64_t* offsets, int64_t M, float* u) {
-  long n = 0;
-  int rc = snap_check(c, rows, T, x, offsets, M, u, &n); if (rc) return rc;
+  SnapGeom g;
+  int rc = snap_check(c, rows, T, x, offsets, M, u, &g); if (rc) return rc;
+  const long n = g.n;
   NIF_ENTER(c, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
   if (n == 0) return ensure_packed(c);
@@ -921,25 +1047,14 @@ extern "C" int nif_forward_snapshots(nif_ctx* c, const float* rows, int32_t rows
 }
 
 // ---- per-snapshot normal equations in the latent (k_encode.hip, include/nif_hip_encode.h) --------------------------
-static int enc_check(const nif_encode_args* a, long* n) {
-  if (!a) return fail(NIF_ERR_INVALID, "null");
-  if (a->abi_version != NIF_ENCODE_ABI_VERSION)
-    return fail(NIF_ERR_INVALID, "nif_encode_args: abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(NIF_ENCODE_ABI_VERSION));
-  if (a->reserved0 || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
-    return fail(NIF_ERR_INVALID, "nif_encode_args: reserved fields must be zero");
+static int enc_check(const nif_encode_args* a, SnapGeom* g) {
+  int rc = snap_args_check(a, NIF_ENCODE_ABI_VERSION, "nif_encode_args"); if (rc) return rc;
   const nif_ctx* c = a->ctx;
-  const int64_t* off = a->offsets_host;
-  if (!c || !a->latents || !a->S_out || a->T <= 0 || (off ? off[0] != 0 : a->M < 0)) return fail(NIF_ERR_INVALID, "bad argument");
-  if (off) for (int64_t t = 0; t < a->T; ++t) if (off[t + 1] < off[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
-  *n = off ? (long)off[a->T] : (long)(a->T * a->M);
-  if (*n > 0 && (!a->x || !a->y)) return fail(NIF_ERR_INVALID, "bad argument");
-  if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
-    return fail(NIF_ERR_INVALID, std::string("nif_snapshot_normal_eq: not built for the ") +
-                                     (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
-                                     " policy (the tangent kernels run exact products, the policy's forward does not)");
+  rc = snap_geom_check(c, a->latents, a->T, a->x, a->offsets_host, a->M, a->y != nullptr, g); if (rc) return rc;
+  if (!a->S_out) return fail(NIF_ERR_INVALID, "bad argument");
+  rc = snap_policy_refusal(c, "nif_snapshot_normal_eq", false); if (rc) return rc;
   if (c->r > 64) return fail(NIF_ERR_INVALID, "nif_snapshot_normal_eq: latent_dim " + std::to_string(c->r) + " > 64");
-  if (c->capturing) return fail(NIF_ERR_STATE, "nif_snapshot_normal_eq: not capturable (inside nif_graph_begin / nif_graph_end)");
-  return NIF_OK;
+  return snap_not_capturing(c, "nif_snapshot_normal_eq");
 }
 // floats per padded point of a chunk: what encode holds in c->enc, and for the last-layer class what ensure_capacity holds besides
 static long enc_point_floats(const nif_ctx* c) {
@@ -947,8 +1062,9 @@ static long enc_point_floats(const nif_ctx* c) {
   return 2L * c->r + c->si + (long)c->so * c->r + c->so;
 }
 extern "C" int nif_snapshot_normal_eq_dev(const nif_encode_args* a) {
-  long n = 0;
-  int rc = enc_check(a, &n); if (rc) return rc;
+  SnapGeom g;
+  int rc = enc_check(a, &g); if (rc) return rc;
+  const long n = g.n;
   nif_ctx* c = a->ctx;
   NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
   rc = ensure_packed(c); if (rc) return rc;
@@ -978,8 +1094,7 @@ extern "C" int nif_snapshot_normal_eq_dev(const nif_encode_args* a) {
   offs[T] = n;
   // chunks of whole snapshots within the budget of nif_forward_snapshots' images (at least one snapshot each)
   const long ppf = enc_point_floats(c);
-  const long budget = c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES;
-  long tiles_budget = budget / (long)(sizeof(float) * 32 * ppf);
+  long tiles_budget = snap_budget(c) / (long)(sizeof(float) * 32 * ppf);
   if (tiles_budget < 1) tiles_budget = 1;
   std::vector<long> cuts{0};
   long tiles_max = 0;
@@ -1014,8 +1129,7 @@ extern "C" int nif_snapshot_normal_eq_dev(const nif_encode_args* a) {
   else { ea.dydx = dydx; ea.u = u; }
   auto phi_pass = [&](const float* xs, long B) {      // x -> phi of B points into c->PHI, as nif_x_to_phi runs it
     ProfScope p_(c, NIF_PROF_SNET_FWD);
-    if (c->use_wide) wide_forward(c, xs, si, 0, B, false);
-    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xs, si, 0, B); launch_pnet(ma, c->NB, false, c->st); }
+    ll_phi_pass(c, xs, si, 0, B);
   };
   if (shared_phi) phi_pass(a->x, M);
   for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
@@ -1049,8 +1163,9 @@ extern "C" int nif_snapshot_normal_eq_dev(const nif_encode_args* a) {
   return NIF_OK;
 }
 extern "C" int nif_snapshot_normal_eq(const nif_encode_args* a) {
-  long n = 0;
-  int rc = enc_check(a, &n); if (rc) return rc;
+  SnapGeom g;
+  int rc = enc_check(a, &g); if (rc) return rc;
+  const long n = g.n;
   nif_ctx* c = a->ctx;
   NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
@@ -1293,75 +1408,59 @@ extern "C" int nif_hessian(nif_ctx* c, const float* xin, int64_t B, const int32_
 }
 
 // ---- snapshot-wise derivatives (include/nif_hip_snapderiv.h) ---------------------------------------------------------
-static int sd_check(const nif_snapderiv_args* a, long* n) {
-  if (!a) return fail(NIF_ERR_INVALID, "null");
-  if (a->abi_version != NIF_SNAPDERIV_ABI_VERSION)
-    return fail(NIF_ERR_INVALID, "nif_snapderiv_args: abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(NIF_SNAPDERIV_ABI_VERSION));
-  if (a->reserved0 || a->reserved1 || a->reserved2 || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
-    return fail(NIF_ERR_INVALID, "nif_snapderiv_args: reserved fields must be zero");
+static int sd_check(const nif_snapderiv_args* a, SnapGeom* g, HessIdx* I) {
+  int rc = snap_args_check(a, NIF_SNAPDERIV_ABI_VERSION, "nif_snapderiv_args"); if (rc) return rc;
   const nif_ctx* c = a->ctx;
-  const int64_t* off = a->offsets_host;
-  if (!c || !a->rows || !a->y_idx || !a->x_idx || a->T <= 0 || a->ny <= 0 || a->nx <= 0 || (off ? off[0] != 0 : a->M < 0))
-    return fail(NIF_ERR_INVALID, "bad argument");
+  rc = snap_geom_check(c, a->rows, a->T, a->x, a->offsets_host, a->M, a->u && a->dudx && (a->order != 2 || a->d2udx2), g); if (rc) return rc;
   if (a->order != 1 && a->order != 2) return fail(NIF_ERR_INVALID, "nif_snapshot_derivatives: order must be 1 or 2");
-  if (off) for (int64_t t = 0; t < a->T; ++t) if (off[t + 1] < off[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
-  *n = off ? (long)off[a->T] : (long)(a->T * a->M);
-  if (*n > 0 && (!a->x || !a->u || !a->dudx || (a->order == 2 && !a->d2udx2))) return fail(NIF_ERR_INVALID, "bad argument");
-  if (a->ny > 16) return fail(NIF_ERR_INVALID, "y_index: at most 16 entries");
-  for (int i = 0; i < a->ny; ++i)
-    if (a->y_idx[i] < 0 || a->y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
+  rc = snap_y_index(c, a->y_idx, a->ny, I); if (rc) return rc;
+  if (!a->x_idx || a->nx <= 0) return fail(NIF_ERR_INVALID, "bad argument");
   for (int j = 0; j < a->nx; ++j) {
     if (a->x_idx[j] < 0 || a->x_idx[j] >= c->si) return fail(NIF_ERR_INVALID, "x_index out of range (0 <= j < si_dim: coordinates only)");
     for (int k = 0; k < j; ++k) if (a->x_idx[k] == a->x_idx[j]) return fail(NIF_ERR_INVALID, "x_index: an index is repeated");
   }
   if (a->nx > 16) return fail(NIF_ERR_INVALID, "HessianLayer: at most 16 coordinate and 16 parameter columns in x_index");
   { const int rcw = wide_refused(c, "nif_snapshot_derivatives"); if (rcw) return rcw; }
-  if (c->capturing) return fail(NIF_ERR_STATE, "nif_snapshot_derivatives: not capturable (inside nif_graph_begin / nif_graph_end)");
-  return NIF_OK;
+  return snap_not_capturing(c, "nif_snapshot_derivatives");
 }
-// one snapshot of the combined path: its slot vector and the forward f32 planes of its hidden matrices (the format k_jac reads)
+// One snapshot of the tangent kernels' combined path: its slot vector and the forward f32 planes of its hidden matrices (the format
+// k_jac reads), each with g more beside it for the direction streams of a launch group (k_jac_wt; the coordinate derivatives: g = 0):
+// slot vectors [1 + g][tc][po], then per snapshot and hidden matrix the 1 + g planes [W_j | W'_0,j | ..]
 static long sd_plane_f32x4(const nif_ctx* c) { return plane_f32x4(PLANES_T16, snet3_nbl(c->n)); }
-static long sd_chunk(const nif_ctx* c, long T) {
-  const long per = (long)sizeof(float) * c->po + (long)c->nh * sd_plane_f32x4(c) * (long)sizeof(f32x4);
-  long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
-  if (tc > 65535) tc = 65535;
-  if (tc > T) tc = T;
-  return tc < 1 ? 1 : tc;
+static long sp_snapshot_bytes(const nif_ctx* c, int g) {
+  return (1 + g) * ((long)sizeof(float) * c->po + (long)c->nh * sd_plane_f32x4(c) * (long)sizeof(f32x4));
 }
-static long sd_combined_floats(const nif_ctx* c, long tc) { return snap_r4(tc * c->po) + tc * c->nh * sd_plane_f32x4(c) * 4 + 4; }
-// Hypernetwork classes on k_jac_snap.  Per chunk of snapshots: the slot vectors w_t in fp32 from theta, their hidden matrices packed
-// from w_t (one launch per hidden matrix over the chunk), then one launch per seed group over the chunk.  The kernels leave every
-// output row [n][so][nx] / [n][so][nx][nx] in c->d_b / c->d_c; the rows y_idx are gathered behind the last chunk.
-static int sd_combined(nif_ctx* c, const nif_snapderiv_args* a, float* buf, long tc_max, const float* lat, const long* off_dev, long n,
+static long sp_combined_floats(const nif_ctx* c, long tc, int g) { return snap_r4((1 + g) * tc * c->po) + (1 + g) * tc * c->nh * sd_plane_f32x4(c) * 4 + 4; }
+// the slot vectors w [tc][po] in fp32 from the latent rows of a chunk and their hidden matrices as f32 planes (one launch per hidden
+// matrix over the chunk): matrix j of snapshot y at WF + (y nh + j) ps planes
+static void snap_pack_f32(nif_ctx* c, const float* lat, long tc, float* w, f32x4* WF, int ps) {
+  const long plane_s = sd_plane_f32x4(c);
+  ProfScope p_(c, NIF_PROF_PACK);
+  launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat, tc, w, c->st);
+  for (int j = 0; j < c->nh; ++j)
+    launch_pack16_fwd_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, snet3_nbl(c->n), WF + (long)j * ps * plane_s,
+                            c->nh * ps * plane_s, c->st);
+}
+// Hypernetwork classes on k_jac_snap.  Per chunk of snapshots: the slot vectors and planes (snap_pack_f32), then one launch per seed
+// group over the chunk.  The kernels leave every output row [n][so][nx] / [n][so][nx][nx] in c->d_b / c->d_c; the rows y_idx are
+// gathered behind the last chunk.
+static int sd_combined(nif_ctx* c, const nif_snapderiv_args* a, const SnapPlan& P, const SnapGeom& g, long tc_max, const float* lat,
                        const HessIdx& I) {
-  const long T = a->T, M = a->M;
-  const int64_t* off_host = a->offsets_host;
-  const int nx = a->nx, so = c->so, NBL = snet3_nbl(c->n);
+  const long n = g.n;
+  const int nx = a->nx, so = c->so;
   const bool hess = a->order == 2;
   int rc = stage(c, c->d_b, nullptr, n * so * nx); if (rc) return rc;
   if (hess) { rc = stage(c, c->d_c, nullptr, n * so * nx * nx); if (rc) return rc; }
-  float* w = buf;
+  float* w = P.body;
   f32x4* WF = reinterpret_cast<f32x4*>(w + snap_r4(tc_max * c->po));
-  const long plane_s = sd_plane_f32x4(c);
-  for (long t0 = 0; t0 < T; t0 += tc_max) {
-    const long tc = T - t0 < tc_max ? T - t0 : tc_max;
-    long mmax = M, n_pts = tc * M;
-    if (off_host) {
-      mmax = 0; n_pts = off_host[t0 + tc] - off_host[t0];
-      for (long t = t0; t < t0 + tc; ++t) if (off_host[t + 1] - off_host[t] > mmax) mmax = off_host[t + 1] - off_host[t];
-    }
-    if (n_pts == 0) continue;
-    {
-      ProfScope p_(c, NIF_PROF_PACK);
-      launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
-      for (int j = 0; j < c->nh; ++j)
-        launch_pack16_fwd_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + (long)j * plane_s, c->nh * plane_s, c->st);
-    }
-    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, mmax);
-    sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr; sa.WF = WF; sa.WB = nullptr;
-    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * plane_s; sa.snap_T = (int)tc;
+  for (SnapWalk k{g, tc_max}; k.next();) {
+    const long tc = k.tc;
+    snap_pack_f32(c, lat + k.t0 * c->r, tc, w, WF, 1);
+    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, k.mmax);
+    snap_r0_net(sa, w, P, k, c->nh * sd_plane_f32x4(c));
+    sa.WF = WF; sa.WB = nullptr;
     // (ragged: the kernel rebases by the call's own offsets; shared mesh: by t M inside the chunk)
-    const long pb = off_dev ? 0 : t0 * M;
+    const long pb = g.off ? 0 : k.t0 * g.M;
     float* u = a->u + pb * so;
     float* fj = c->d_b + pb * so * nx;
     float* fh = hess ? c->d_c + pb * so * nx * nx : nullptr;
@@ -1388,67 +1487,42 @@ static int sd_combined(nif_ctx* c, const nif_snapderiv_args* a, float* buf, long
   return NIF_OK;
 }
 extern "C" int nif_snapshot_derivatives_dev(const nif_snapderiv_args* a) {
-  long n = 0;
-  int rc = sd_check(a, &n); if (rc) return rc;
+  SnapGeom g; HessIdx I;
+  int rc = sd_check(a, &g, &I); if (rc) return rc;
   nif_ctx* c = a->ctx;
   NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
   rc = ensure_packed(c); if (rc) return rc;
   const bool lat_in = a->rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
-  if (lat_in && c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
-    return fail(NIF_ERR_INVALID, std::string("nif_snapshot_derivatives: latents are not built for the ") +
-                                     (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
-                                     " policy (the tangent kernels run exact products, the policy's ParameterNet does not; pass p)");
+  if (lat_in) { rc = snap_policy_refusal(c, "nif_snapshot_derivatives", true); if (rc) return rc; }
   if (!ll && !c->jac_ok) return fail(NIF_ERR_INVALID, "HessianLayer: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
+  const long n = g.n, T = g.T, M = g.M;
   if (n == 0) return NIF_OK;
-  const long T = a->T, M = a->M;
-  const int64_t* offsets = a->offsets_host;
-  const int nx = a->nx, ny = a->ny, si = c->si;
+  const int nx = a->nx, ny = a->ny;
   const bool hess = a->order == 2;
-  HessIdx I; I.ny = ny;
-  for (int i = 0; i < 16; ++i) I.y_idx[i] = i < ny ? a->y_idx[i] : 0;
   int32_t xi[16];      // HessianLayer's numbering of the same columns
   for (int j = 0; j < nx; ++j) xi[j] = c->pi + a->x_idx[j];
   // the routes: the point-wise layers on the device-built [p_t | x] table; k_jac_snap on combined nets; the last-layer
   // class' tangents once per shared mesh; else the point-wise kernels behind latent tiles built on the device
-  const bool pointwise = snap_pointwise(c) && !lat_in;
-  const bool combined = !ll && !snap_pointwise(c);
-  const bool phi_dot = ll && !offsets && !snap_pointwise(c) && phi_dot_d2_supported(c->r, c->so, nx, hess);
-  const long tc_max = combined ? sd_chunk(c, T) : 0;
-  // one buffer, one growth: [offsets (ragged) | latent rows (from p) | the table, or the combined nets of one chunk of snapshots]
-  const long off_f = offsets ? 2 * (T + 1) : 0, lat_f = (pointwise || lat_in) ? 0 : T * c->r;
-  const bool table = pointwise || (!offsets && !phi_dot && !combined);
-  const int tcol = pointwise ? c->pi + si : si;
-  const long tab_f = table ? n * tcol : (combined ? sd_combined_floats(c, tc_max) : 0);
-  rc = c->snap.reserve(c, snap_r4(off_f + lat_f) + tab_f + 1); if (rc) return rc;
-  rc = ensure_capacity(c, combined ? T : (phi_dot ? (T > M ? T : M) : (n > T ? n : T)), false); if (rc) return rc;
+  SnapPlan P;
+  snap_routes(c, g, lat_in, phi_dot_d2_supported(c->r, c->so, nx, hess), true, &P);
+  const long tc_max = P.combined ? snap_chunk(c, T, sp_snapshot_bytes(c, 0)) : 0;
+  rc = snap_plan_reserve(c, g, a->x, lat_in, P.pointwise ? c->pi : 0, 0, P.combined ? sp_combined_floats(c, tc_max, 0) : 0, true, &P);
+  if (rc) return rc;
   float* d2 = a->d2udx2;
-  if (!hess && !combined) {      // these routes run the second-order kernels at either order
-    rc = c->sd_tmp.reserve(c, (phi_dot ? 0 : n * ny * nx * nx) + 1); if (rc) return rc;
-    d2 = phi_dot ? nullptr : c->sd_tmp.p;
+  if (!hess && !P.combined) {      // these routes run the second-order kernels at either order
+    rc = c->sd_tmp.reserve(c, (P.phi_dot ? 0 : n * ny * nx * nx) + 1); if (rc) return rc;
+    d2 = P.phi_dot ? nullptr : c->sd_tmp.p;
   }
-  SnapArgs sn; memset(&sn, 0, sizeof(sn));
-  sn.T = T; sn.M = M; sn.n = n; sn.pi = pointwise ? c->pi : 0; sn.si = si; sn.r = c->r; sn.x = a->x;
-  if (offsets) {      // (host memory of the caller: consumed before this returns)
-    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
-    HIPCHK(hipMemcpyAsync(c->snap.p, offsets, sizeof(int64_t) * (size_t)(T + 1), hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
-  }
-  if (table) sn.table = c->snap + snap_r4(off_f + lat_f);
-  if (pointwise) {
+  SnapArgs& sn = P.sn;
+  if (P.pointwise) {
     sn.p = a->rows;
     launch_snap_expand(sn, c->st);
     return hessian_core(c, sn.table, n, a->y_idx, ny, xi, nx, a->u, a->dudx, d2);
   }
   const float* lat = a->rows;
-  if (!lat_in) {      // the ParameterNet over the T rows, its output back as rows [T][r]
-    PNetArgs pa; fill_pnet(c, pa, a->rows, T); pa.ncol = c->pi;
-    { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, false, c->st); }
-    launch_tiles_to_rows(c->Z, T, c->r, c->snap + off_f, c->st);
-    lat = c->snap + off_f;
-  }
-  if (combined) return sd_combined(c, a, c->snap + snap_r4(off_f + lat_f), tc_max, lat, sn.offsets, n, I);
-  if (phi_dot) {      // phi, phi', phi'' of the mesh once, contracted with every snapshot's coefficients
+  if (!lat_in) { snap_latents_from_p(c, a->rows, T, P.lat); lat = P.lat; }
+  if (P.combined) return sd_combined(c, a, P, g, tc_max, lat, I);
+  if (P.phi_dot) {      // phi, phi', phi'' of the mesh once, contracted with every snapshot's coefficients
     rc = hessian_core(c, a->x, M, a->y_idx, ny, xi, nx, nullptr, nullptr, nullptr, false, true); if (rc) return rc;
     ProfScope p_(c, NIF_PROF_SNET_FWD);
     launch_phi_dot_d2(c->d_d, c->d_b, hess ? c->d_c.p : nullptr, lat, c->theta + c->ll_bias, T, M, c->r, c->so, nx, I, a->u, a->dudx, d2, c->st);
@@ -1457,47 +1531,29 @@ extern "C" int nif_snapshot_derivatives_dev(const nif_snapderiv_args* a) {
   }
   sn.lat = lat; sn.Z = c->Z;
   launch_snap_expand(sn, c->st);
-  return hessian_core(c, table ? sn.table : a->x, n, a->y_idx, ny, xi, nx, a->u, a->dudx, d2, false);
+  return hessian_core(c, P.table ? sn.table : a->x, n, a->y_idx, ny, xi, nx, a->u, a->dudx, d2, false);
 }
 extern "C" int nif_snapshot_derivatives(const nif_snapderiv_args* a) {
-  long n = 0;
-  int rc = sd_check(a, &n); if (rc) return rc;
+  SnapGeom g; HessIdx I;
+  int rc = sd_check(a, &g, &I); if (rc) return rc;
   nif_ctx* c = a->ctx;
   NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
-  const long T = a->T;
-  const long f_rows = snap_r4(T * (a->rows_are_latent ? c->r : c->pi)), f_x = snap_r4((a->offsets_host ? n : (long)a->M) * c->si);
-  const long f_u = snap_r4(n * c->so), f_d = snap_r4(n * a->ny * a->nx), f_h = a->order == 2 ? f_d * a->nx : 0;
-  rc = c->sd_io.reserve(c, f_rows + f_x + f_u + f_d + f_h + 4); if (rc) return rc;
+  const long n = g.n, n_d = n * a->ny * a->nx;
+  SnapSeg s[5] = {{a->rows, nullptr, g.T * (a->rows_are_latent ? c->r : c->pi)}, {a->x, nullptr, (g.off ? n : g.M) * c->si},
+                  {nullptr, a->u, n * c->so}, {nullptr, a->dudx, n_d}, {nullptr, a->d2udx2, a->order == 2 ? n_d * a->nx : 0}};
+  rc = snap_stage_in(c, s, 5); if (rc) return rc;
   nif_snapderiv_args d = *a;
-  float* q = c->sd_io.p;
-  d.rows = q; q += f_rows;
-  d.x = q; q += f_x;
-  d.u = q; q += f_u;
-  d.dudx = q; q += f_d;
-  d.d2udx2 = q;
-  HIPCHK(hipMemcpyAsync(const_cast<float*>(d.rows), a->rows, sizeof(float) * (size_t)(T * (a->rows_are_latent ? c->r : c->pi)), hipMemcpyHostToDevice, c->st));
-  if (n > 0) HIPCHK(hipMemcpyAsync(const_cast<float*>(d.x), a->x, sizeof(float) * (size_t)((a->offsets_host ? n : (long)a->M) * c->si), hipMemcpyHostToDevice, c->st));
+  d.rows = s[0].dev; d.x = s[1].dev; d.u = s[2].dev; d.dudx = s[3].dev; d.d2udx2 = s[4].dev;
   rc = nif_snapshot_derivatives_dev(&d); if (rc) return rc;
-  if (n > 0) {
-    HIPCHK(hipMemcpyAsync(a->u, d.u, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(a->dudx, d.dudx, sizeof(float) * (size_t)(n * a->ny * a->nx), hipMemcpyDeviceToHost, c->st));
-    if (a->order == 2) HIPCHK(hipMemcpyAsync(a->d2udx2, d.d2udx2, sizeof(float) * (size_t)(n * a->ny * a->nx * a->nx), hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipStreamSynchronize(c->st));
-  return NIF_OK;
+  return snap_stage_out(c, s, 5);
 }
 
 // ---- snapshot-wise parameter derivatives (include/nif_hip_snapparam.h) ------------------------------------------------
-static int sp_check(const nif_snapparam_args* a, long* n) {
-  if (!a) return fail(NIF_ERR_INVALID, "null");
-  if (a->abi_version != NIF_SNAPPARAM_ABI_VERSION)
-    return fail(NIF_ERR_INVALID, "nif_snapparam_args: abi_version " + std::to_string(a->abi_version) + " != " + std::to_string(NIF_SNAPPARAM_ABI_VERSION));
-  if (a->reserved0 || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
-    return fail(NIF_ERR_INVALID, "nif_snapparam_args: reserved fields must be zero");
+static int sp_check(const nif_snapparam_args* a, SnapGeom* g, HessIdx* I) {
+  int rc = snap_args_check(a, NIF_SNAPPARAM_ABI_VERSION, "nif_snapparam_args"); if (rc) return rc;
   const nif_ctx* c = a->ctx;
-  const int64_t* off = a->offsets_host;
-  if (!c || !a->rows || !a->y_idx || a->T <= 0 || a->ny <= 0 || (off ? off[0] != 0 : a->M < 0)) return fail(NIF_ERR_INVALID, "bad argument");
+  rc = snap_geom_check(c, a->rows, a->T, a->x, a->offsets_host, a->M, a->u && a->dudp, g); if (rc) return rc;
   if (a->rows_are_latent) {
     if (!a->drows) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: latent rows need drows [T, nd, r]");
     if (a->p_idx || a->np) return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: p_idx / np go with rows [T, pi], not with latents");
@@ -1510,56 +1566,28 @@ static int sp_check(const nif_snapparam_args* a, long* n) {
       for (int k = 0; k < j; ++k) if (a->p_idx[k] == a->p_idx[j]) return fail(NIF_ERR_INVALID, "p_index: an index is repeated");
     }
   }
-  if (off) for (int64_t t = 0; t < a->T; ++t) if (off[t + 1] < off[t]) return fail(NIF_ERR_INVALID, "offsets must not decrease");
-  *n = off ? (long)off[a->T] : (long)(a->T * a->M);
-  if (*n > 0 && (!a->x || !a->u || !a->dudp)) return fail(NIF_ERR_INVALID, "bad argument");
-  if (a->ny > 16) return fail(NIF_ERR_INVALID, "y_index: at most 16 entries");
-  for (int i = 0; i < a->ny; ++i)
-    if (a->y_idx[i] < 0 || a->y_idx[i] >= c->so) return fail(NIF_ERR_INVALID, "y_index out of range");
-  if (c->capturing) return fail(NIF_ERR_STATE, "nif_snapshot_param_derivatives: not capturable (inside nif_graph_begin / nif_graph_end)");
-  return NIF_OK;
+  rc = snap_y_index(c, a->y_idx, a->ny, I); if (rc) return rc;
+  return snap_not_capturing(c, "nif_snapshot_param_derivatives");
 }
 constexpr int SP_GROUP = 3;      // direction streams of one launch (the tangent kernels' NIF_JAC_MAXSEED)
-// one snapshot of the weight-tangent path: the slot vectors w_t, wd_t,0 .. wd_t,g-1 and, per hidden matrix, the 1 + g forward f32 planes
-// [W_j | W'_0,j | ..] (the format k_jac reads); g = the directions of a launch group
-static long sp_chunk(const nif_ctx* c, long T, int g) {
-  const long per = (1 + g) * ((long)sizeof(float) * c->po + (long)c->nh * sd_plane_f32x4(c) * (long)sizeof(f32x4));
-  long tc = (c->opt_snap_bytes > 0 ? c->opt_snap_bytes : NIF_SNAP_IMAGE_BYTES) / per;
-  if (tc > 65535) tc = 65535;
-  if (tc > T) tc = T;
-  return tc < 1 ? 1 : tc;
-}
-static long sp_combined_floats(const nif_ctx* c, long tc, int g) { return snap_r4((1 + g) * tc * c->po) + (1 + g) * tc * c->nh * sd_plane_f32x4(c) * 4 + 4; }
 // Hypernetwork classes on k_jac_wt.  lat [T][r], D [nd][T][r] (direction-major).  Per chunk of snapshots: w_t and its planes once; per
 // group of g <= 3 directions the tangent slot vectors wd_t,d (k_dlatent_to_w), their planes beside W_j's, one launch.  The kernel leaves
 // every output row [n][so][nd] in c->d_b; the rows y_idx are gathered behind the last chunk.
-static int sp_combined(nif_ctx* c, const nif_snapparam_args* a, float* buf, long tc_max, int gmax, const float* lat, const float* D, int nd,
-                       const long* off_dev, long n, const HessIdx& I) {
-  const long T = a->T, M = a->M;
-  const int64_t* off_host = a->offsets_host;
+static int sp_combined(nif_ctx* c, const nif_snapparam_args* a, const SnapPlan& P, const SnapGeom& g_, long tc_max, int gmax, const float* lat,
+                       const float* D, int nd, const HessIdx& I) {
+  const long T = g_.T, n = g_.n;
   const int so = c->so, NBL = snet3_nbl(c->n), ps = 1 + gmax;
   int rc = stage(c, c->d_b, nullptr, n * so * nd); if (rc) return rc;
-  float* w = buf;                                   // [1 + gmax][tc_max][po]: w_t, then each stream's wd_t
+  float* w = P.body;                                // [1 + gmax][tc_max][po]: w_t, then each stream's wd_t
   f32x4* WF = reinterpret_cast<f32x4*>(w + snap_r4((long)ps * tc_max * c->po));
   const long plane_s = sd_plane_f32x4(c);
-  for (long t0 = 0; t0 < T; t0 += tc_max) {
-    const long tc = T - t0 < tc_max ? T - t0 : tc_max;
-    long mmax = M, n_pts = tc * M;
-    if (off_host) {
-      mmax = 0; n_pts = off_host[t0 + tc] - off_host[t0];
-      for (long t = t0; t < t0 + tc; ++t) if (off_host[t + 1] - off_host[t] > mmax) mmax = off_host[t + 1] - off_host[t];
-    }
-    if (n_pts == 0) continue;
-    {
-      ProfScope p_(c, NIF_PROF_PACK);
-      launch_latent_to_w(c->theta, c->last_w, c->last_b, c->r, c->po, lat + t0 * c->r, tc, w, c->st);
-      for (int j = 0; j < c->nh; ++j)
-        launch_pack16_fwd_batch(w, dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + (long)j * ps * plane_s, c->nh * ps * plane_s, c->st);
-    }
-    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, mmax);
-    sa.theta = w; sa.r = 0; sa.off_Wh = 0; sa.off_bh = 0; sa.Z = nullptr; sa.WF = WF; sa.WB = nullptr;
-    sa.snap_off = off_dev ? off_dev + t0 : nullptr; sa.snap_M = M; sa.snap_wstride = c->nh * ps * plane_s; sa.snap_T = (int)tc;
-    const long pb = off_dev ? 0 : t0 * M;      // (ragged: the kernel rebases by the call's own offsets; shared mesh: by t M inside the chunk)
+  for (SnapWalk k{g_, tc_max}; k.next();) {
+    const long t0 = k.t0, tc = k.tc;
+    snap_pack_f32(c, lat + t0 * c->r, tc, w, WF, ps);
+    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, k.mmax);
+    snap_r0_net(sa, w, P, k, c->nh * ps * plane_s);
+    sa.WF = WF; sa.WB = nullptr;
+    const long pb = g_.off ? 0 : t0 * g_.M;      // (ragged: the kernel rebases by the call's own offsets; shared mesh: by t M inside the chunk)
     for (int d0 = 0; d0 < nd; d0 += gmax) {
       const int g = nd - d0 < gmax ? nd - d0 : gmax;
       const float* wd[SP_GROUP] = {nullptr, nullptr, nullptr};
@@ -1584,53 +1612,36 @@ static int sp_combined(nif_ctx* c, const nif_snapparam_args* a, float* buf, long
   return NIF_OK;
 }
 extern "C" int nif_snapshot_param_derivatives_dev(const nif_snapparam_args* a) {
-  long n = 0;
-  int rc = sp_check(a, &n); if (rc) return rc;
+  SnapGeom g; HessIdx I;
+  int rc = sp_check(a, &g, &I); if (rc) return rc;
   nif_ctx* c = a->ctx;
   NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
   rc = ensure_packed(c); if (rc) return rc;
   const bool lat_in = a->rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
-  if (lat_in && c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
-    return fail(NIF_ERR_INVALID, std::string("nif_snapshot_param_derivatives: latents are not built for the ") +
-                                     (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") +
-                                     " policy (the tangent kernels run exact products, the policy's ParameterNet does not; pass p)");
-  const bool pointwise = snap_pointwise(c) && !lat_in;      // JacobianLayer's kernels on the device-built [p_t | x] table
+  if (lat_in) { rc = snap_policy_refusal(c, "nif_snapshot_param_derivatives", true); if (rc) return rc; }
+  const int nd = lat_in ? a->nd : a->np, si = c->si, r = c->r, so = c->so;
+  // the routes (DESIGN 2.9): JacobianLayer's kernels on the table; k_jac_wt on combined nets; the last-layer class' phi once per shared
+  // mesh; else the point-wise kernels behind latent and direction tiles built on the device
+  SnapPlan P;
+  snap_routes(c, g, lat_in, phi_dot_supported(r, so), true, &P);
+  const bool pointwise = P.pointwise, combined = P.combined, phi_dot = P.phi_dot, table = P.table;
   if (pointwise) { const int rcw = wide_refused(c, "JacobianLayer"); if (rcw) return rcw; }
   if (!ll && !c->jac_ok) return fail(NIF_ERR_INVALID, "JacobianLayer: one weight plane and the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
-  const bool combined = !ll && !snap_pointwise(c);          // k_jac_wt on combined nets
   if (combined) {
     SNetArgs probe; fill_snet(c, probe, nullptr, 0, 0, 32);
     if (!jac_wt_supported(probe))
       return fail(NIF_ERR_INVALID, "nif_snapshot_param_derivatives: one weight plane and four images of the small hyper-vectors of this shape exceed the 160 KB LDS of a CU");
   }
+  const long n = g.n, T = g.T, M = g.M;
   if (n == 0) return NIF_OK;
-  const long T = a->T, M = a->M;
-  const int64_t* offsets = a->offsets_host;
-  const int nd = lat_in ? a->nd : a->np, ny = a->ny, si = c->si, r = c->r, so = c->so;
-  HessIdx I; I.ny = ny;
-  for (int i = 0; i < 16; ++i) I.y_idx[i] = i < ny ? a->y_idx[i] : 0;
-  // the routes (DESIGN 2.9): JacobianLayer's kernels on the table; k_jac_wt on combined nets; the last-layer class' phi once per shared
-  // mesh; else the point-wise kernels behind latent and direction tiles built on the device
-  const bool phi_dot = ll && !pointwise && !offsets && phi_dot_supported(r, so);
   const int gmax = nd < SP_GROUP ? nd : SP_GROUP;
-  const long tc_max = combined ? sp_chunk(c, T, gmax) : 0;
-  // one buffer, one growth: [offsets (ragged) | latent rows (from p) | direction rows [nd][T][r] | so zeros | the table, or the
-  // combined nets of one chunk of snapshots]
-  const long off_f = offsets ? 2 * (T + 1) : 0, lat_f = (pointwise || lat_in) ? 0 : T * r, dir_f = pointwise ? 0 : (long)nd * T * r;
-  const long head_f = snap_r4(off_f + lat_f + dir_f + so);
-  const bool table = pointwise || (!offsets && !phi_dot && !combined);
-  const int tcol = pointwise ? c->pi + si : si;
-  const long tab_f = table ? n * tcol : (combined ? sp_combined_floats(c, tc_max, gmax) : 0);
-  rc = c->snap.reserve(c, head_f + tab_f + 1); if (rc) return rc;
-  SnapArgs sn; memset(&sn, 0, sizeof(sn));
-  sn.T = T; sn.M = M; sn.n = n; sn.pi = pointwise ? c->pi : 0; sn.si = si; sn.r = r; sn.x = a->x;
-  if (offsets) {      // (host memory of the caller: consumed before this returns)
-    static_assert(sizeof(long) == sizeof(int64_t), "offsets travel as they are");
-    HIPCHK(hipMemcpyAsync(c->snap.p, offsets, sizeof(int64_t) * (size_t)(T + 1), hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    sn.offsets = reinterpret_cast<const long*>(c->snap.p);
-  }
-  if (table) sn.table = c->snap + head_f;
+  const long tc_max = combined ? snap_chunk(c, T, sp_snapshot_bytes(c, gmax)) : 0;
+  // the extra head floats: [direction rows [nd][T][r] | so zeros].  The point workspaces are sized behind the point-wise return
+  // (jacobian_core sizes its own)
+  const long dir_f = pointwise ? 0 : (long)nd * T * r;
+  rc = snap_plan_reserve(c, g, a->x, lat_in, pointwise ? c->pi : 0, dir_f + so, combined ? sp_combined_floats(c, tc_max, gmax) : 0, false, &P);
+  if (rc) return rc;
+  SnapArgs& sn = P.sn;
   if (pointwise) {
     sn.p = a->rows;
     launch_snap_expand(sn, c->st);
@@ -1642,32 +1653,29 @@ extern "C" int nif_snapshot_param_derivatives_dev(const nif_snapparam_args* a) {
   }
   // ---- the latent and the directions of every snapshot: lat [T][r], D [nd][T][r] ------------------------------------------------------
   const long ttiles = (T + 31) / 32;
-  rc = ensure_capacity(c, combined ? T : (phi_dot ? (T > M ? T : M) : (n > T ? n : T)), false); if (rc) return rc;
+  rc = snap_point_capacity(c, g, P); if (rc) return rc;
   const float* lat = a->rows;
-  float* D = c->snap + off_f + lat_f;
+  float* D = P.extra;
   float* zero = D + dir_f;
   if (lat_in) launch_dir_rows(a->drows, T, nd, r, D, c->st);
-  else {      // the ParameterNet over the T rows and, per column, its input tangent (k_mlp_jac, as nif_jacobian runs it): back as rows
+  else {      // per column the ParameterNet's input tangent over the T rows (k_mlp_jac, as nif_jacobian runs it) back as rows, then the latents
     rc = ensure_packed_p32(c); if (rc) return rc;
     rc = c->d_c.reserve(c, ttiles * 32 * r); if (rc) return rc;
     PNetArgs pa; fill_pnet(c, pa, a->rows, T); pa.ncol = c->pi;
-    ProfScope p_(c, NIF_PROF_PNET_FWD);
     for (int j = 0; j < nd; ++j) {
       PNetArgs pj = pa; pj.Z = ll ? c->DA : c->DZ;      // (primal again into a scratch)
       launch_mlp_jac(pj, c->NSTB, a->p_idx[j], c->d_c, c->st);
       launch_tiles_to_rows(c->d_c, T, r, D + (long)j * T * r, c->st);
     }
-    launch_pnet(pa, c->NSTB, false, c->st);
-    launch_tiles_to_rows(c->Z, T, r, c->snap + off_f, c->st);
-    lat = c->snap + off_f;
+    snap_latents_from_p(c, a->rows, T, P.lat);
+    lat = P.lat;
   }
-  if (combined) return sp_combined(c, a, c->snap + head_f, tc_max, gmax, lat, D, nd, sn.offsets, n, I);
+  if (combined) return sp_combined(c, a, P, g, tc_max, gmax, lat, D, nd, I);
   if (phi_dot) {      // phi of the mesh once; u, and the same contraction over the nd T tangent coefficient rows without the bias
     HIPCHK(hipMemsetAsync(zero, 0, sizeof(float) * (size_t)so, c->st));
     rc = stage(c, c->d_b, nullptr, n * so * nd); if (rc) return rc;
     ProfScope p_(c, NIF_PROF_SNET_FWD);
-    if (c->use_wide) wide_forward(c, a->x, si, 0, M, false);
-    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, a->x, si, 0, M); launch_pnet(ma, c->NB, false, c->st); }
+    ll_phi_pass(c, a->x, si, 0, M);
     launch_phi_dot(c->PHI, lat, c->theta + c->ll_bias, T, M, r, so, a->u, c->st);
     launch_phi_dot(c->PHI, D, zero, (long)nd * T, M, r, so, c->d_b, c->st);
     launch_snapparam_gather(c->d_b, T, M, so, nd, I, a->dudp, c->st);
@@ -1684,8 +1692,7 @@ extern "C" int nif_snapshot_param_derivatives_dev(const nif_snapparam_args* a) {
   sn.table = nullptr;
   if (ll) {
     ProfScope p_(c, NIF_PROF_SNET_FWD);
-    if (c->use_wide) wide_forward(c, xg, si, 0, n, false);
-    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, xg, si, 0, n); launch_pnet(ma, c->NB, false, c->st); }
+    ll_phi_pass(c, xg, si, 0, n);
     LLArgs la; fill_ll(c, la, n); la.u_out = a->u;
     launch_ll_out(la, false, c->st);
     for (int d = 0; d < nd; ++d) {
@@ -1715,34 +1722,20 @@ extern "C" int nif_snapshot_param_derivatives_dev(const nif_snapparam_args* a) {
   return NIF_OK;
 }
 extern "C" int nif_snapshot_param_derivatives(const nif_snapparam_args* a) {
-  long n = 0;
-  int rc = sp_check(a, &n); if (rc) return rc;
+  SnapGeom g; HessIdx I;
+  int rc = sp_check(a, &g, &I); if (rc) return rc;
   nif_ctx* c = a->ctx;
   NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
   HIPCHK(hipStreamSynchronize(c->st));
-  const long T = a->T;
   const bool lat_in = a->rows_are_latent != 0;
-  const long nd = lat_in ? a->nd : a->np;
-  const long n_rows = T * (lat_in ? c->r : c->pi), n_dr = lat_in ? T * nd * c->r : 0, n_x = (a->offsets_host ? n : (long)a->M) * c->si;
-  const long f_rows = snap_r4(n_rows), f_dr = snap_r4(n_dr), f_x = snap_r4(n_x), f_u = snap_r4(n * c->so), f_d = snap_r4(n * a->ny * nd);
-  rc = c->sp_io.reserve(c, f_rows + f_dr + f_x + f_u + f_d + 4); if (rc) return rc;
+  const long n = g.n, nd = lat_in ? a->nd : a->np;
+  SnapSeg s[5] = {{a->rows, nullptr, g.T * (lat_in ? c->r : c->pi)}, {a->drows, nullptr, lat_in ? g.T * nd * c->r : 0},
+                  {a->x, nullptr, (g.off ? n : g.M) * c->si}, {nullptr, a->u, n * c->so}, {nullptr, a->dudp, n * a->ny * nd}};
+  rc = snap_stage_in(c, s, 5); if (rc) return rc;
   nif_snapparam_args d = *a;
-  float* q = c->sp_io.p;
-  d.rows = q; q += f_rows;
-  d.drows = lat_in ? q : nullptr; q += f_dr;
-  d.x = q; q += f_x;
-  d.u = q; q += f_u;
-  d.dudp = q;
-  HIPCHK(hipMemcpyAsync(const_cast<float*>(d.rows), a->rows, sizeof(float) * (size_t)n_rows, hipMemcpyHostToDevice, c->st));
-  if (lat_in) HIPCHK(hipMemcpyAsync(const_cast<float*>(d.drows), a->drows, sizeof(float) * (size_t)n_dr, hipMemcpyHostToDevice, c->st));
-  if (n > 0) HIPCHK(hipMemcpyAsync(const_cast<float*>(d.x), a->x, sizeof(float) * (size_t)n_x, hipMemcpyHostToDevice, c->st));
+  d.rows = s[0].dev; d.drows = lat_in ? s[1].dev : nullptr; d.x = s[2].dev; d.u = s[3].dev; d.dudp = s[4].dev;
   rc = nif_snapshot_param_derivatives_dev(&d); if (rc) return rc;
-  if (n > 0) {
-    HIPCHK(hipMemcpyAsync(a->u, d.u, sizeof(float) * (size_t)(n * c->so), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(a->dudp, d.dudp, sizeof(float) * (size_t)(n * a->ny * nd), hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipStreamSynchronize(c->st));
-  return NIF_OK;
+  return snap_stage_out(c, s, 5);
 }
 
 extern "C" int nif_pnet_latent(nif_ctx* c, const float* p, int64_t B, float* lr) {
@@ -1772,8 +1765,7 @@ extern "C" int nif_x_to_phi(nif_ctx* c, const float* x, int64_t B, float* phi) {
   rc = ensure_capacity(c, B, false); if (rc) return rc;
   rc = stage(c, c->d_a, x, B * c->si); if (rc) return rc;
   rc = stage(c, c->d_d, nullptr, B * c->so * c->r); if (rc) return rc;
-  if (c->use_wide) wide_forward(c, c->d_a, c->si, 0, B, false);
-  else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, c->d_a, c->si, 0, B); launch_pnet(ma, c->NB, false, c->st); }
+  ll_phi_pass(c, c->d_a, c->si, 0, B);
   launch_tiles_to_rows(c->PHI, B, c->so * c->r, c->d_d, c->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(phi, c->d_d, sizeof(float) * (size_t)(B * c->so * c->r), hipMemcpyDeviceToHost, c->st));
@@ -1809,8 +1801,7 @@ extern "C" int nif_shapenet_given_w_dev(nif_ctx* c, const float* x, const float*
   if (c->kind == NIF_KIND_LASTLAYER) {   // u = Dot(phi(x), w) + bias with caller-supplied w [B, r]
     int rc = ensure_packed(c); if (rc) return rc;
     rc = ensure_capacity(c, B, false); if (rc) return rc;
-    if (c->use_wide) wide_forward(c, x, c->si, 0, B, false);
-    else { ensure_ll_mlp_planes(c); PNetArgs ma; fill_snet_mlp(c, ma, x, c->si, 0, B); launch_pnet(ma, c->NB, false, c->st); }
+    ll_phi_pass(c, x, c->si, 0, B);
     launch_rows_to_tiles(w, B, c->r, c->Z, c->st);
     LLArgs la; fill_ll(c, la, B); la.u_out = u;
     launch_ll_out(la, false, c->st);

@@ -149,20 +149,19 @@ struct nif_ctx {
   hipEvent_t t0 = nullptr, t1 = nullptr;
   // staging for the host-pointer API
   DevBuf<float> d_a, d_b, d_c, d_d;
-  // snapshot-wise inference (nif_forward_snapshots*): [offsets | latent rows | table, or the combined nets of one chunk of snapshots:
-  // slot vectors, plane scales, packed planes] of one call, rebuilt by every call.  opt_snap_bytes: the chunk's budget
-  // (nif_set_option "snapshot_image_bytes", 0 = the default)
-  DevBuf<float> snap; long opt_snap_bytes = 0;
+  // the snapshot calls (nif_forward_snapshots*, nif_snapshot_derivatives*, nif_snapshot_param_derivatives*; nif_api.hip SnapPlan):
+  // [offsets | latent rows | the call's extra head rows | table, or the combined nets of one chunk of snapshots: slot vectors and
+  // packed planes] of one call, rebuilt by every call.  opt_snap_bytes: the chunk's budget (nif_set_option "snapshot_image_bytes",
+  // 0 = the default).  snap_io: the staging of the two derivative calls' host-pointer entries, [rows | .. | outputs] (calls on a
+  // context are serial; the forward and encode entries stage through d_a .. d_d and enc_S)
+  DevBuf<float> snap, snap_io; long opt_snap_bytes = 0;
   // per-snapshot normal equations (nif_snapshot_normal_eq*, k_encode.hip): [tile_start | offsets] of one call and the padded operands
   // [Z | unit pattern | xpad | dydx | u] of one chunk of snapshots (bounded by the same budget), rebuilt by every call; enc_S stages
   // the host-pointer entry's result
   DevBuf<float> enc; DevBuf<double> enc_S;
   // snapshot-wise derivatives (nif_snapshot_derivatives*): sd_tmp takes the second-order output of an order-1 call on the routes that
-  // run the second-order kernels anyway; sd_io stages the host-pointer entry's [rows | x | u | dudx | d2udx2]
-  DevBuf<float> sd_tmp, sd_io;
-  // snapshot-wise parameter derivatives (nif_snapshot_param_derivatives*): sp_io stages the host-pointer entry's [rows | drows | x | u |
-  // dudp]; everything else of a call lives in `snap` and the point workspaces
-  DevBuf<float> sp_io;
+  // run the second-order kernels anyway.  (The parameter derivatives keep everything in `snap` and the point workspaces.)
+  DevBuf<float> sd_tmp;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

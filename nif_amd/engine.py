@@ -279,110 +279,113 @@ class Engine(object):
         d.upload(x)
         return d
 
+    # The three pieces every snapshot call below is made of.  A mesh reaches an entry as (d_x, x_off, offsets, m, n): the device
+    # array of the coordinates and the float offset into it, the ragged offsets [T + 1] (else None, with m points per snapshot),
+    # n points in all.
+    def _snapshot_call(self, uploads, shapes, call, dtype=np.float32):
+        """The device round trip of one call: the row arrays `uploads` side by side in one device array d_r; call(d_r, outs) ->
+        the entry's return code, outs the device addresses of the outputs of `shapes`, side by side in another; the outputs back
+        as NumPy arrays.  A first output without elements (no points, or no snapshots) makes no call"""
+        outs = [np.empty(s, dtype=dtype) for s in shapes]
+        if not outs[0].size:
+            return outs
+        at = [0]
+        for o in outs:
+            at.append(at[-1] + o.size)
+        d_r = DeviceArray(self, sum(a.size for a in uploads))
+        d_o = (DeviceArray64 if dtype == np.float64 else DeviceArray)(self, at[-1])
+        try:
+            d_r.upload(np.concatenate([a.ravel() for a in uploads]))
+            check(call(d_r, [d_o.at(i) for i in at[:-1]]))
+            for o, i in zip(outs, at):
+                check(self.lib.nif_d2h(self.ctx, ptr(o), d_o.at(i), o.nbytes))
+        finally:
+            d_r.free(); d_o.free()
+        return outs
+
+    def _ragged(self, who, name, rows, xs, run):
+        """T coordinate arrays [M_t, si] concatenated on the device: run(d_x, 0, offsets, 0, n)"""
+        self._not_capturing(who)
+        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
+        if len(xs) != int(np.shape(rows)[0]):
+            raise ValueError("%s: %d rows for %d meshes" % (name, int(np.shape(rows)[0]), len(xs)))
+        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
+        n = int(offsets[-1])
+        d_x = DeviceArray(self, n * self.spec.si_dim) if n else None      # (no points: no call reads it)
+        try:
+            if n:
+                d_x.upload(np.concatenate(xs, axis=0))
+            return run(d_x, 0, offsets, 0, n)
+        finally:
+            if n:
+                d_x.free()
+
+    def _shared(self, rows, mesh, lo, hi, run):
+        """the points lo .. hi of a snapshot_mesh handle: run(mesh, x_off, None, m, n), every output [n, ...] back as [T, hi - lo, ...]"""
+        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
+        return tuple(o.reshape((t, m) + o.shape[1:]) for o in run(mesh, int(lo) * self.spec.si_dim, None, m, t * m))
+
+    def _snapshot_rows(self, rows, is_latent):
+        return self._rows(rows, self.spec.pi_hidden if is_latent else self.spec.pi_dim, "latent" if is_latent else "parameter inputs")
+
+    @staticmethod
+    def _snapshot_geometry(a, d_r, rows, is_latent, d_x, x_off, off, m, yi):
+        """the members that nif_snapderiv_args and nif_snapparam_args share"""
+        a.rows, a.rows_are_latent, a.T = d_r.at(0), 1 if is_latent else 0, rows.shape[0]
+        a.x, a.M = d_x.at(x_off), int(m)
+        a.offsets_host = None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64))
+        a.y_idx, a.ny = yi.ctypes.data_as(C.POINTER(C.c_int32)), yi.size
+
     def _snapshots(self, rows, is_latent, d_x, x_off, offsets, m, n):
         self._not_capturing()
-        rows = self._rows(rows, self.spec.pi_hidden if is_latent else self.spec.pi_dim, "latent" if is_latent else "parameter inputs")
-        so = self.spec.so_dim
-        out = np.empty((n, so), dtype=np.float32)
-        if not n:
-            return out
+        rows = self._snapshot_rows(rows, is_latent)
         off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        d_r, d_u = DeviceArray(self, rows.size), DeviceArray(self, n * so)
-        try:
-            d_r.upload(rows)
-            check(self.lib.nif_forward_snapshots_dev(self.ctx, d_r.at(0), 1 if is_latent else 0, rows.shape[0], d_x.at(x_off),
-                                                     None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64)), int(m), d_u.at(0)))
-            check(self.lib.nif_d2h(self.ctx, ptr(out), d_u.at(0), out.size * 4))
-        finally:
-            d_r.free(); d_u.free()
-        return out
+        return self._snapshot_call([rows], [(n, self.spec.so_dim)], lambda d_r, o: self.lib.nif_forward_snapshots_dev(
+            self.ctx, d_r.at(0), 1 if is_latent else 0, rows.shape[0], d_x.at(x_off),
+            None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64)), int(m), o[0]))
 
     def forward_snapshots(self, rows, is_latent, mesh, lo, hi):
         """rows [T, pi] (or [T, r] latents) on the points lo .. hi of a snapshot_mesh handle -> [T, hi - lo, so]"""
-        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
-        return self._snapshots(rows, is_latent, mesh, int(lo) * self.spec.si_dim, None, m, t * m).reshape(t, m, self.spec.so_dim)
+        return self._shared(rows, mesh, lo, hi, lambda *g: self._snapshots(rows, is_latent, *g))[0]
 
     def forward_snapshots_ragged(self, rows, is_latent, xs):
         """rows [T, .] and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> [sum M_t, so], snapshot after snapshot"""
-        self._not_capturing()
-        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
-        if len(xs) != int(np.shape(rows)[0]):
-            raise ValueError("forward_snapshots_ragged: %d rows for %d meshes" % (int(np.shape(rows)[0]), len(xs)))
-        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
-        n = int(offsets[-1])
-        if not n:
-            return np.empty((0, self.spec.so_dim), dtype=np.float32)
-        d_x = DeviceArray(self, n * self.spec.si_dim)
-        try:
-            d_x.upload(np.concatenate(xs, axis=0))
-            return self._snapshots(rows, is_latent, d_x, 0, offsets, 0, n)
-        finally:
-            d_x.free()
+        return self._ragged("nif_forward_snapshots", "forward_snapshots_ragged", rows, xs, lambda *g: self._snapshots(rows, is_latent, *g))[0]
 
     # ---- snapshot-wise derivatives (include/nif_hip_snapderiv.h; Model.predict_snapshot_derivatives plans the chunks) ----------
     def _snapshot_derivs(self, rows, is_latent, d_x, x_off, offsets, m, n, y_index, x_index, order):
         self._not_capturing("nif_snapshot_derivatives")
-        s = self.spec
-        rows = self._rows(rows, s.pi_hidden if is_latent else s.pi_dim, "latent" if is_latent else "parameter inputs")
+        rows = self._snapshot_rows(rows, is_latent)
         yi = np.ascontiguousarray(list(y_index), dtype=np.int32)
         xi = np.ascontiguousarray(list(x_index), dtype=np.int32)
         ny, nx = yi.size, xi.size
-        u = np.empty((n, s.so_dim), dtype=np.float32)
-        d = np.empty((n, ny, nx), dtype=np.float32)
-        h = np.empty((n, ny, nx, nx), dtype=np.float32) if order == 2 else None
-        if not n:
-            return (u, d) if h is None else (u, d, h)
         off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        d_r, d_o = DeviceArray(self, rows.size), DeviceArray(self, u.size + d.size + (0 if h is None else h.size))
-        try:
-            d_r.upload(rows)
+
+        def call(d_r, o):
             a = _lib.nif_snapderiv_args()
             a.abi_version, a.order, a.ctx = _lib.NIF_SNAPDERIV_ABI_VERSION, int(order), self.ctx
-            a.rows, a.rows_are_latent, a.T = d_r.at(0), 1 if is_latent else 0, rows.shape[0]
-            a.x, a.M = d_x.at(x_off), int(m)
-            a.offsets_host = None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64))
-            a.y_idx, a.ny = yi.ctypes.data_as(C.POINTER(C.c_int32)), ny
+            self._snapshot_geometry(a, d_r, rows, is_latent, d_x, x_off, off, m, yi)
             a.x_idx, a.nx = xi.ctypes.data_as(C.POINTER(C.c_int32)), nx
-            a.u, a.dudx = d_o.at(0), d_o.at(u.size)
-            a.d2udx2 = None if h is None else d_o.at(u.size + d.size)
-            check(self.lib.nif_snapshot_derivatives_dev(C.byref(a)))
-            check(self.lib.nif_d2h(self.ctx, ptr(u), d_o.at(0), u.size * 4))
-            check(self.lib.nif_d2h(self.ctx, ptr(d), d_o.at(u.size), d.size * 4))
-            if h is not None:
-                check(self.lib.nif_d2h(self.ctx, ptr(h), d_o.at(u.size + d.size), h.size * 4))
-        finally:
-            d_r.free(); d_o.free()
-        return (u, d) if h is None else (u, d, h)
+            a.u, a.dudx, a.d2udx2 = o[0], o[1], (o[2] if order == 2 else None)
+            return self.lib.nif_snapshot_derivatives_dev(C.byref(a))
+        return tuple(self._snapshot_call([rows], [(n, self.spec.so_dim), (n, ny, nx)] + ([(n, ny, nx, nx)] if order == 2 else []), call))
 
     def snapshot_derivatives(self, rows, is_latent, mesh, lo, hi, y_index, x_index, order):
         """rows [T, pi] (or [T, r] latents) on the points lo .. hi of a snapshot_mesh handle -> (u [T, hi - lo, so],
         dudx [T, hi - lo, ny, nx][, d2udx2 [T, hi - lo, ny, nx, nx]]); x_index counts coordinates from 0"""
-        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
-        outs = self._snapshot_derivs(rows, is_latent, mesh, int(lo) * self.spec.si_dim, None, m, t * m, y_index, x_index, order)
-        return tuple(o.reshape((t, m) + o.shape[1:]) for o in outs)
+        return self._shared(rows, mesh, lo, hi, lambda *g: self._snapshot_derivs(rows, is_latent, *g, y_index, x_index, order))
 
     def snapshot_derivatives_ragged(self, rows, is_latent, xs, y_index, x_index, order):
         """rows [T, .] and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> the same outputs [sum M_t, ...], snapshot after snapshot"""
-        self._not_capturing("nif_snapshot_derivatives")
-        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
-        if len(xs) != int(np.shape(rows)[0]):
-            raise ValueError("snapshot_derivatives_ragged: %d rows for %d meshes" % (int(np.shape(rows)[0]), len(xs)))
-        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
-        n = int(offsets[-1])
-        d_x = DeviceArray(self, max(n, 1) * self.spec.si_dim)
-        try:
-            if n:
-                d_x.upload(np.concatenate(xs, axis=0))
-            return self._snapshot_derivs(rows, is_latent, d_x, 0, offsets, 0, n, y_index, x_index, order)
-        finally:
-            d_x.free()
+        return self._ragged("nif_snapshot_derivatives", "snapshot_derivatives_ragged", rows, xs,
+                            lambda *g: self._snapshot_derivs(rows, is_latent, *g, y_index, x_index, order))
 
     # ---- snapshot-wise parameter derivatives (include/nif_hip_snapparam.h; Model.predict_snapshot_parameter_derivatives plans the chunks) ----
     def _snapshot_param_derivs(self, rows, drows, d_x, x_off, offsets, m, n, y_index, p_index):
         self._not_capturing("nif_snapshot_param_derivatives")
         s = self.spec
         is_latent = drows is not None
-        rows = self._rows(rows, s.pi_hidden if is_latent else s.pi_dim, "latent" if is_latent else "parameter inputs")
+        rows = self._snapshot_rows(rows, is_latent)
         yi = np.ascontiguousarray(list(y_index), dtype=np.int32)
         if is_latent:
             drows = np.ascontiguousarray(drows, dtype=np.float32)
@@ -392,55 +395,29 @@ class Engine(object):
         else:
             pi_ = np.ascontiguousarray(list(p_index), dtype=np.int32)
             nd = pi_.size
-        ny = yi.size
-        u = np.empty((n, s.so_dim), dtype=np.float32)
-        d = np.empty((n, ny, nd), dtype=np.float32)
-        if not n:
-            return u, d
         off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        d_r, d_o = DeviceArray(self, rows.size + (drows.size if is_latent else 0)), DeviceArray(self, u.size + d.size)
-        try:
-            d_r.upload(np.concatenate([rows.ravel(), drows.ravel()]) if is_latent else rows)
+
+        def call(d_r, o):
             a = _lib.nif_snapparam_args()
             a.abi_version, a.ctx = _lib.NIF_SNAPPARAM_ABI_VERSION, self.ctx
-            a.rows, a.rows_are_latent, a.T = d_r.at(0), 1 if is_latent else 0, rows.shape[0]
+            self._snapshot_geometry(a, d_r, rows, is_latent, d_x, x_off, off, m, yi)
             if is_latent:
                 a.drows, a.nd = d_r.at(rows.size), nd
             else:
                 a.p_idx, a.np = pi_.ctypes.data_as(C.POINTER(C.c_int32)), nd
-            a.x, a.M = d_x.at(x_off), int(m)
-            a.offsets_host = None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64))
-            a.y_idx, a.ny = yi.ctypes.data_as(C.POINTER(C.c_int32)), ny
-            a.u, a.dudp = d_o.at(0), d_o.at(u.size)
-            check(self.lib.nif_snapshot_param_derivatives_dev(C.byref(a)))
-            check(self.lib.nif_d2h(self.ctx, ptr(u), d_o.at(0), u.size * 4))
-            check(self.lib.nif_d2h(self.ctx, ptr(d), d_o.at(u.size), d.size * 4))
-        finally:
-            d_r.free(); d_o.free()
-        return u, d
+            a.u, a.dudp = o
+            return self.lib.nif_snapshot_param_derivatives_dev(C.byref(a))
+        return tuple(self._snapshot_call([rows, drows] if is_latent else [rows], [(n, s.so_dim), (n, yi.size, nd)], call))
 
     def snapshot_param_derivatives(self, rows, drows, mesh, lo, hi, y_index, p_index):
         """rows [T, pi] with p_index (drows None), or latents [T, r] with directions drows [T, nd, r], on the points lo .. hi of a
         snapshot_mesh handle -> (u [T, hi - lo, so], dudp [T, hi - lo, ny, nd])"""
-        t, m = int(np.shape(rows)[0]), int(hi) - int(lo)
-        outs = self._snapshot_param_derivs(rows, drows, mesh, int(lo) * self.spec.si_dim, None, m, t * m, y_index, p_index)
-        return tuple(o.reshape((t, m) + o.shape[1:]) for o in outs)
+        return self._shared(rows, mesh, lo, hi, lambda *g: self._snapshot_param_derivs(rows, drows, *g, y_index, p_index))
 
     def snapshot_param_derivatives_ragged(self, rows, drows, xs, y_index, p_index):
         """rows [T, .] (and drows) and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> the same outputs [sum M_t, ...], snapshot after snapshot"""
-        self._not_capturing("nif_snapshot_param_derivatives")
-        xs = [self._rows(a, self.spec.si_dim, "coordinates") for a in xs]
-        if len(xs) != int(np.shape(rows)[0]):
-            raise ValueError("snapshot_param_derivatives_ragged: %d rows for %d meshes" % (int(np.shape(rows)[0]), len(xs)))
-        offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in xs])]).astype(np.int64)
-        n = int(offsets[-1])
-        d_x = DeviceArray(self, max(n, 1) * self.spec.si_dim)
-        try:
-            if n:
-                d_x.upload(np.concatenate(xs, axis=0))
-            return self._snapshot_param_derivs(rows, drows, d_x, 0, offsets, 0, n, y_index, p_index)
-        finally:
-            d_x.free()
+        return self._ragged("nif_snapshot_param_derivatives", "snapshot_param_derivatives_ragged", rows, xs,
+                            lambda *g: self._snapshot_param_derivs(rows, drows, *g, y_index, p_index))
 
     # ---- encoding (include/nif_hip_encode.h; nif_amd/encode.py runs the Levenberg-Marquardt loop around these two) ----------
     def snapshot_samples(self, x, y, w=None, counts=None):
@@ -476,18 +453,11 @@ class Engine(object):
         lat = self._rows(latents, r, "latent")
         if lat.shape[0] != samples.t:
             raise ValueError("snapshot_normal_eq: %d latents for %d snapshots" % (lat.shape[0], samples.t))
-        out = np.zeros((samples.t, r + 1, r + 1), dtype=np.float64)
-        if not samples.t:
-            return out
-        d_l, d_s = DeviceArray(self, lat.size), DeviceArray64(self, out.size)
-        try:
-            d_l.upload(lat)
-            a = samples.args(d_l, d_s)
-            check(self.lib.nif_snapshot_normal_eq_dev(C.byref(a)))
-            out[...] = d_s.download().reshape(out.shape)
-        finally:
-            d_l.free(); d_s.free()
-        return out
+        def call(d_l, o):
+            a = samples.args(d_l, d_l)
+            a.S_out = o[0]      # (args() reads arrays; the output is an address here)
+            return self.lib.nif_snapshot_normal_eq_dev(C.byref(a))
+        return self._snapshot_call([lat], [(samples.t, r + 1, r + 1)], call, dtype=np.float64)[0]
 
     def p_to_lr(self, p):
         p = self._rows(p, self.spec.pi_dim, "parameter inputs")

@@ -193,6 +193,70 @@ def test_call_inside_a_graph_capture_is_refused():
     assert _rel(model.predict_snapshots(d["xsh"], p=d["p"][:1])[0], d["ref_shared"][0]) < BAR
 
 
+FRONT_T, FRONT_M = 2, 3
+# the geometry faults every snapshot entry refuses in its shared front end: (rows, T, x, offsets) as the entry sees them -> the return
+# code and the message, {who} the entry's name
+FRONT_FAULTS = {
+    "no_snapshots": (dict(T=0), -1, "bad argument"),
+    "offsets_start_at_one": (dict(offsets=[1, 3, 6]), -1, "bad argument"),
+    "offsets_decrease": (dict(offsets=[0, 2, 1]), -1, "offsets must not decrease"),
+    "null_rows": (dict(rows=None), -1, "bad argument"),
+    "points_without_coordinates": (dict(x=None), -1, "bad argument"),
+    "inside_a_capture": (dict(capture=True), -4, "{who}: not capturable (inside nif_graph_begin / nif_graph_end)"),
+}
+
+
+@pytest.mark.parametrize("entry", ["nif_forward_snapshots", "nif_snapshot_normal_eq", "nif_snapshot_derivatives",
+                                   "nif_snapshot_param_derivatives"])
+def test_every_device_entry_refuses_the_same_geometry_faults_alike(entry):
+    """host-side refusals of the four *_dev entries: nothing is launched between the valid call in front and the one behind"""
+    import ctypes as C
+    from nif_amd import _lib
+    m, model, spec, ws, _, _, _ = _make("ms_32x2_r7_si3")
+    e, n = m._engine, FRONT_T * FRONT_M
+    rng = np.random.default_rng(11)
+    latent = entry == "nif_snapshot_normal_eq"               # (its rows are latents; the others are given p)
+    d_rows, d_x, d_y = e.alloc(FRONT_T * max(spec.pi, spec.r)), e.alloc(6 * spec.si), e.alloc(6 * spec.so)
+    d_out, d_s = e.alloc(6 * spec.so * 4), e.alloc(2 * FRONT_T * (spec.r + 1) ** 2)        # (d_s: float64 [T, r + 1, r + 1])
+    d_rows.upload(rng.uniform(-1, 1, size=FRONT_T * (spec.r if latent else spec.pi)))
+    d_x.upload(rng.uniform(-1, 1, size=6 * spec.si)); d_y.upload(rng.uniform(-1, 1, size=6 * spec.so))
+    idx = (C.c_int32 * 1)(0)
+
+    def call(rows=d_rows.at(0), T=FRONT_T, x=d_x.at(0), offsets=None, capture=False):
+        off = None if offsets is None else np.array(offsets, dtype=np.int64)
+        off_p = None if off is None else off.ctypes.data_as(C.POINTER(C.c_int64))
+        M = 0 if offsets is not None else FRONT_M
+        if entry == "nif_forward_snapshots":
+            return e.lib.nif_forward_snapshots_dev(e.ctx, rows, 0, T, x, off_p, M, d_out.at(0))
+        if entry == "nif_snapshot_normal_eq":
+            a = _lib.nif_encode_args()
+            a.abi_version, a.latents, a.y, a.S_out = _lib.NIF_ENCODE_ABI_VERSION, rows, d_y.at(0), d_s.at(0)
+        elif entry == "nif_snapshot_derivatives":
+            a = _lib.nif_snapderiv_args()
+            a.abi_version, a.order, a.rows = _lib.NIF_SNAPDERIV_ABI_VERSION, 1, rows
+            a.y_idx, a.ny, a.x_idx, a.nx, a.u, a.dudx = idx, 1, idx, 1, d_out.at(0), d_out.at(6 * spec.so)
+        else:
+            a = _lib.nif_snapparam_args()
+            a.abi_version, a.rows = _lib.NIF_SNAPPARAM_ABI_VERSION, rows
+            a.y_idx, a.ny, a.p_idx, a.np, a.u, a.dudp = idx, 1, idx, 1, d_out.at(0), d_out.at(6 * spec.so)
+        a.ctx, a.T, a.x, a.offsets_host, a.M = e.ctx, T, x, off_p, M
+        return getattr(e.lib, entry + "_dev")(C.byref(a))
+
+    assert call() == 0 and call(offsets=[0, 2, 6]) == 0     # (planes packed, workspaces sized: a capture has nothing else to refuse)
+    for name, (fault, code, message) in FRONT_FAULTS.items():
+        if fault.get("capture"):
+            e.graph_begin()
+        try:
+            rc = call(**{k: v for k, v in fault.items() if k != "capture"})
+            said = e.lib.nif_last_error().decode()
+        finally:
+            if fault.get("capture"):
+                e.graph_end()
+        assert (rc, said) == (code, message.format(who=entry)), (entry, name)
+    assert call() == 0 and call(offsets=[0, 2, 6]) == 0
+    e.sync()
+
+
 def test_host_pointer_entry_equals_the_device_pointer_entry():
     import ctypes as C
     from nif_amd._lib import check, ptr
