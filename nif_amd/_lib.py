@@ -255,6 +255,27 @@ SNAPPARAM_SIGNATURES = {
 }
 
 
+NIF_SNAPPARAM2_ABI_VERSION = 1
+
+
+class nif_snapparam2_args(C.Structure):
+    """include/nif_hip_snapparam2.h, field for field"""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("rows_are_latent", C.c_int32), ("ctx", _CTX), ("rows", _VP), ("drows", _VP), ("ddrows", _VP),
+        ("nd", C.c_int32), ("np", C.c_int32), ("p_idx", C.POINTER(C.c_int32)), ("T", C.c_int64), ("x", _VP),
+        ("offsets_host", C.POINTER(C.c_int64)), ("M", C.c_int64), ("y_idx", C.POINTER(C.c_int32)), ("ny", C.c_int32), ("nxc", C.c_int32),
+        ("x_idx", C.POINTER(C.c_int32)), ("u", _VP), ("dudp", _VP), ("d2udp2", _VP), ("dudx", _VP), ("d2udpdx", _VP),
+        ("reserved", C.c_int64 * 4),
+    ]
+
+
+# include/nif_hip_snapparam2.h, one to one (bound by load() with the tables above)
+SNAPPARAM2_SIGNATURES = {
+    "nif_snapshot_param_second_derivatives": (C.c_int, [C.POINTER(nif_snapparam2_args)]),
+    "nif_snapshot_param_second_derivatives_dev": (C.c_int, [C.POINTER(nif_snapparam2_args)]),
+}
+
+
 def load():
     """dlopen libnif_hip.so and bind every symbol of include/nif_hip.h.  Raises if it is absent."""
     global _lib
@@ -265,7 +286,8 @@ def load():
             "libnif_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-    for table in (SIGNATURES, SNAPSHOT_SIGNATURES, ENCODE_SIGNATURES, SNAPDERIV_SIGNATURES, SNAPPARAM_SIGNATURES):
+    for table in (SIGNATURES, SNAPSHOT_SIGNATURES, ENCODE_SIGNATURES, SNAPDERIV_SIGNATURES, SNAPPARAM_SIGNATURES,
+                  SNAPPARAM2_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the library does not export it
             fn.restype = res

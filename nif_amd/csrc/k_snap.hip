@@ -229,3 +229,39 @@ int launch_snet4_snap(const SNetArgs& a, long T, long Mmax, hipStream_t st) {
 #undef S4L
   return (int)per;
 }
+
+// second order (include/nif_hip_snapparam2.h), the table route: the parameter rows of HessianLayer's result over the
+// columns [np parameters | nxc coordinates], H [rows][nx][nx] -> d2pp [rows][np][np] and d2px [rows][np][nxc]
+__global__ __launch_bounds__(256) void k_snapparam2_blocks(const float* __restrict__ H, long rows, int np, int nxc, float* __restrict__ d2pp,
+                                                           float* __restrict__ d2px) {
+  const int nx = np + nxc;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * np * nx) return;
+  const long row = idx / (np * nx);
+  const int e = (int)(idx - row * (np * nx)), a = e / nx, col = e - a * nx;
+  const float v = H[(row * nx + a) * nx + col];
+  if (col < np) d2pp[(row * np + a) * np + col] = v;
+  else d2px[(row * np + a) * nxc + (col - np)] = v;
+}
+void launch_snapparam2_blocks(const float* H, long rows, int np, int nxc, float* d2pp, float* d2px, hipStream_t st) {
+  hipLaunchKernelGGL(k_snapparam2_blocks, dim3((unsigned)((rows * np * (np + nxc) + 255) / 256)), dim3(256), 0, st, H, rows, np, nxc, d2pp, d2px);
+}
+__global__ __launch_bounds__(256) void k_snapparam2_gather(const float* __restrict__ f, long n, long s_r, long s_n, long s_y, HessIdx I, Sp2Map map,
+                                                           float* __restrict__ out) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;      // (point, i)
+  if (e >= n * I.ny) return;
+  const long a = e / I.ny; const int i = (int)(e - a * I.ny);
+  const float* src = f + a * s_n + I.y_idx[i] * s_y;
+  for (int col = 0; col < map.n; ++col) out[e * map.n + col] = src[map.src[col] * s_r];
+}
+void launch_snapparam2_gather(const float* f, long n, long s_r, long s_n, long s_y, const HessIdx& I, const Sp2Map& map, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_snapparam2_gather, dim3((unsigned)((n * I.ny + 255) / 256)), dim3(256), 0, st, f, n, s_r, s_n, s_y, I, map, out);
+}
+// the source offsets k_through_lw takes, for a contiguous stack of n vectors of `stride` floats
+__global__ void k_stride_offsets(long* __restrict__ off, int n, long stride) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < n) off[q] = (long)q * stride;
+}
+void launch_stride_offsets(long* off, int n, long stride, hipStream_t st) {
+  hipLaunchKernelGGL(k_stride_offsets, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, off, n, stride);
+}

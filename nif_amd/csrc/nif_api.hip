@@ -16,6 +16,7 @@
 #include "../../include/nif_hip_snapshots.h"
 #include "../../include/nif_hip_snapderiv.h"
 #include "../../include/nif_hip_snapparam.h"
+#include "../../include/nif_hip_snapparam2.h"
 #include "../../include/nif_hip_encode.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
@@ -805,6 +806,7 @@ static int snap_not_capturing(const nif_ctx* c, const char* who) {
 static bool snap_reserved(const nif_encode_args& a) { return a.reserved0 != 0; }
 static bool snap_reserved(const nif_snapderiv_args& a) { return a.reserved0 || a.reserved1 || a.reserved2; }
 static bool snap_reserved(const nif_snapparam_args& a) { return a.reserved0 != 0; }
+static bool snap_reserved(const nif_snapparam2_args&) { return false; }
 template <class A>
 static int snap_args_check(const A* a, int version, const char* name) {
   if (!a) return fail(NIF_ERR_INVALID, "null");
@@ -1323,7 +1325,7 @@ static int hessian_core(nif_ctx* c, const float* xin_dev, int64_t B, const int32
     const int nvec = np_ + np_ * np_;
     float* ap = nullptr;
     if (nvec > 0) {
-      const long need = (long)nvec * blk + 64;        // + the source offsets (as raw bytes behind the vectors)
+      const long need = (long)nvec * blk + 2L * nvec + 2;      // + the nvec source offsets (longs, as raw bytes behind the vectors)
       rc = c->jac_mu.reserve(c, need); if (rc) return rc;
       ap = c->jac_mu;
       for (int j = 0; j < np_; ++j)
@@ -1736,6 +1738,310 @@ extern "C" int nif_snapshot_param_derivatives(const nif_snapparam_args* a) {
   d.rows = s[0].dev; d.drows = lat_in ? s[1].dev : nullptr; d.x = s[2].dev; d.u = s[3].dev; d.dudp = s[4].dev;
   rc = nif_snapshot_param_derivatives_dev(&d); if (rc) return rc;
   return snap_stage_out(c, s, 5);
+}
+
+// ---- second order of the snapshot-wise parameter derivatives (include/nif_hip_snapparam2.h) ----------------------------
+static int sp2_check(const nif_snapparam2_args* a, SnapGeom* g, HessIdx* I) {
+  const char* who = "nif_snapshot_param_second_derivatives";
+  int rc = snap_args_check(a, NIF_SNAPPARAM2_ABI_VERSION, "nif_snapparam2_args"); if (rc) return rc;
+  const nif_ctx* c = a->ctx;
+  if (a->nxc < 0) return fail(NIF_ERR_INVALID, std::string(who) + ": nxc < 0");
+  const bool xc = a->nxc > 0;
+  rc = snap_geom_check(c, a->rows, a->T, a->x, a->offsets_host, a->M, a->u && a->dudp && a->d2udp2 && (!xc || (a->dudx && a->d2udpdx)), g);
+  if (rc) return rc;
+  if (a->rows_are_latent) {
+    if (!a->drows) return fail(NIF_ERR_INVALID, std::string(who) + ": latent rows need drows [T, nd, r]");
+    if (a->p_idx || a->np) return fail(NIF_ERR_INVALID, std::string(who) + ": p_idx / np go with rows [T, pi], not with latents");
+    if (a->nd < 1 || a->nd > 8) return fail(NIF_ERR_INVALID, std::string(who) + ": 1 to 8 directions (nd)");
+  } else {
+    if (a->drows || a->ddrows || a->nd) return fail(NIF_ERR_INVALID, std::string(who) + ": drows / ddrows / nd go with latent rows (rows_are_latent = 1)");
+    if (!a->p_idx || a->np < 1 || a->np > 8) return fail(NIF_ERR_INVALID, std::string(who) + ": 1 to 8 parameter columns (p_idx, np)");
+    for (int j = 0; j < a->np; ++j) {
+      if (a->p_idx[j] < 0 || a->p_idx[j] >= c->pi) return fail(NIF_ERR_INVALID, "p_index out of range (0 <= c < pi_dim)");
+      for (int k = 0; k < j; ++k) if (a->p_idx[k] == a->p_idx[j]) return fail(NIF_ERR_INVALID, "p_index: an index is repeated");
+    }
+  }
+  if (xc != (a->x_idx != nullptr)) return fail(NIF_ERR_INVALID, std::string(who) + ": x_idx and nxc go together");
+  if (!xc && (a->dudx || a->d2udpdx)) return fail(NIF_ERR_INVALID, std::string(who) + ": dudx / d2udpdx are null exactly when nxc is 0");
+  if (a->nxc > c->si) return fail(NIF_ERR_INVALID, std::string(who) + ": more coordinate columns than coordinates (nxc <= si_dim)");
+  if (a->nxc > 16) return fail(NIF_ERR_INVALID, "HessianLayer: at most 16 coordinate and 16 parameter columns in x_index");
+  for (int j = 0; j < a->nxc; ++j) {
+    if (a->x_idx[j] < 0 || a->x_idx[j] >= c->si) return fail(NIF_ERR_INVALID, "x_index out of range (0 <= j < si_dim: coordinates only)");
+    for (int k = 0; k < j; ++k) if (a->x_idx[k] == a->x_idx[j]) return fail(NIF_ERR_INVALID, "x_index: an index is repeated");
+  }
+  rc = snap_y_index(c, a->y_idx, a->ny, I); if (rc) return rc;
+  if (xc) { const int rcw = wide_refused(c, "nif_snapshot_derivatives"); if (rcw) return rcw; }      // (phi' of a wide ShapeNet is not built)
+  return snap_not_capturing(c, who);
+}
+// Hypernetwork classes on k_jac_wt2.  lat [T][r], D [nd][T][r], DD [nd nd][T][r] (pair (a, b), a <= b, at a nd + b; null: no second
+// directions).  Per chunk of snapshots: w_t, every direction's tangent slot vector and their planes ONCE ([W_j | W'_0,j .. W'_nd-1,j |
+// W''_j] per hidden layer); per pair a <= b its second slot vector wdd = DD_ab . Wh (k_dlatent_to_w: never a difference of combined
+// vectors) into the one W'' slot, then one launch that is told its planes' places; per (direction, coordinate) one launch of the mixed
+// form.  The kernel leaves every output row [n][so][nd nd] in c->d_c and [n][so][nd nxc] in c->d_b; the rows y_idx are gathered behind
+// the last chunk.
+static int sp2_combined(nif_ctx* c, const nif_snapparam2_args* a, const SnapPlan& P, const SnapGeom& g_, long tc_max, const float* lat,
+                        const float* D, const float* DD, int nd, const HessIdx& I) {
+  const long T = g_.T, n = g_.n;
+  const int so = c->so, NBL = snet3_nbl(c->n), ps = 2 + nd, nxc = a->nxc;
+  int rc = stage(c, c->d_c, nullptr, n * so * nd * nd); if (rc) return rc;
+  if (nxc) { rc = stage(c, c->d_b, nullptr, n * so * nd * nxc); if (rc) return rc; }
+  float* w = P.body;                                // [2 + nd][tc_max][po]: w_t, each direction's wd_t, the pair's wdd_t
+  f32x4* WF = reinterpret_cast<f32x4*>(w + snap_r4((long)ps * tc_max * c->po));
+  const long plane_s = sd_plane_f32x4(c);
+  auto slot = [&](int i) { return w + (long)i * tc_max * c->po; };
+  auto pack = [&](const float* dir, long tc, int i) {      // slot vector i of the chunk from its direction rows, and its planes
+    launch_dlatent_to_w(c->theta, c->last_w, c->r, c->po, dir, tc, slot(i), c->st);
+    for (int j = 0; j < c->nh; ++j)
+      launch_pack16_fwd_batch(slot(i), dense_ref(hyper_wslot(c, 1 + j), c->n, c->n), c->po, (int)tc, NBL, WF + ((long)j * ps + i) * plane_s,
+                              c->nh * ps * plane_s, c->st);
+  };
+  for (SnapWalk k{g_, tc_max}; k.next();) {
+    const long t0 = k.t0, tc = k.tc;
+    snap_pack_f32(c, lat + t0 * c->r, tc, w, WF, ps);
+    {
+      ProfScope p_(c, NIF_PROF_PACK);
+      for (int d = 0; d < nd; ++d) pack(D + ((long)d * T + t0) * c->r, tc, 1 + d);
+    }
+    SNetArgs sa; fill_snet(c, sa, a->x, c->si, 0, k.mmax);
+    snap_r0_net(sa, w, P, k, c->nh * ps * plane_s);
+    sa.WF = WF; sa.WB = nullptr; sa.u_out = nullptr;
+    const long pb = g_.off ? 0 : t0 * g_.M;      // (ragged: the kernel rebases by the call's own offsets; shared mesh: by t M inside the chunk)
+    for (int i = 0; i < nd; ++i)
+      for (int j = i; j < nd; ++j) {
+        if (DD) { ProfScope p_(c, NIF_PROF_PACK); pack(DD + ((long)(i * nd + j) * T + t0) * c->r, tc, 1 + nd); }
+        ProfScope p_(c, NIF_PROF_SNET_FWD);
+        launch_jac_wt2(sa, tc, i == j ? 1 : 0, slot(1 + i), slot(1 + j), DD ? slot(1 + nd) : nullptr, 1 + i, 1 + j, 1 + nd, ps, 0, nd * nd,
+                       i * nd + j, j * nd + i, c->d_c + pb * so * nd * nd, c->st);
+      }
+    for (int i = 0; i < nd; ++i)
+      for (int j = 0; j < nxc; ++j) {
+        ProfScope p_(c, NIF_PROF_SNET_FWD);
+        launch_jac_wt2(sa, tc, 2, slot(1 + i), nullptr, nullptr, 1 + i, 0, 0, ps, a->x_idx[j], nd * nxc, i * nxc + j, i * nxc + j,
+                       c->d_b + pb * so * nd * nxc, c->st);
+      }
+  }
+  launch_jac_gather(c->d_c, n, so, nd * nd, I, a->d2udp2, c->st);
+  if (nxc) launch_jac_gather(c->d_b, n, so, nd * nxc, I, a->d2udpdx, c->st);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+// Last-layer class, u = phi(x) . a + bias with the latent a: d2u/dp_a dp_b = phi . a''_ab and d2u/dp_a dx_j = phi'_j . a'_a.  lat [T][r],
+// D [nd][T][r] the tangent coefficient rows, DDc [pairs][T][r] the second ones (pair (a, b), a <= b, in that order; null: none), zero:
+// so zeros.  Shared mesh (P.phi_dot): phi once per call and phi'_j once per coordinate (k_mlp_jac over the mesh), each contracted with
+// every row by k_phi_dot.  Else: the point-wise epilogue behind coefficient tiles (k_snap_expand), as the first order runs it.
+static int sp2_lastlayer(nif_ctx* c, const nif_snapparam2_args* a, SnapPlan& P, const SnapGeom& g, const float* lat, const float* D,
+                         const float* DDc, const float* zero, int nd, const HessIdx& I) {
+  const long n = g.n, T = g.T, M = g.M;
+  const int r = c->r, so = c->so, si = c->si, nxc = a->nxc, npair = nd * (nd + 1) / 2;
+  Sp2Map mp, mx;
+  memset(&mp, 0, sizeof(mp)); memset(&mx, 0, sizeof(mx));
+  mp.n = nd * nd; mx.n = nd * nxc;
+  for (int i = 0, q = 0; i < nd; ++i)
+    for (int j = i; j < nd; ++j, ++q) { mp.src[i * nd + j] = q; mp.src[j * nd + i] = q; }
+  int rc = c->sd_tmp.reserve(c, n * so * (npair + (long)nd * nxc) + 1); if (rc) return rc;
+  float* fa = c->sd_tmp.p;                 // the pairs' rows over every output
+  float* fx = fa + n * so * npair;         // the mixed rows
+  if (!DDc) HIPCHK(hipMemsetAsync(a->d2udp2, 0, sizeof(float) * (size_t)(n * a->ny * nd * nd), c->st));
+  if (nxc) ensure_ll_mlp_planes(c);
+  ProfScope p_(c, NIF_PROF_SNET_FWD);
+  if (P.phi_dot) {
+    rc = c->d_c.reserve(c, ((M + 31) / 32) * 32 * (long)r * so); if (rc) return rc;
+    ll_phi_pass(c, a->x, si, 0, M);
+    if (DDc) {
+      launch_phi_dot(c->PHI, DDc, zero, (long)npair * T, M, r, so, fa, c->st);
+      launch_snapparam2_gather(fa, n, n * so, so, 1, I, mp, a->d2udp2, c->st);
+    }
+    for (int j = 0; j < nxc; ++j) {      // phi'_j of the mesh in phi's tile layout, contracted with every tangent row
+      PNetArgs mj; fill_snet_mlp(c, mj, a->x, si, 0, M); mj.Z = c->DPHI;
+      launch_mlp_jac(mj, c->NB, a->x_idx[j], c->d_c, c->st);
+      launch_phi_dot(c->d_c, D, zero, (long)nd * T, M, r, so, fx + (long)j * nd * n * so, c->st);
+      for (int i = 0; i < nd; ++i) mx.src[i * nxc + j] = j * nd + i;
+    }
+    if (nxc) launch_snapparam2_gather(fx, n, n * so, so, 1, I, mx, a->d2udpdx, c->st);
+    HIPCHK(hipGetLastError());
+    return NIF_OK;
+  }
+  const long zd_sz = ((n + 31) / 32) * 32 * r;
+  rc = c->d_c.reserve(c, zd_sz * (1 + (nxc ? so : 0))); if (rc) return rc;
+  float* zt = c->d_c;                      // one coefficient row of every snapshot as tiles
+  float* dphi = c->d_c + zd_sz;            // phi'_j of every point
+  SnapArgs& sn = P.sn;
+  sn.lat = lat; sn.Z = c->Z;
+  launch_snap_expand(sn, c->st);
+  const float* xg = P.table ? sn.table : a->x;
+  sn.table = nullptr;
+  ll_phi_pass(c, xg, si, 0, n);
+  if (DDc) {
+    for (int q = 0; q < npair; ++q) {
+      sn.lat = DDc + (long)q * T * r; sn.Z = zt;
+      launch_snap_expand(sn, c->st);
+      launch_ll_jac_out(c->PHI, c->Z, nullptr, zt, n, r, so, npair, q, fa, c->st);
+    }
+    launch_snapparam2_gather(fa, n, 1, (long)so * npair, npair, I, mp, a->d2udp2, c->st);
+  }
+  for (int j = 0; j < nxc; ++j) {
+    PNetArgs mj; fill_snet_mlp(c, mj, xg, si, 0, n); mj.Z = c->DPHI;
+    launch_mlp_jac(mj, c->NB, a->x_idx[j], dphi, c->st);
+    for (int i = 0; i < nd; ++i) {
+      sn.lat = D + (long)i * T * r; sn.Z = zt;
+      launch_snap_expand(sn, c->st);
+      launch_ll_jac_out(c->PHI, zt, dphi, nullptr, n, r, so, nd * nxc, i * nxc + j, fx, c->st);
+    }
+  }
+  if (nxc) launch_jac_gather(fx, n, so, nd * nxc, I, a->d2udpdx, c->st);
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_snapshot_param_second_derivatives_dev(const nif_snapparam2_args* a) {
+  SnapGeom g; HessIdx I;
+  int rc = sp2_check(a, &g, &I); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  const char* who = "nif_snapshot_param_second_derivatives";
+  rc = ensure_packed(c); if (rc) return rc;
+  const bool lat_in = a->rows_are_latent != 0, ll = c->kind == NIF_KIND_LASTLAYER;
+  if (lat_in) { rc = snap_policy_refusal(c, who, true); if (rc) return rc; }
+  const int nd = lat_in ? a->nd : a->np, r = c->r, so = c->so, ny = a->ny, nxc = a->nxc;
+  // the routes: k_jac_wt2 on combined nets; the last-layer class' phi and phi' against the coefficient rows; else, from
+  // p, HessianLayer's kernels on the device-built table
+  SnapPlan P;
+  snap_routes(c, g, lat_in, phi_dot_supported(r, so), true, &P);
+  bool combined = P.combined && c->jac_ok;
+  if (combined) { SNetArgs probe; fill_snet(c, probe, nullptr, 0, 0, 32); combined = jac_wt_supported(probe); }
+  const bool lastlayer = ll && !snap_pointwise(c);
+  if (!combined && !lastlayer && lat_in)
+    return fail(NIF_ERR_INVALID, std::string(who) + (P.combined
+        ? ": one weight plane and four images of the small hyper-vectors of this shape exceed the 160 KB LDS of a CU"
+        : ": latents are not built for this shape (its nets run the legacy kernels; pass p)"));
+  if (!combined && !lastlayer) { const int rcw = wide_refused(c, "HessianLayer"); if (rcw) return rcw; }
+  PNetArgs pa; fill_pnet(c, pa, a->rows, g.T); pa.ncol = c->pi;
+  if (!lat_in && !pjac_supported(pa)) return fail(NIF_ERR_INVALID, "HessianLayer on parameter columns: ParameterNets of up to 128 units");
+  const long n = g.n, T = g.T;
+  if (n == 0) return NIF_OK;
+  // u, dudx and dudp as the first-order calls give them, bit for bit: their own routes, ahead of the second order on the stream
+  if (nxc) {
+    nif_snapderiv_args d; memset(&d, 0, sizeof(d));
+    d.abi_version = NIF_SNAPDERIV_ABI_VERSION; d.order = 1; d.ctx = c; d.rows = a->rows; d.rows_are_latent = a->rows_are_latent; d.T = a->T;
+    d.x = a->x; d.offsets_host = a->offsets_host; d.M = a->M; d.y_idx = a->y_idx; d.ny = ny; d.x_idx = a->x_idx; d.nx = nxc;
+    d.u = a->u; d.dudx = a->dudx;
+    rc = nif_snapshot_derivatives_dev(&d); if (rc) return rc;
+  }
+  {
+    nif_snapparam_args d; memset(&d, 0, sizeof(d));
+    d.abi_version = NIF_SNAPPARAM_ABI_VERSION; d.rows_are_latent = a->rows_are_latent; d.ctx = c; d.rows = a->rows; d.drows = a->drows;
+    d.nd = a->nd; d.np = a->np; d.p_idx = a->p_idx; d.T = a->T; d.x = a->x; d.offsets_host = a->offsets_host; d.M = a->M;
+    d.y_idx = a->y_idx; d.ny = ny; d.u = a->u; d.dudp = a->dudp;
+    rc = nif_snapshot_param_derivatives_dev(&d); if (rc) return rc;
+  }
+  if (lastlayer) {
+    // ---- the coefficient rows of every snapshot: lat [T][r], a' = D [nd][T][r], a'' = DDc [pairs][T][r] ------------------------------
+    const int npair = nd * (nd + 1) / 2;
+    const long ttiles = (T + 31) / 32, blk = ttiles * 32 * r;
+    const long dir_f = (long)nd * T * r, ddc_f = (long)npair * T * r, ddf_f = (lat_in && a->ddrows) ? (long)nd * nd * T * r : 0;
+    rc = snap_plan_reserve(c, g, a->x, lat_in, 0, dir_f + ddc_f + ddf_f + so, 0, false, &P); if (rc) return rc;
+    rc = snap_point_capacity(c, g, P); if (rc) return rc;
+    const float* lat = a->rows;
+    float* D = P.extra;
+    float* DDc = D + dir_f;
+    float* DDf = DDc + ddc_f;
+    float* zero = DDf + ddf_f;
+    HIPCHK(hipMemsetAsync(zero, 0, sizeof(float) * (size_t)so, c->st));
+    if (lat_in) {
+      launch_dir_rows(a->drows, T, nd, r, D, c->st);
+      if (a->ddrows) {
+        launch_dir_rows(a->ddrows, T, nd * nd, r, DDf, c->st);
+        for (int i = 0, q = 0; i < nd; ++i)
+          for (int j = i; j < nd; ++j, ++q)
+            HIPCHK(hipMemcpyAsync(DDc + (long)q * T * r, DDf + (long)(i * nd + j) * T * r, sizeof(float) * (size_t)(T * r), hipMemcpyDeviceToDevice, c->st));
+      } else DDc = nullptr;
+    } else {      // a' per column as the first-order call forms it (k_mlp_jac); a'' = z'' last_w per pair (k_pjac2, ONE k_through_lw)
+      rc = ensure_packed_p32(c); if (rc) return rc;
+      rc = c->d_c.reserve(c, blk); if (rc) return rc;
+      rc = c->jac_mu.reserve(c, 2 * npair * blk + 2L * npair + 2); if (rc) return rc;      // [z'' | a'' | npair source offsets (longs)]
+      for (int j = 0; j < nd; ++j) {
+        PNetArgs pj = pa; pj.Z = c->DA;      // (primal again into a scratch)
+        launch_mlp_jac(pj, c->NSTB, a->p_idx[j], c->d_c, c->st);
+        launch_tiles_to_rows(c->d_c, T, r, D + (long)j * T * r, c->st);
+      }
+      float* zs = c->jac_mu;
+      float* ap = zs + (long)npair * blk;
+      for (int i = 0, q = 0; i < nd; ++i)
+        for (int j = i; j < nd; ++j, ++q) launch_pjac2(pa, a->p_idx[i], a->p_idx[j], zs + (long)q * blk, c->st);
+      long* off_dev = reinterpret_cast<long*>(ap + (long)npair * blk);
+      launch_stride_offsets(off_dev, npair, blk, c->st);      // vector q sits q blk floats behind zs (on the device: the entry stays asynchronous)
+      launch_through_lw(zs, off_dev, npair, c->theta + c->last_w, r, ttiles * 32, ap, c->st);
+      for (int q = 0; q < npair; ++q) launch_tiles_to_rows(ap + (long)q * blk, T, r, DDc + (long)q * T * r, c->st);
+      snap_latents_from_p(c, a->rows, T, P.lat);
+      lat = P.lat;
+    }
+    return sp2_lastlayer(c, a, P, g, lat, D, DDc, zero, nd, I);
+  }
+  if (!combined) {      // HessianLayer on the table over [p_idx | pi + x_idx]; its parameter rows of the Hessian are the two blocks
+    P.pointwise = true; P.combined = false; P.phi_dot = false; P.table = true;
+    const int nx = nd + nxc;
+    const long n_j = n * ny * nx;
+    rc = snap_plan_reserve(c, g, a->x, false, c->pi, 0, 0, true, &P); if (rc) return rc;
+    rc = c->sd_tmp.reserve(c, n * so + n_j + n_j * nx + 1); if (rc) return rc;
+    int32_t cols[24];
+    for (int j = 0; j < nd; ++j) cols[j] = a->p_idx[j];
+    for (int j = 0; j < nxc; ++j) cols[nd + j] = c->pi + a->x_idx[j];
+    P.sn.p = a->rows;
+    launch_snap_expand(P.sn, c->st);
+    float* H = c->sd_tmp.p + n * so + n_j;
+    rc = hessian_core(c, P.sn.table, n, a->y_idx, ny, cols, nx, c->sd_tmp.p, c->sd_tmp.p + n * so, H); if (rc) return rc;
+    launch_snapparam2_blocks(H, n * ny, nd, nxc, a->d2udp2, a->d2udpdx, c->st);
+    HIPCHK(hipGetLastError());
+    return NIF_OK;
+  }
+  // ---- the latent, the directions and the second directions of every snapshot: lat [T][r], D [nd][T][r], DD [nd nd][T][r] -------------
+  const long tc_max = snap_chunk(c, T, sp_snapshot_bytes(c, 1 + nd));
+  const long dir_f = (long)nd * T * r, dd_f = (long)nd * nd * T * r;
+  rc = snap_plan_reserve(c, g, a->x, lat_in, 0, dir_f + dd_f, sp_combined_floats(c, tc_max, 1 + nd), false, &P); if (rc) return rc;
+  rc = snap_point_capacity(c, g, P); if (rc) return rc;
+  const float* lat = a->rows;
+  float* D = P.extra;
+  float* DD = D + dir_f;
+  if (lat_in) {
+    launch_dir_rows(a->drows, T, nd, r, D, c->st);
+    if (a->ddrows) launch_dir_rows(a->ddrows, T, nd * nd, r, DD, c->st);
+    else DD = nullptr;
+  } else {      // dz/dp per column as the first-order call forms it (k_mlp_jac), d2z/dp_a dp_b per pair (k_pjac2), over the T rows
+    rc = ensure_packed_p32(c); if (rc) return rc;
+    rc = c->d_c.reserve(c, ((T + 31) / 32) * 32 * r); if (rc) return rc;
+    for (int j = 0; j < nd; ++j) {
+      PNetArgs pj = pa; pj.Z = c->DZ;      // (primal again into a scratch)
+      launch_mlp_jac(pj, c->NSTB, a->p_idx[j], c->d_c, c->st);
+      launch_tiles_to_rows(c->d_c, T, r, D + (long)j * T * r, c->st);
+    }
+    for (int i = 0; i < nd; ++i)
+      for (int j = i; j < nd; ++j) {
+        launch_pjac2(pa, a->p_idx[i], a->p_idx[j], c->d_c, c->st);
+        launch_tiles_to_rows(c->d_c, T, r, DD + (long)(i * nd + j) * T * r, c->st);
+      }
+    snap_latents_from_p(c, a->rows, T, P.lat);
+    lat = P.lat;
+  }
+  return sp2_combined(c, a, P, g, tc_max, lat, D, DD, nd, I);
+}
+extern "C" int nif_snapshot_param_second_derivatives(const nif_snapparam2_args* a) {
+  SnapGeom g; HessIdx I;
+  int rc = sp2_check(a, &g, &I); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  const bool lat_in = a->rows_are_latent != 0;
+  const long n = g.n, nd = lat_in ? a->nd : a->np, n_p = n * a->ny * nd;
+  SnapSeg s[9] = {{a->rows, nullptr, g.T * (lat_in ? c->r : c->pi)}, {a->drows, nullptr, lat_in ? g.T * nd * c->r : 0},
+                  {a->ddrows, nullptr, (lat_in && a->ddrows) ? g.T * nd * nd * c->r : 0}, {a->x, nullptr, (g.off ? n : g.M) * c->si},
+                  {nullptr, a->u, n * c->so}, {nullptr, a->dudp, n_p}, {nullptr, a->d2udp2, n_p * nd},
+                  {nullptr, a->dudx, n * a->ny * a->nxc}, {nullptr, a->d2udpdx, n_p * a->nxc}};
+  rc = snap_stage_in(c, s, 9); if (rc) return rc;
+  nif_snapparam2_args d = *a;
+  d.rows = s[0].dev; d.drows = lat_in ? s[1].dev : nullptr; d.ddrows = (lat_in && a->ddrows) ? s[2].dev : nullptr; d.x = s[3].dev;
+  d.u = s[4].dev; d.dudp = s[5].dev; d.d2udp2 = s[6].dev;
+  d.dudx = a->nxc ? s[7].dev : nullptr; d.d2udpdx = a->nxc ? s[8].dev : nullptr;
+  rc = nif_snapshot_param_second_derivatives_dev(&d); if (rc) return rc;
+  return snap_stage_out(c, s, 9);
 }
 
 extern "C" int nif_pnet_latent(nif_ctx* c, const float* p, int64_t B, float* lr) {

@@ -160,7 +160,9 @@ struct nif_ctx {
   // the host-pointer entry's result
   DevBuf<float> enc; DevBuf<double> enc_S;
   // snapshot-wise derivatives (nif_snapshot_derivatives*): sd_tmp takes the second-order output of an order-1 call on the routes that
-  // run the second-order kernels anyway.  (The parameter derivatives keep everything in `snap` and the point workspaces.)
+  // run the second-order kernels anyway.  (The first-order parameter derivatives keep everything in `snap` and the point workspaces;
+  // their second order, nif_snapshot_param_second_derivatives*, takes it for the last-layer route's rows over every output and for
+  // HessianLayer's results on the table route.)
   DevBuf<float> sd_tmp;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;

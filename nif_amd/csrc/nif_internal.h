@@ -488,6 +488,19 @@ void launch_snapparam_gather(const float* f, long T, long M, int so, int nd, con
 bool jac_wt_supported(const SNetArgs& a);
 void launch_jac_wt(const SNetArgs& a, long T, int ns, const float* const* wd, int pstride, int nd_total, int d0, float* dudp,
                    hipStream_t st);
+// second order of the same (nif_snapshot_param_second_derivatives*).  k_jac_wtan2.hip: ONE pair on T combined nets -- form 0
+// a general pair a < b, 1 a diagonal pair, 2 a direction x coordinate `seed`; wd_a, wd_b, wdd [T][po] the pair's tangent slot vectors
+// (wdd null: no second direction), pl_* their planes' places among the pstride planes per hidden layer at a.WF (W itself at 0); the
+// value lands in columns i0 and i1 of out [n][so][row].  Shapes: jac_wt_supported's.  k_snap.hip: the parameter rows of HessianLayer's
+// H [rows][np + nxc][np + nxc] -> d2pp [rows][np][np], d2px [rows][np][nxc]
+void launch_jac_wt2(const SNetArgs& a, long T, int form, const float* wd_a, const float* wd_b, const float* wdd, int pl_a, int pl_b,
+                    int pl_dd, int pstride, int seed, int row, int i0, int i1, float* out, hipStream_t st);
+void launch_stride_offsets(long* off, int n, long stride, hipStream_t st);      // off[q] = q stride (k_through_lw's source offsets of a contiguous stack)
+void launch_snapparam2_blocks(const float* H, long rows, int np, int nxc, float* d2pp, float* d2px, hipStream_t st);
+// rows y_idx and the columns map.src of f -> out [n][ny][map.n]: out[a][i][col] = f[map.src[col] s_r + a s_n + y_idx[i] s_y] (the last-layer
+// route: k_phi_dot's row-major results [rows][n][so], or the point-wise epilogue's [n][so][rows]; a pair's one value goes to both its places)
+struct Sp2Map { int n; int src[128]; };
+void launch_snapparam2_gather(const float* f, long n, long s_r, long s_n, long s_y, const HessIdx& I, const Sp2Map& map, float* out, hipStream_t st);
 // per-snapshot normal equations in the latent (k_encode.hip, nif_snapshot_normal_eq*).  The snapshots t0 .. t1 of a call in
 // the padded layout: snapshot t owns the 32-point tiles tile_start[t] .. tile_start[t + 1] (whole tiles: no tile straddles two
 // snapshots; padding points repeat the snapshot's last point and weigh 0), its points are offsets[t] .. offsets[t + 1] of x / y / w

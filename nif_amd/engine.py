@@ -419,6 +419,62 @@ class Engine(object):
         return self._ragged("nif_snapshot_param_derivatives", "snapshot_param_derivatives_ragged", rows, xs,
                             lambda *g: self._snapshot_param_derivs(rows, drows, *g, y_index, p_index))
 
+    # ---- their second order (include/nif_hip_snapparam2.h; Model.predict_snapshot_parameter_derivatives(order=2) plans the chunks) ----
+    def _snapshot_param_second_derivs(self, rows, drows, ddrows, d_x, x_off, offsets, m, n, y_index, p_index, x_index):
+        self._not_capturing("nif_snapshot_param_second_derivatives")
+        s = self.spec
+        is_latent = drows is not None
+        rows = self._snapshot_rows(rows, is_latent)
+        yi = np.ascontiguousarray(list(y_index), dtype=np.int32)
+        xi = np.ascontiguousarray(list(x_index or []), dtype=np.int32)
+        if is_latent:
+            drows = np.ascontiguousarray(drows, dtype=np.float32)
+            if drows.ndim != 3 or drows.shape[0] != rows.shape[0] or drows.shape[2] != s.pi_hidden:
+                raise ValueError("dlatent: expected shape (%d, nd, %d), got %s" % (rows.shape[0], s.pi_hidden, drows.shape))
+            pi_, nd = None, drows.shape[1]
+            if ddrows is not None:
+                ddrows = np.ascontiguousarray(ddrows, dtype=np.float32)
+                if ddrows.shape != (rows.shape[0], nd, nd, s.pi_hidden):
+                    raise ValueError("d2latent: expected shape (%d, %d, %d, %d), got %s" % (rows.shape[0], nd, nd, s.pi_hidden, ddrows.shape))
+        else:
+            pi_ = np.ascontiguousarray(list(p_index), dtype=np.int32)
+            nd, ddrows = pi_.size, None
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        ny, nxc = yi.size, xi.size
+
+        def call(d_r, o):
+            a = _lib.nif_snapparam2_args()
+            a.abi_version, a.ctx = _lib.NIF_SNAPPARAM2_ABI_VERSION, self.ctx
+            self._snapshot_geometry(a, d_r, rows, is_latent, d_x, x_off, off, m, yi)
+            if is_latent:
+                a.drows, a.nd = d_r.at(rows.size), nd
+                if ddrows is not None:
+                    a.ddrows = d_r.at(rows.size + drows.size)
+            else:
+                a.p_idx, a.np = pi_.ctypes.data_as(C.POINTER(C.c_int32)), nd
+            a.u, a.dudp, a.d2udp2 = o[0], o[1], o[2]
+            if nxc:
+                a.x_idx, a.nxc = xi.ctypes.data_as(C.POINTER(C.c_int32)), nxc
+                a.dudx, a.d2udpdx = o[3], o[4]
+            return self.lib.nif_snapshot_param_second_derivatives_dev(C.byref(a))
+        uploads = [rows] + ([drows] if is_latent else []) + ([ddrows] if ddrows is not None else [])
+        shapes = [(n, s.so_dim), (n, ny, nd), (n, ny, nd, nd)] + ([(n, ny, nxc), (n, ny, nd, nxc)] if nxc else [])
+        return tuple(self._snapshot_call(uploads, shapes, call))
+
+    def snapshot_param_second_derivatives(self, rows, drows, ddrows, mesh, lo, hi, y_index, p_index, x_index):
+        """rows [T, pi] with p_index (drows, ddrows None), or latents [T, r] with directions drows [T, nd, r] and second directions
+        ddrows [T, nd, nd, r] (or None), on the points lo .. hi of a snapshot_mesh handle -> (u [T, hi - lo, so],
+        dudp [T, hi - lo, ny, nd], d2udp2 [T, hi - lo, ny, nd, nd][, dudx [T, hi - lo, ny, nx], d2udpdx [T, hi - lo, ny, nd, nx]]), the
+        last two with a non-empty x_index (coordinates from 0)"""
+        return self._shared(rows, mesh, lo, hi,
+                            lambda *g: self._snapshot_param_second_derivs(rows, drows, ddrows, *g, y_index, p_index, x_index))
+
+    def snapshot_param_second_derivatives_ragged(self, rows, drows, ddrows, xs, y_index, p_index, x_index):
+        """rows [T, .] (and drows, ddrows) and T coordinate arrays [M_t, si] (M_t = 0 allowed) -> the same outputs [sum M_t, ...],
+        snapshot after snapshot"""
+        return self._ragged("nif_snapshot_param_second_derivatives", "snapshot_param_second_derivatives_ragged", rows, xs,
+                            lambda *g: self._snapshot_param_second_derivs(rows, drows, ddrows, *g, y_index, p_index, x_index))
+
     # ---- encoding (include/nif_hip_encode.h; nif_amd/encode.py runs the Levenberg-Marquardt loop around these two) ----------
     def snapshot_samples(self, x, y, w=None, counts=None):
         """The samples of T snapshots on the device, uploaded once for all snapshot_normal_eq calls of one encode.  counts None: a

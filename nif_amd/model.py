@@ -375,7 +375,8 @@ class Model(object):
                                   lambda rows, il, mesh, lo, hi: e.snapshot_derivatives(rows, il, mesh, lo, hi, yi, xi, order),
                                   lambda rows, il, xs: e.snapshot_derivatives_ragged(rows, il, xs, yi, xi, order))
 
-    def predict_snapshot_parameter_derivatives(self, x, p=None, p_index=None, latent=None, dlatent=None, y_index=None, batch_size=None):
+    def predict_snapshot_parameter_derivatives(self, x, p=None, p_index=None, latent=None, dlatent=None, y_index=None, order=1, d2latent=None,
+                                               x_index=None, batch_size=None):
         """predict_snapshots with the field's first derivative in the other half of the input vector: x, p | latent and batch_size as
         there.  With p [T, pi]: p_index lists distinct ParameterNet input columns 0 <= c < pi (default: all of them), and
         dudp[t][m, i, c] = d u_{y_index[i]} / d p_{p_index[c]} -- for snapshot t what JacobianLayer(model, y_index, p_index) returns on
@@ -385,11 +386,23 @@ class Model(object):
         returns (u [T, M, so], dudp [T, M, ny, nd]); a list / tuple of meshes: a tuple of lists of [M_t, ...] arrays.  The ParameterNet
         and its tangents run once per snapshot; the hypernetwork classes run 1 + 2 g hidden products per layer for a group of g <= 3
         directions on the snapshot's combined matrices and their tangents.  Device staging is bounded by
-        _SNAPSHOT_CHUNK_BYTES as in predict_snapshots; the result does not depend on it."""
+        _SNAPSHOT_CHUNK_BYTES as in predict_snapshots; the result does not depend on it.
+        order=2 (at most 8 columns or directions) adds d2udp2 [T, M, ny, nd, nd] and, with x_index (distinct coordinates 0 <= j < si),
+        dudx [T, M, ny, nx] and the mixed block d2udpdx [T, M, ny, nd, nx]: returns (u, dudp, d2udp2[, dudx, d2udpdx]).  With p they are
+        the blocks of what HessianLayer(model, y_index, p_index + [pi + j for j in x_index]) returns on the same table (d2udx2 stays
+        with predict_snapshot_derivatives).  With latent: d2udp2[t][m, i, a, b] = d2u_i/dz2 [dlatent[t, a], dlatent[t, b]] +
+        du_i/dz . d2latent[t, a, b] and d2udpdx[t][m, i, a, j] = d2u_i/dz dx_j [dlatent[t, a]]; d2latent [T, nd, nd, r] (default: zeros)
+        is symmetric in its two direction axes.  u and dudp are bit for bit the order=1 call's, and d2udp2[..., a, b] and [..., b, a] are
+        one value.  The hypernetwork classes run one launch per pair on the snapshot's combined matrices, their tangents and second
+        tangents."""
         who = "predict_snapshot_parameter_derivatives"
         s = self._owner._spec
         if self._role != "full":
             raise ValueError("%s exists on the full model only (%s is a sub-model view)" % (who, self._role))
+        if order not in (1, 2):
+            raise ValueError("%s: order must be 1 or 2, got %r" % (who, order))
+        if order == 1 and (d2latent is not None or x_index is not None):
+            raise ValueError("%s: d2latent and x_index go with order=2" % who)
         if (p is None) == (latent is None):
             raise ValueError("%s: exactly one of p [T, pi] and latent [T, r]" % who)
         if (latent is None) != (dlatent is None):
@@ -423,6 +436,39 @@ class Model(object):
         # (last-layer class: also the so * r rows of phi)
         per_point = 4 * (s.pi_dim + s.si_dim + s.so_dim + s.pi_hidden * (1 + min(nd, 3)) + (ny + s.so_dim) * nd +
                          (s.so_dim * s.pi_hidden if s.connectivity == "last_layer" else 0))
+        if order == 2:
+            if nd > 8:
+                raise ValueError("%s: order=2 takes at most 8 %s, got %d" % (who, "parameter columns" if dl is None else "directions", nd))
+            xi = [] if x_index is None else [int(j) for j in x_index]
+            if x_index is not None and (not xi or any(j < 0 or j >= s.si_dim for j in xi)):
+                raise ValueError("%s: x_index lists coordinates 0 <= j < %d, got %r" % (who, s.si_dim, xi))
+            if len(set(xi)) != len(xi):
+                raise ValueError("%s: x_index repeats an index: %r" % (who, xi))
+            d2 = None
+            if d2latent is not None:
+                if dl is None:
+                    raise ValueError("%s: d2latent goes with latent and dlatent, not with p" % who)
+                d2 = np.ascontiguousarray(d2latent, dtype=np.float32)
+                if d2.shape != (dl.shape[0], nd, nd, s.pi_hidden):
+                    raise ValueError("%s: expected d2latent of shape (%d, %d, %d, %d), got %s" % (who, dl.shape[0], nd, nd, s.pi_hidden, d2.shape))
+                if not np.array_equal(d2.view(np.uint32), np.ascontiguousarray(d2.transpose(0, 2, 1, 3)).view(np.uint32)):
+                    raise ValueError("%s: d2latent must be symmetric in its two direction axes (bit for bit)" % who)
+            nx = len(xi)
+            tails = [(s.so_dim,), (ny, nd), (ny, nd, nd)] + ([(ny, nx), (ny, nd, nx)] if nx else [])
+            # the new rows: the pair and mixed results over every output, the gathered ones, and the first-order coordinate rows
+            per_point += 4 * ((ny + s.so_dim) * (nd * nd + nd * nx + nx))
+            if dl is None:
+                return self._snapshot_run(
+                    who, x, p, latent, batch_size, per_point, tails,
+                    lambda rows, il, mesh, lo, hi: e.snapshot_param_second_derivatives(rows, None, None, mesh, lo, hi, yi, pi_, xi),
+                    lambda rows, il, xs: e.snapshot_param_second_derivatives_ragged(rows, None, None, xs, yi, pi_, xi))
+            # (one per-snapshot array beside the rows: the directions, then the nd * nd second directions)
+            both = dl if d2 is None else np.concatenate([dl, d2.reshape(dl.shape[0], nd * nd, s.pi_hidden)], axis=1)
+            split = (lambda b: (b, None)) if d2 is None else (lambda b: (b[:, :nd], b[:, nd:].reshape(b.shape[0], nd, nd, s.pi_hidden)))
+            return self._snapshot_run(
+                who, x, p, latent, batch_size, per_point, tails,
+                lambda rd, il, mesh, lo, hi: e.snapshot_param_second_derivatives(rd[0], *split(rd[1]), mesh, lo, hi, yi, None, xi),
+                lambda rd, il, xs: e.snapshot_param_second_derivatives_ragged(rd[0], *split(rd[1]), xs, yi, None, xi), extra=both)
         if dl is None:
             return self._snapshot_run(who, x, p, latent, batch_size, per_point, [(s.so_dim,), (ny, nd)],
                                       lambda rows, il, mesh, lo, hi: e.snapshot_param_derivatives(rows, None, mesh, lo, hi, yi, pi_),
