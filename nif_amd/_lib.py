@@ -276,6 +276,24 @@ SNAPPARAM2_SIGNATURES = {
 }
 
 
+NIF_SNAPFIT_ABI_VERSION = 1
+
+
+class nif_snapfit_args(C.Structure):
+    """include/nif_hip_snapfit.h, field for field"""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("reserved0", C.c_int32), ("ctx", _CTX), ("p", _VP), ("T", C.c_int64), ("x", _VP), ("M", C.c_int64),
+        ("y", _VP), ("sw", _VP), ("batch_global", C.c_int64), ("reserved", C.c_int64 * 4),
+    ]
+
+
+# include/nif_hip_snapfit.h, one to one (bound by load() with the tables above)
+SNAPFIT_SIGNATURES = {
+    "nif_snapshot_loss_grad": (C.c_int, [C.POINTER(nif_snapfit_args)]),
+    "nif_snapshot_loss_grad_dev": (C.c_int, [C.POINTER(nif_snapfit_args)]),
+}
+
+
 def load():
     """dlopen libnif_hip.so and bind every symbol of include/nif_hip.h.  Raises if it is absent."""
     global _lib
@@ -287,7 +305,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
     for table in (SIGNATURES, SNAPSHOT_SIGNATURES, ENCODE_SIGNATURES, SNAPDERIV_SIGNATURES, SNAPPARAM_SIGNATURES,
-                  SNAPPARAM2_SIGNATURES):
+                  SNAPPARAM2_SIGNATURES, SNAPFIT_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the library does not export it
             fn.restype = res

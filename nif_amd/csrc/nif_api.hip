@@ -18,6 +18,7 @@
 #include "../../include/nif_hip_snapparam.h"
 #include "../../include/nif_hip_snapparam2.h"
 #include "../../include/nif_hip_encode.h"
+#include "../../include/nif_hip_snapfit.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
 static inline bool act_on(const nif_ctx* c) { return c->act_l1 != 0.f || c->act_l2 != 0.f; }
@@ -807,6 +808,7 @@ static bool snap_reserved(const nif_encode_args& a) { return a.reserved0 != 0; }
 static bool snap_reserved(const nif_snapderiv_args& a) { return a.reserved0 || a.reserved1 || a.reserved2; }
 static bool snap_reserved(const nif_snapparam_args& a) { return a.reserved0 != 0; }
 static bool snap_reserved(const nif_snapparam2_args&) { return false; }
+static bool snap_reserved(const nif_snapfit_args& a) { return a.reserved0 != 0; }
 template <class A>
 static int snap_args_check(const A* a, int version, const char* name) {
   if (!a) return fail(NIF_ERR_INVALID, "null");
@@ -2188,11 +2190,12 @@ static void gw_add_tangents(GwArgs& q, int n, const int* seeds) {
   q.zt_mod = q.ntiles; q.bias_ntiles = q.ntiles; q.ntiles *= 1 + n;
   for (int d = 0; d < 3; ++d) q.seed[d] = (seeds && d < n) ? seeds[d] : 0;
 }
-// ParameterNet: first layer, hidden matrices, bottleneck -- from the stash slots at pST, SM = dL/d(bottleneck output)
+// ParameterNet: first layer, hidden matrices, bottleneck -- from the stash slots at pST, SM = dL/d(bottleneck output).  ncol: the
+// columns of xin's rows (0: the table's pi + si; the snapshot step's rows of p alone: pi)
 static void gw_pnet_stack(const nif_ctx* c, const GwArgs& base, const float* xin, const float* pST, const float* SM, float omega, int rows,
-                          hipStream_t st) {
+                          hipStream_t st, int ncol = 0) {
   GwArgs g = base;
-  g.DA = pST + (long)(c->nm + 1) * c->slot_p; g.xin = xin; g.ncol = c->pi + c->si; g.col0 = 0; g.nd = c->pi; g.scale = omega;
+  g.DA = pST + (long)(c->nm + 1) * c->slot_p; g.xin = xin; g.ncol = ncol > 0 ? ncol : c->pi + c->si; g.col0 = 0; g.nd = c->pi; g.scale = omega;
   g.W = dense_ref(c->first_w, c->pi, c->nst); g.Bv = vec_ref(c->first_b, c->nst);
   launch_gw_first(g, c->NSTB, rows, st);
   for (int mi = 0; mi < c->nm; ++mi) {
@@ -2713,6 +2716,139 @@ extern "C" int nif_loss_grad_dev(nif_ctx* c, const float* xin, const float* y, c
   if (!c || !xin || !y || B <= 0 || Bg < B) return fail(NIF_ERR_INVALID, "bad argument");
   NIF_ENTER(c, NIF_FLUSH_TAIL)      // (a step whose gradient was never consumed: its rows are about to be overwritten)
   return loss_grad_core(c, xin, y, sw, B, Bg, 0, nullptr, nullptr, 0.f);
+}
+
+// ---- the snapshot-wise training step of the last-layer class (include/nif_hip_snapfit.h, k_snapfit.hip) ----------------
+// loss_grad_ll's step on the table [repeat(p, M) | tile(x, T)] from its factors: the ParameterNet over the T rows of p, the ShapeNet
+// (with its training stash) over the M rows of x, the head over (t, m), then each net's adjoint and weight-gradient reductions over its
+// own tiles.
+static int snapfit_check(const nif_snapfit_args* a) {
+  int rc = snap_args_check(a, NIF_SNAPFIT_ABI_VERSION, "nif_snapfit_args"); if (rc) return rc;
+  const nif_ctx* c = a->ctx;
+  const char* who = "nif_snapshot_loss_grad";
+  if (!c || a->T < 0 || a->M < 0 || a->batch_global < 0) return fail(NIF_ERR_INVALID, "bad argument");
+  const int64_t n = a->T * a->M;
+  if (n > 0 && (!a->p || !a->x || !a->y)) return fail(NIF_ERR_INVALID, "bad argument");
+  if (a->batch_global != 0 && a->batch_global < n) return fail(NIF_ERR_INVALID, "bad argument");
+  if (c->kind != NIF_KIND_LASTLAYER)
+    return fail(NIF_ERR_INVALID, std::string(who) + ": not built for the hypernetwork classes (NIF, NIFMultiScale): their weight gradients are "
+                                 "per-snapshot sums no kernel forms; the step factors for NIFMultiScaleLastLayerParameterized only");
+  if (c->cfg.mixed_policy != NIF_POLICY_FLOAT32)
+    return fail(NIF_ERR_INVALID, std::string(who) + ": not built for the " +
+                                 (c->cfg.mixed_policy == NIF_POLICY_MIXED_BF16 ? "mixed_bfloat16" : "mixed_float16") + " policy");
+  if (act_on(c)) return fail(NIF_ERR_INVALID, std::string(who) + ": not built with an activity regulariser set on the context");
+  if (c->jac_l1 != 0.f) return fail(NIF_ERR_INVALID, std::string(who) + ": not built with a latent Jacobian regulariser set on the context");
+  if (!snapfit_supported(c->r, c->so))
+    return fail(NIF_ERR_INVALID, std::string(who) + ": so * latent_dim = " + std::to_string(c->so * c->r) + " > 64");
+  return snap_not_capturing(c, who);
+}
+static int snapshot_loss_grad_core(nif_ctx* c, const float* p, const float* x, const float* y, const float* sw, long T, long M, long Bg) {
+  c->last_step_small = false;
+  int rc = nif_metric_flush(c); if (rc) return rc;      // (grad[P] is rewritten without a k_small launch)
+  rc = ensure_packed(c); if (rc) return rc;
+  if (T == 0 || M == 0) {
+    HIPCHK(hipMemsetAsync(c->grad, 0, sizeof(float) * (size_t)(c->P + 1), c->st));
+    c->grad_rewritten();
+    return NIF_OK;
+  }
+  rc = ensure_capacity(c, T > M ? T : M, true); if (rc) return rc;
+  rc = c->sf_dap.reserve(c, snapfit_dap_floats(T, M, c->r)); if (rc) return rc;
+  c->grad_rewritten();
+  const long mtiles = (M + 31) / 32, ttiles = (T + 31) / 32;
+  const int si = c->si;
+  PNetArgs pa; fill_pnet(c, pa, p, T); pa.ncol = c->pi;
+  const bool fused_p = !pnet_force_stash() && pnet_bwg_supported(pa);
+  if (!fused_p) { const int rcp = ensure_packed_p32(c); if (rcp) return rcp; }
+  { ProfScope p_(c, NIF_PROF_PNET_FWD); launch_pnet(pa, c->NSTB, !fused_p, c->st); }
+  PNetArgs ma;
+  if (!c->use_wide) { ensure_ll_mlp_planes(c); fill_snet_mlp(c, ma, x, si, 0, M); }
+  {      // phi of the mesh, stashed: the 32-point MLP kernels (k_snet4<.., LL> fuses the point-wise head), layer by layer from 129 units
+    ProfScope p_(c, NIF_PROF_SNET_FWD);
+    if (c->use_wide) wide_forward(c, x, si, 0, M, true);
+    else launch_pnet(ma, c->NB, true, c->st);
+  }
+  {
+    SnapFitArgs ha; memset(&ha, 0, sizeof(ha));
+    ha.loss_kind = c->loss_kind; ha.PHI = c->PHI; ha.A = c->Z; ha.bias = c->theta + c->ll_bias; ha.last_w = c->theta + c->last_w;
+    ha.y = y; ha.sw = sw; ha.T = T; ha.M = M; ha.r = c->r; ha.so = c->so; ha.inv_bg = 1.0f / (float)Bg;
+    ha.DPHI = c->DPHI; ha.DU = c->DU; ha.DAP = c->sf_dap; ha.DA = c->DA; ha.DZL = c->DZL; ha.loss_partial = c->loss_partial;
+    ProfScope p_(c, NIF_PROF_SNET);
+    launch_snapfit_head(ha, c->st);
+    launch_snapfit_da(ha, c->st);
+  }
+  // The ShapeNet's reductions run over the mesh tiles, the ParameterNet's over the snapshot tiles: each group gets the partial rows of
+  // its own tile count and is reduced on its own below (the two column ranges of a row are disjoint: theta is [ParameterNet | ShapeNet]),
+  // so nothing depends on what a reduction kernel leaves in a row it has no tile for
+  const int rows_m = rows_for(c, mtiles), rows_t = rows_for(c, ttiles);
+  if (c->use_wide) wide_backward(c, x, si, 0, M, rows_m);
+  {
+    ProfScope p_(c, NIF_PROF_GW);
+    const GwArgs base = gw_base(c, mtiles, M, c->partial);
+    GwArgs g = base;
+    if (!c->use_wide) {
+      launch_pnet_bwd(ma, c->NB, c->st);
+      const int nms = c->nh;
+      float* sST = c->stash_s;
+      g.DA = sST + (long)(nms + 1) * c->slot_s; g.xin = x; g.ncol = si; g.col0 = 0; g.nd = si; g.scale = ma.omega;
+      g.W = dense_ref(c->s_first_w, c->si, c->n); g.Bv = vec_ref(c->s_first_b, c->n);
+      launch_gw_first(g, c->NB, rows_m, c->st);
+      for (int mi = 0; mi < nms; ++mi) {
+        g = base; g.IN = sST + (long)mi * c->slot_s; g.DA = sST + (long)(nms + 2 + mi) * c->slot_s; g.scale = ma.omega;
+        long w_off, b_off; snet_mat(c, mi, &w_off, &b_off);
+        g.W = dense_ref(w_off, c->n, c->n); g.Bv = vec_ref(b_off, c->n);
+        if (launch_gw_mfma(g, c->NB, c->NB, rows_m, c->st) < 0) return fail(NIF_ERR_STATE, "internal: no reader for the hidden matrices' stash rows");
+      }
+      g = base; g.IN = sST + (long)nms * c->slot_s; g.SM = c->DPHI; g.nc = c->r * c->so;
+      g.W = dense_ref(c->s_bott_w, c->n, c->r * c->so); g.Bv = vec_ref(c->s_bott_b, c->r * c->so);
+      launch_gw_out(g, c->NB, rows_m, c->st);
+    }
+    g = base; g.IN = c->use_wide ? nullptr : c->stash_s + (long)c->nh * c->slot_s; g.SM = c->DU; g.nc = c->so;   // (k_gw_bias reads SM alone)
+    g.W = dense_ref(0, 0, c->so); g.Bv = vec_ref(c->ll_bias, c->so);
+    launch_gw_out(g, c->NB, rows_m, c->st);
+  }
+  {
+    ProfScope p_(c, NIF_PROF_PNET_BWD);
+    if (fused_p) launch_pnet_bwg(pa, c->partial, c->pstride, rows_t, c->st);
+    else launch_pnet_bwd(pa, c->NSTB, c->st);
+    const GwArgs base = gw_base(c, ttiles, T, c->partial);
+    if (!fused_p) gw_pnet_stack(c, base, p, c->stash_p, c->DZL, pa.omega, rows_t, c->st, c->pi);
+    GwArgs g = base; g.IN = c->ZL; g.SM = c->DA; g.nc = c->r;   // latent (padded rows) x dL/da
+    g.W = dense_ref(c->last_w, c->r, c->r); g.Bv = vec_ref(c->last_b, c->r);
+    launch_gw_out(g, c->RB, rows_t, c->st);
+  }
+  {
+    ProfScope pr_(c, NIF_PROF_REDUCE);
+    const long np = c->s_first_w;      // (the loss slot of the first reduction is the first column of the second)
+    launch_reduce(c->partial, c->pstride, rows_t, nullptr, 0, c->grad, np, c->st);
+    launch_reduce(c->partial + np, c->pstride, rows_m, c->loss_partial, (int)mtiles, c->grad + np, c->P - np, c->st);
+  }
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_snapshot_loss_grad_dev(const nif_snapfit_args* a) {
+  int rc = snapfit_check(a); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  const long n = (long)(a->T * a->M);
+  return snapshot_loss_grad_core(c, a->p, a->x, a->y, a->sw, (long)a->T, (long)a->M, a->batch_global ? (long)a->batch_global : n);
+}
+extern "C" int nif_snapshot_loss_grad(const nif_snapfit_args* a) {
+  int rc = snapfit_check(a); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  const long T = (long)a->T, M = (long)a->M, n = T * M;
+  nif_snapfit_args d = *a;
+  if (n > 0) {
+    rc = stage(c, c->d_a, a->p, T * c->pi); if (rc) return rc;
+    rc = stage(c, c->d_b, a->x, M * c->si); if (rc) return rc;
+    rc = stage(c, c->d_d, a->y, n * c->so); if (rc) return rc;
+    if (a->sw) { rc = stage(c, c->d_c, a->sw, n); if (rc) return rc; }
+    d.p = c->d_a; d.x = c->d_b; d.y = c->d_d; d.sw = a->sw ? c->d_c.p : nullptr;
+  }
+  rc = nif_snapshot_loss_grad_dev(&d); if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
 }
 
 // Size every workspace of a training step over up to B_max points (n_tangents Sobolev seeds, 0 = plain step) now, so

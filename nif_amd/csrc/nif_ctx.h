@@ -164,6 +164,8 @@ struct nif_ctx {
   // their second order, nif_snapshot_param_second_derivatives*, takes it for the last-layer route's rows over every output and for
   // HessianLayer's results on the table route.)
   DevBuf<float> sd_tmp;
+  // the snapshot-wise training step (nif_snapshot_loss_grad*, k_snapfit.hip): every mesh tile's share of dL/da, [mesh tiles][T][r]
+  DevBuf<float> sf_dap;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

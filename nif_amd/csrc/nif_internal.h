@@ -404,6 +404,27 @@ struct LLArgs {
   float* loss_partial;  // [gridDim.x]
 };
 void launch_ll_out(const LLArgs& a, bool train, hipStream_t st);
+// the same head for T snapshots on one shared mesh of M points (k_snapfit.hip; include/nif_hip_snapfit.h): phi of the mesh, a of the
+// snapshots, the sums over t inside a mesh tile's workgroup, the sum over m as per-tile partials and an ordered second kernel
+struct SnapFitArgs {
+  int loss_kind;
+  const float* PHI;     // [mesh tiles][so*r][32]
+  const float* A;       // [snapshot tiles][r][32]   pnet output a of the T rows of p
+  const float* bias;    // last_layer_bias [so]
+  const float* last_w;  // pnet last layer W[r][r]
+  const float* y; const float* sw;   // [T][M][so], [T][M] or null
+  long T, M; int r, so; float inv_bg;
+  float* DPHI;          // [mesh tiles][so*r][32]   summed over t
+  float* DU;            // [mesh tiles][so][32]     summed over t
+  float* DAP;           // [mesh tiles][T][r]       one mesh tile's share of dL/da
+  float* DA;            // [snapshot tiles][r][32]  dL/da
+  float* DZL;           // [snapshot tiles][r][32]  dL/d latent (through the r x r map)
+  float* loss_partial;  // [mesh tiles]
+};
+bool snapfit_supported(int r, int so);              // so * r <= 64 (the head's register sums)
+long snapfit_dap_floats(long T, long M, int r);
+void launch_snapfit_head(const SnapFitArgs& a, hipStream_t st);      // grid = mesh tiles
+void launch_snapfit_da(const SnapFitArgs& a, hipStream_t st);        // grid = snapshot tiles; behind the head
 // last-layer class at 129..512 units: one dense layer of the shared SIREN ShapeNet per launch, tiled over a workgroup (k_wide.hip).
 // Every activation / adjoint buffer is [tiles][features][32] with exactly `features` rows per tile (the layout of PHI / DPHI)
 struct WideArgs {

@@ -628,6 +628,41 @@ class Engine(object):
     def loss_grad_dev(self, d_x, d_y, d_sw, b_local, b_global):
         check(self.lib.nif_loss_grad_dev(self.ctx, d_x, d_y, d_sw, int(b_local), int(b_global)))
 
+    # snapshot-wise step of the last-layer class (include/nif_hip_snapfit.h; Model.fit_snapshots plans the steps)
+    def _snapfit_args(self, p, t, x, m, y, sw, batch_global):
+        a = _lib.nif_snapfit_args()
+        a.abi_version, a.ctx, a.T, a.M, a.batch_global = _lib.NIF_SNAPFIT_ABI_VERSION, self.ctx, int(t), int(m), int(batch_global)
+        a.p, a.x, a.y, a.sw = p, x, y, sw
+        return a
+
+    def snapshot_loss_grad_dev(self, d_p, t, d_x, m, d_y, d_sw, batch_global=0):
+        """[grad | loss] of nif_loss_grad_dev on the table [repeat(p, M) | tile(x, T)], from device pointers p [T, pi], x [M, si],
+        y [T, M, so], sw [T, M] or None; batch_global 0 = T M.  Leaves the result where loss_grad_dev leaves it"""
+        a = self._snapfit_args(d_p, t, d_x, m, d_y, d_sw, batch_global)
+        check(self.lib.nif_snapshot_loss_grad_dev(C.byref(a)))
+
+    def snapshot_loss_grad(self, p, x, y, sample_weight=None, batch_global=0, want_grad=True):
+        """host arrays p [T, pi], x [M, si], y [T, M, so], sample_weight [T, M] or None -> (total loss, flat gradient)"""
+        s = self.spec
+        p = self._rows(p, s.pi_dim, "parameter inputs")
+        x = self._rows(x, s.si_dim, "coordinates")
+        t, m = p.shape[0], x.shape[0]
+        y = _f32(y)
+        if y.shape == (t, m) and s.so_dim == 1:
+            y = y[:, :, None]
+        if y.shape != (t, m, s.so_dim):
+            raise ValueError("snapshot_loss_grad: expected targets of shape (%d, %d, %d), got %s" % (t, m, s.so_dim, y.shape))
+        sw = None
+        if sample_weight is not None:
+            sw = _f32(sample_weight)
+            if sw.shape != (t, m):
+                raise ValueError("snapshot_loss_grad: expected sample_weight of shape (%d, %d), got %s" % (t, m, sw.shape))
+        a = self._snapfit_args(ptr(p), t, ptr(x), m, ptr(y), ptr(sw), batch_global)
+        check(self.lib.nif_snapshot_loss_grad(C.byref(a)))
+        if not want_grad:
+            return self.grad_read_loss(), None
+        return self.grad_read()
+
     # Sobolev (two-output model u, du/dx; include/nif_hip.h nif_sobolev_*)
     def sobolev_loss_grad_dev(self, d_x, d_y, d_g, d_sw, b_local, b_global, x_index, w_jac, y_index=None):
         """y_index = None: the derivative term over every output; else over the listed outputs (d_g rows stay [so][nx])"""

@@ -723,10 +723,170 @@ class Model(object):
             if ema is not None:
                 e.set_ema(None)
 
-    def _fit(self, e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch, validation_data,
-             steps_per_epoch):
+    def fit_snapshots(self, x, u, p, sample_weight=None, epochs=1, snapshots_per_step=None, shuffle=True, callbacks=None, verbose=0,
+                      initial_epoch=0):
+        """fit() for T snapshots u [T, M, so] on one shared mesh x [M, si] with the ParameterNet inputs p [T, pi], without the
+        [T M, pi + si] table: for NIFMultiScaleLastLayerParameterized the field is phi(x) . a(p) + bias, so a step runs the ShapeNet
+        over the M mesh points and the ParameterNet over its snapshots' rows of p, and only the head is O(T M)
+        (include/nif_hip_snapfit.h).  A step is `snapshots_per_step` whole snapshots on the full mesh (None: all T; the last step of an
+        epoch may be shorter); per epoch one permutation of the snapshots, gathered on the device.  It computes what fit() computes on
+        the expanded table hstack([repeat(p, M), tile(x, T)]) with batch_size = snapshots_per_step * M and the same snapshots per
+        batch.  sample_weight: [T, M], [M] (per mesh point) or [T] (per snapshot).  Behind every step the tail of fit(): the compiled
+        optimizer with its gradient transform and weight average, the pruning hooks, the loss metric, callbacks and History["loss"].
+        Not built: the hypernetwork classes, mesh blocks per step, ragged meshes, mixed policies, the activity and latent-Jacobian
+        regularisers, more than one GPU, compile(metrics=...)."""
+        if self._role != "full" or self.optimizer is None:
+            raise RuntimeError("You must compile your model before training/testing. Use `model.compile(optimizer, loss)`.")
+        s = self._owner._spec
+        if s.kind != "NIFMultiScaleLastLayerParameterized":
+            raise NotImplementedError("fit_snapshots: built for NIFMultiScaleLastLayerParameterized, whose field factors into "
+                                      "phi(x) . a(p); %s needs a per-snapshot weight-gradient kernel that does not exist "
+                                      "(fit() on the expanded table trains it)" % s.kind)
+        if s.mixed_policy != "float32":
+            raise NotImplementedError("fit_snapshots: not built for the %s policy" % s.mixed_policy)
+        comm = dist.get()
+        if comm is not None and comm.world > 1:
+            raise NotImplementedError("fit_snapshots: one GPU (world = %d)" % comm.world)
+        if getattr(self, "_metrics", []):
+            raise NotImplementedError("fit_snapshots: compile(metrics=...) is not built (History carries 'loss')")
+        if self._jac_reg or self._po_l1 or tuple(getattr(self._owner, "_act_reg", (0.0, 0.0))) != (0.0, 0.0):
+            raise NotImplementedError("fit_snapshots: not built with an activity or latent-Jacobian regulariser")
+        ema = ema_of(self.optimizer)
+        if ema is not None and getattr(self, "_is_pruned", False):
+            raise NotImplementedError("fit_snapshots() of a pruned model (nif_amd.sparsity) with %s(use_ema=True): not built"
+                                      % type(self.optimizer).__name__)
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        if p.ndim == 1 and s.pi_dim == 1:
+            p = p[:, None]
+        if x.ndim == 1 and s.si_dim == 1:
+            x = x[:, None]
+        if x.ndim != 2 or x.shape[1] != s.si_dim:
+            raise ValueError("fit_snapshots: x must have shape (M, si_dim=%d), got %r" % (s.si_dim, x.shape))
+        if p.ndim != 2 or p.shape[1] != s.pi_dim:
+            raise ValueError("fit_snapshots: p must have shape (T, pi_dim=%d), got %r" % (s.pi_dim, p.shape))
+        T, M = p.shape[0], x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape == (T, M) and s.so_dim == 1:
+            u = u[:, :, None]
+        if u.shape != (T, M, s.so_dim):
+            raise ValueError("fit_snapshots: u must have shape (T=%d, M=%d, so_dim=%d), got %r" % (T, M, s.so_dim, u.shape))
+        sw = None
+        if sample_weight is not None:
+            w = np.asarray(sample_weight, dtype=np.float32)
+            if w.shape == (T, M):
+                sw = w
+            elif w.shape == (M,):           # (T == M: a vector weighs the mesh points)
+                sw = np.broadcast_to(w[None, :], (T, M))
+            elif w.shape == (T,):
+                sw = np.broadcast_to(w[:, None], (T, M))
+            else:
+                raise ValueError("fit_snapshots: sample_weight must have shape (T, M), (M,) or (T,) = (%d, %d), got %r" % (T, M, w.shape))
+            sw = np.ascontiguousarray(sw, dtype=np.float32)
+        k = T if snapshots_per_step is None else int(snapshots_per_step)
+        if T > 0 and k < 1:
+            raise ValueError("snapshots_per_step must be a positive integer")
+        e = self._engine
+        self._push_losses(e, 1)
+        grad_tf = grad_transform_of(self.optimizer)
+        if grad_tf is not None:
+            e.set_grad_transform(grad_tf)
+        try:
+            if ema is not None:
+                e.set_ema(*ema)
+            return self._fit_snapshots(e, s, x, u, p, sw, T, M, k, epochs, shuffle, callbacks, verbose, initial_epoch)
+        finally:
+            if grad_tf is not None:
+                e.set_grad_transform(None)
+            if ema is not None:
+                e.set_ema(None)
+
+    def _fit_snapshots(self, e, s, x, u, p, sw, T, M, k, epochs, shuffle, callbacks, verbose, initial_epoch):
         self.stop_training = False
-        is_adam = isinstance(self.optimizer, Adam) and self.optimizer.is_plain     # (else the step travels as a nif_opt)
+        is_adam = self._fresh_slots_init(e)
+        pi, row = s.pi_dim, M * s.so_dim          # a snapshot's row of p, and of u as [T][M so]
+        callbacks = list(callbacks or [])
+        hist = History()
+        owned = []
+
+        def resident(host, n):
+            d = e.alloc(max(1, n)); owned.append(d)
+            if host is not None and n:
+                d.upload(host)
+            return d
+        try:
+            d_x = resident(x, x.size)
+            src_p, src_u = resident(p, p.size), resident(u, u.size)
+            src_w = resident(sw, sw.size) if sw is not None else None
+            for cb in callbacks:
+                if hasattr(cb, "set_model"):
+                    cb.set_model(self)
+            for cb in callbacks:
+                if hasattr(cb, "on_train_begin"):
+                    cb.on_train_begin({})
+            gather = bool(shuffle) and T > 0 and M > 0
+            d_p, d_u, d_w = src_p, src_u, src_w
+            if gather:      # one permutation of the snapshots per epoch: 4 bytes per snapshot travel, the rows move on the device
+                d_p, d_u = resident(None, p.size), resident(None, u.size)
+                d_w = resident(None, sw.size) if sw is not None else None
+                d_perm = resident(None, T)
+            rng = np.random.default_rng(getattr(self, "_shuffle_seed", None))
+            steps = [min(k, T - t0) for t0 in range(0, T, k)] if T > 0 and M > 0 else []
+            batch_hook = self._batch_hook(e, callbacks)
+            for epoch in range(initial_epoch, epochs):
+                if self.stop_training:
+                    break
+                for cb in callbacks:
+                    if hasattr(cb, "on_epoch_begin"):
+                        cb.on_epoch_begin(epoch, {})
+                t_start = time.time()
+                if gather:
+                    perm = rng.permutation(T).astype(np.int32)
+                    d_perm.upload(perm.view(np.float32))
+                    e.gather_rows(src_p, d_perm, T, pi, d_p)
+                    e.gather_rows(src_u, d_perm, T, row, d_u)
+                    if sw is not None:
+                        e.gather_rows(src_w, d_perm, T, M, d_w)
+                adam = self.optimizer.as_struct() if is_adam else self.optimizer.as_opt()
+                step_dev = e.adam_step_dev if is_adam else e.opt_step_dev
+                self._push_losses(e, 1)           # (a callback of the previous epoch may have evaluated another model on the shared engine)
+                e.metric_read(reset=True)
+                t0 = 0
+                for ts in steps:
+                    bg = ts * M
+                    if batch_hook is not None:
+                        batch_hook()
+                    e.snapshot_loss_grad_dev(d_p.at(t0 * pi), ts, d_x.at(0), M, d_u.at(t0 * row),
+                                             d_w.at(t0 * M) if d_w is not None else None, bg)
+                    self._step_tail(e, None, step_dev, adam, bg)
+                    t0 += ts
+                tot, cnt = e.metric_read(reset=True)   # accumulated on the device: one host sync per epoch
+                logs = {"loss": tot / max(cnt, 1.0)}
+                for cb in callbacks:
+                    if hasattr(cb, "on_epoch_end"):
+                        cb.on_epoch_end(epoch, logs)
+                hist.epoch.append(epoch)
+                for key, v in logs.items():
+                    hist.history.setdefault(key, []).append(v)
+                if verbose:
+                    print("Epoch %d/%d - %.2fs - loss: %.4e" % (epoch + 1, epochs, time.time() - t_start, logs["loss"]))
+        finally:
+            self._pop_losses(e)
+            e.sync()
+            for arr in owned:
+                arr.free()
+        if ema_of(self.optimizer) is not None and epochs > initial_epoch:
+            self.optimizer.finalize_variable_values(self)
+        for cb in callbacks:
+            if hasattr(cb, "on_train_end"):
+                cb.on_train_end({})
+        self.history = hist
+        return hist
+
+    # what fit() and fit_snapshots() share around their loss-and-gradient calls
+    def _fresh_slots_init(self, e):
+        """a newly compiled optimizer starts with zero slots and iteration 0; returns whether the step travels as a plain Adam struct
+        (else as a nif_opt)"""
         if getattr(self, "_fresh_slots", False):
             z = np.zeros((e.n_params,), dtype=np.float32)
             acc0 = getattr(self.optimizer, "initial_accumulator_value", None)      # Adagrad's slot 0 starts there
@@ -736,6 +896,22 @@ class Model(object):
             if ema_of(self.optimizer) is not None:
                 e.set_opt_slot(3, e.get_flat())      # Keras creates the average with the variable's value (exists before a captured epoch)
             self._fresh_slots = False
+        return isinstance(self.optimizer, Adam) and self.optimizer.is_plain
+
+    @staticmethod
+    def _step_tail(e, comm, step_dev, adam, bg):
+        """behind a step's [grad | loss]: the cross-rank sum (comm: more than one rank), the optimizer step (with it the gradient
+        transform, the regularisers' term and the weight average, all engine state) and Keras' loss metric -- the sample-weighted mean
+        over the batches"""
+        if comm is not None:
+            comm.all_reduce_grad(e)
+        step_dev(adam)
+        e.metric_accumulate(bg)
+
+    def _fit(self, e, s, kinds, x, y, batch_size, epochs, verbose, callbacks, shuffle, sample_weight, initial_epoch, validation_data,
+             steps_per_epoch):
+        self.stop_training = False
+        is_adam = self._fresh_slots_init(e)
         ncol = s.pi_dim + s.si_dim
         shard = x if isinstance(x, ShardBatches) else None
         if shard is not None:
@@ -879,10 +1055,7 @@ class Model(object):
                                                 d_sw.at(b0) if d_sw is not None else None, b, bg)
                         else:
                             e.zero_grad()
-                        if world > 1:
-                            comm.all_reduce_grad(e)
-                        step_dev(adam)
-                        e.metric_accumulate(bg)     # Keras' loss metric: sample-weighted mean over the batches,
+                        self._step_tail(e, comm if world > 1 else None, step_dev, adam, bg)
                 if steps_per_epoch is not None:
                     # Keras with array inputs and steps_per_epoch (TensorLikeDataAdapter: ONE iterator over `epochs` successive passes,
                     # never recreated): an epoch takes its steps from where the last one stopped, a new permutation whenever a pass is
@@ -1074,8 +1247,12 @@ class SobolevModel(Model):
                 raise ValueError("loss_weights = [w_u > 0, w_dudx]")
             self.loss_weights = lw
 
+    def fit_snapshots(self, *args, **kwargs):
+        raise NotImplementedError("SobolevModel.fit_snapshots: the snapshot-wise step has no derivative outputs (fit() on the expanded "
+                                  "table trains the two- and three-output models)")
+
     def _run(self, x):
-        if self._order == 2:       # HessianLayer(model, y_index, x_index)(x), the layer the model wraps
+        if self._order == 2:      # HessianLayer(model, y_index, x_index)(x), the layer the model wraps
             return list(self._engine.hessian(x, self.y_index, self.x_index))
         u, j = self._engine.sobolev_forward(x, self.x_index)
         return [u, j if self._all_y else np.ascontiguousarray(j[:, self.y_index, :])]
