@@ -294,6 +294,24 @@ SNAPFIT_SIGNATURES = {
 }
 
 
+NIF_SENSORS_ABI_VERSION = 1
+
+
+class nif_sensors_args(C.Structure):
+    """include/nif_hip_sensors.h, field for field"""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("reserved0", C.c_int32), ("ctx", _CTX), ("x", _VP), ("M", C.c_int64), ("mask", _VP),
+        ("K", C.c_int64), ("pivots_out", _VP), ("diag_out", _VP), ("reserved", C.c_int64 * 4),
+    ]
+
+
+# include/nif_hip_sensors.h, one to one (bound by load() with the tables above)
+SENSORS_SIGNATURES = {
+    "nif_select_sensors": (C.c_int, [C.POINTER(nif_sensors_args)]),
+    "nif_select_sensors_dev": (C.c_int, [C.POINTER(nif_sensors_args)]),
+}
+
+
 def load():
     """dlopen libnif_hip.so and bind every symbol of include/nif_hip.h.  Raises if it is absent."""
     global _lib
@@ -305,7 +323,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  nif_amd has no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
     for table in (SIGNATURES, SNAPSHOT_SIGNATURES, ENCODE_SIGNATURES, SNAPDERIV_SIGNATURES, SNAPPARAM_SIGNATURES,
-                  SNAPPARAM2_SIGNATURES, SNAPFIT_SIGNATURES):
+                  SNAPPARAM2_SIGNATURES, SNAPFIT_SIGNATURES, SENSORS_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the library does not export it
             fn.restype = res

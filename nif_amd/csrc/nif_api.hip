@@ -19,6 +19,7 @@
 #include "../../include/nif_hip_snapparam2.h"
 #include "../../include/nif_hip_encode.h"
 #include "../../include/nif_hip_snapfit.h"
+#include "../../include/nif_hip_sensors.h"
 
 #define NIF_ACT_SLABS 32   // point slabs of the activity regulariser's plane pass
 static inline bool act_on(const nif_ctx* c) { return c->act_l1 != 0.f || c->act_l2 != 0.f; }
@@ -809,6 +810,7 @@ static bool snap_reserved(const nif_snapderiv_args& a) { return a.reserved0 || a
 static bool snap_reserved(const nif_snapparam_args& a) { return a.reserved0 != 0; }
 static bool snap_reserved(const nif_snapparam2_args&) { return false; }
 static bool snap_reserved(const nif_snapfit_args& a) { return a.reserved0 != 0; }
+static bool snap_reserved(const nif_sensors_args& a) { return a.reserved0 != 0; }
 template <class A>
 static int snap_args_check(const A* a, int version, const char* name) {
   if (!a) return fail(NIF_ERR_INVALID, "null");
@@ -2847,6 +2849,75 @@ extern "C" int nif_snapshot_loss_grad(const nif_snapfit_args* a) {
     d.p = c->d_a; d.x = c->d_b; d.y = c->d_d; d.sw = a->sw ? c->d_c.p : nullptr;
   }
   rc = nif_snapshot_loss_grad_dev(&d); if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(c->st));
+  return NIF_OK;
+}
+
+// ---- sensor placement on the last-layer class's basis (include/nif_hip_sensors.h, k_sensors.hip) ------------------------
+static int sensors_check(const nif_sensors_args* a) {
+  int rc = snap_args_check(a, NIF_SENSORS_ABI_VERSION, "nif_sensors_args"); if (rc) return rc;
+  const nif_ctx* c = a->ctx;
+  const char* who = "nif_select_sensors";
+  if (!c) return fail(NIF_ERR_INVALID, "bad argument");
+  if (c->kind != NIF_KIND_LASTLAYER)
+    return fail(NIF_ERR_INVALID, std::string(who) + ": not built for the hypernetwork classes (NIF, NIFMultiScale): their basis du/dz depends on "
+                                 "the latent, and selection on it at a given latent is not built; the field is linear in a fixed basis "
+                                 "phi(x) for NIFMultiScaleLastLayerParameterized only");
+  if (a->M < 1) return fail(NIF_ERR_INVALID, std::string(who) + ": M = " + std::to_string(a->M) + " < 1");
+  if (!sens_supported(c->r)) return fail(NIF_ERR_INVALID, std::string(who) + ": latent_dim " + std::to_string(c->r) + " > 64");
+  if (a->K < 1 || a->K > c->r)
+    return fail(NIF_ERR_INVALID, std::string(who) + ": K = " + std::to_string(a->K) + " outside 1 .. latent_dim = " + std::to_string(c->r) +
+                                 " (the rows of phi live in R^r: more sensors than r is oversampling, a different algorithm that is not built)");
+  if (!a->x || !a->pivots_out || !a->diag_out) return fail(NIF_ERR_INVALID, "bad argument");
+  return snap_not_capturing(c, who);
+}
+// phi of the mesh as nif_x_to_phi runs it, then K dependent steps of one streaming pass each: 2 K launches behind the first (the
+// update behind the last pivot would serve no step)
+static int select_sensors_core(nif_ctx* c, const float* x, long M, const unsigned char* mask, int K, long long* piv, float* d) {
+  int rc = ensure_packed(c); if (rc) return rc;
+  rc = ensure_capacity(c, M, false); if (rc) return rc;
+  const long tiles = (M + 31) / 32, sop = (long)c->so * c->r;
+  const long f_pr = 2L * NIF_SENS_GRID, f_ps = NIF_SENS_GRID, f_q = snap_r4((long)K * c->r), f_sc = tiles * c->so * 32;
+  rc = c->sens.reserve(c, f_pr + f_ps + f_q + f_sc + tiles * sop * 32); if (rc) return rc;
+  { ProfScope p_(c, NIF_PROF_SNET_FWD); ll_phi_pass(c, x, c->si, 0, M); }
+  SensArgs sa; memset(&sa, 0, sizeof(sa));
+  sa.PHI = c->PHI; sa.PR = reinterpret_cast<long long*>(c->sens.p); sa.PS = c->sens + f_pr; sa.Q = sa.PS + f_ps; sa.SC = sa.Q + f_q;
+  sa.RES = sa.SC + f_sc; sa.piv = piv; sa.d = d; sa.mask = mask; sa.M = M; sa.r = c->r; sa.so = c->so;
+  ProfScope p_(c, NIF_PROF_REDUCE);
+  launch_sens_init(sa, c->st);
+  for (int k = 0; k < K; ++k) {
+    sa.k = k;
+    launch_sens_pivot(sa, c->st);
+    if (k + 1 < K) launch_sens_update(sa, c->st);
+  }
+  HIPCHK(hipGetLastError());
+  return NIF_OK;
+}
+extern "C" int nif_select_sensors_dev(const nif_sensors_args* a) {
+  int rc = sensors_check(a); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  static_assert(sizeof(long long) == sizeof(int64_t), "pivots travel as they are");
+  return select_sensors_core(c, a->x, (long)a->M, a->mask, (int)a->K, reinterpret_cast<long long*>(a->pivots_out), a->diag_out);
+}
+extern "C" int nif_select_sensors(const nif_sensors_args* a) {
+  int rc = sensors_check(a); if (rc) return rc;
+  nif_ctx* c = a->ctx;
+  NIF_ENTER(a->ctx, NIF_FLUSH_TAIL)
+  HIPCHK(hipStreamSynchronize(c->st));
+  const long M = (long)a->M, K = (long)a->K;
+  rc = stage(c, c->d_a, a->x, M * c->si); if (rc) return rc;
+  rc = stage(c, c->d_d, nullptr, 3 * K); if (rc) return rc;      // pivots (int64) | d
+  nif_sensors_args d = *a;
+  d.x = c->d_a; d.pivots_out = reinterpret_cast<int64_t*>(c->d_d.p); d.diag_out = c->d_d + 2 * K;
+  if (a->mask) {
+    rc = c->d_c.reserve(c, (M + 3) / 4); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_c.p, a->mask, (size_t)M, hipMemcpyHostToDevice, c->st));
+    d.mask = reinterpret_cast<const uint8_t*>(c->d_c.p);
+  }
+  rc = nif_select_sensors_dev(&d); if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(a->pivots_out, d.pivots_out, sizeof(int64_t) * (size_t)K, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(a->diag_out, d.diag_out, sizeof(float) * (size_t)K, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   return NIF_OK;
 }

@@ -166,6 +166,8 @@ struct nif_ctx {
   DevBuf<float> sd_tmp;
   // the snapshot-wise training step (nif_snapshot_loss_grad*, k_snapfit.hip): every mesh tile's share of dL/da, [mesh tiles][T][r]
   DevBuf<float> sf_dap;
+  // sensor placement (nif_select_sensors*, k_sensors.hip): the partial rows (int64) | partial scores | Q [K][r] | scores | residual
+  DevBuf<float> sens;
   // RCCL communicator of this context (nif_comm.hip): one rank = one ctx = one GPU
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   DevBuf<float> comm_scratch;      // 64 B device scratch for barrier()

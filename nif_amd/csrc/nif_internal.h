@@ -425,6 +425,23 @@ bool snapfit_supported(int r, int so);              // so * r <= 64 (the head's 
 long snapfit_dap_floats(long T, long M, int r);
 void launch_snapfit_head(const SnapFitArgs& a, hipStream_t st);      // grid = mesh tiles
 void launch_snapfit_da(const SnapFitArgs& a, hipStream_t st);        // grid = snapshot tiles; behind the head
+// sensor placement on phi of a mesh (k_sensors.hip; include/nif_hip_sensors.h): greedy pivoted QR of the M so rows of r floats
+#define NIF_SENS_GRID 1024      // the persistent grid's bound = the length of the partial list
+struct SensArgs {
+  const float* PHI;            // [mesh tiles][so*r][32]
+  float* RES;                  // [mesh tiles][so*r][32]   the running residual
+  float* SC;                   // [mesh tiles][so][32]     score of a row, -1 = no candidate
+  float* PS; long long* PR;    // [sens_grid(M, r)]        every workgroup's best (score, row)
+  float* Q;                    // [K][r]
+  long long* piv; float* d;    // [K]
+  const unsigned char* mask;   // [M] or null
+  long M; int r, so, k;        // k: the step
+};
+int sens_grid(long M, int r);
+bool sens_supported(int r);                                          // r <= 64 (a row in registers)
+void launch_sens_init(const SensArgs& a, hipStream_t st);
+void launch_sens_pivot(const SensArgs& a, hipStream_t st);           // step a.k: q_k, pivots[k], d[k] from the partials of the pass before
+void launch_sens_update(const SensArgs& a, hipStream_t st);          // step a.k: q_k out of every row, the partials of step k + 1
 // last-layer class at 129..512 units: one dense layer of the shared SIREN ShapeNet per launch, tiled over a workgroup (k_wide.hip).
 // Every activation / adjoint buffer is [tiles][features][32] with exactly `features` rows per tile (the layout of PHI / DPHI)
 struct WideArgs {

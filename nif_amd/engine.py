@@ -663,6 +663,36 @@ class Engine(object):
             return self.grad_read_loss(), None
         return self.grad_read()
 
+    # sensor placement on the last-layer class's basis (include/nif_hip_sensors.h; Model.select_sensors cuts the result at the rank)
+    def _sensors_args(self, x, m, mask, k, pivots, diag):
+        a = _lib.nif_sensors_args()
+        a.abi_version, a.ctx, a.M, a.K = _lib.NIF_SENSORS_ABI_VERSION, self.ctx, int(m), int(k)
+        a.x, a.mask, a.pivots_out, a.diag_out = x, mask, pivots, diag
+        return a
+
+    def select_sensors_dev(self, d_x, m, d_mask, k, d_pivots, d_diag):
+        """greedy pivoted QR of phi(x)^T from device pointers x [m, si], mask [m] bytes or None -> pivots [k] int64, diag [k] float32;
+        asynchronous on the context's stream"""
+        self._not_capturing("nif_select_sensors")
+        a = self._sensors_args(d_x, m, d_mask, k, d_pivots, d_diag)
+        check(self.lib.nif_select_sensors_dev(C.byref(a)))
+
+    def select_sensors(self, x, n_sensors, mask=None):
+        """host arrays x [M, si], mask [M] (nonzero = a sensor can stand there) or None -> (pivots [K] int64: rows m * so + s of
+        model_x_to_phi(x) reshaped [M so, r], -1 from the step that found none; diag [K] float32)"""
+        self._not_capturing("nif_select_sensors")
+        x = self._rows(x, self.spec.si_dim, "coordinates")
+        m, k = x.shape[0], int(n_sensors)
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mk.shape != (m,):
+                raise ValueError("select_sensors: expected mask of shape (%d,), got %s" % (m, mk.shape))
+        piv, diag = np.full((max(k, 0),), -1, dtype=np.int64), np.zeros((max(k, 0),), dtype=np.float32)
+        a = self._sensors_args(ptr(x), m, ptr(mk), k, ptr(piv), ptr(diag))
+        check(self.lib.nif_select_sensors(C.byref(a)))
+        return piv, diag
+
     # Sobolev (two-output model u, du/dx; include/nif_hip.h nif_sobolev_*)
     def sobolev_loss_grad_dev(self, d_x, d_y, d_g, d_sw, b_local, b_global, x_index, w_jac, y_index=None):
         """y_index = None: the derivative term over every output; else over the listed outputs (d_g rows stay [so][nx])"""

@@ -2,6 +2,7 @@
 NIF / NIFMultiScale / NIFMultiScaleLastLayerParameterized with build/model/compile/fit/predict and
 the sub-model extractors.  Same constructor arguments, attribute names and error behaviour as the
 reference (file:line cited per method); every number comes from libnif_hip.so (HIP, gfx950)."""
+import collections
 import contextlib
 import json
 import os
@@ -18,6 +19,8 @@ from .optimizers import Adam, ema_of, get as get_optimizer, grad_transform_of, s
 from .spec import Spec
 
 _global_rng = [np.random.default_rng()]
+
+SensorResult = collections.namedtuple("SensorResult", ["point", "component", "x", "diag", "rank"])
 
 
 def set_seed(seed):
@@ -542,6 +545,53 @@ class Model(object):
             return lm_encode(lambda lat: e.snapshot_normal_eq(lat, samples), z0, counts, so, max_iter, tol)
         finally:
             samples.free()
+
+    def select_sensors(self, x, n_sensors=None, mask=None, rtol=None):
+        """Where to put sensors on the mesh x [M, si] so that encode_snapshots recovers a field's latent well from readings there:
+        QDEIM on the learned basis.  For NIFMultiScaleLastLayerParameterized u_t(x) = phi(x) . a(p_t) + bias, and the candidates are
+        the M so rows of model_x_to_phi(x) reshaped [M so, r], a sensor being a (point, component) pair; the device runs the greedy
+        column-pivoted QR of Phi^T (include/nif_hip_sensors.h): each step takes the candidate with the largest residual norm d_k
+        (ties: the lowest row) and projects its direction out of every row.  n_sensors defaults to r and cannot exceed it (more
+        sensors than r is oversampling, a different algorithm); mask [M] bool marks the points where a sensor can stand (None: all).
+        The result is cut at the first step with d_k <= rtol d_0 (default rtol: r float32 epsilons; rtol=0 keeps every step that found
+        a row): `rank` sensors are returned, fewer than asked for when the candidates or the rank of phi run out.
+        Returns SensorResult(point [K'] int64, component [K'] int64, x [K', si] -- x[point] --, diag [K'] float32 -- the d_k --, rank
+        = K').  To use it, pass xs = x[np.unique(point)] and the readings u[:, np.unique(point), :] there to
+        encode_snapshots(xs, readings, ...): a sensor that reads all so components at its point only adds rows to the least-squares
+        problem.  Not built: the hypernetwork classes (their basis du/dz depends on the latent), n_sensors > r, whole points as
+        pivots, weighted candidates, more than one GPU."""
+        if self._role != "full":
+            raise ValueError("select_sensors exists on the full model only (%s is a sub-model view)" % self._role)
+        s = self._owner._spec
+        if s.kind != "NIFMultiScaleLastLayerParameterized":
+            raise NotImplementedError("select_sensors: built for NIFMultiScaleLastLayerParameterized, whose fields are linear in the "
+                                      "fixed basis phi(x); the basis of %s depends on the latent, and selection on du/dz at a given "
+                                      "latent is not built" % s.kind)
+        r, so = s.pi_hidden, s.so_dim
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim == 1 and s.si_dim == 1:
+            x = x[:, None]
+        if x.ndim != 2 or x.shape[1] != s.si_dim or x.shape[0] < 1:
+            raise ValueError("select_sensors: x must have shape (M >= 1, si_dim=%d), got %r" % (s.si_dim, x.shape))
+        k = r if n_sensors is None else int(n_sensors)
+        if k < 1 or k > r:
+            raise ValueError("select_sensors: n_sensors = %d outside 1 .. latent_dim = %d (more sensors than latent dimensions is "
+                             "oversampling, which is not built)" % (k, r))
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.shape != (x.shape[0],):
+                raise ValueError("select_sensors: mask must have shape (M=%d,), got %r" % (x.shape[0], mask.shape))
+            mask = mask != 0
+        rtol = float(r * np.finfo(np.float32).eps if rtol is None else rtol)
+        if rtol < 0.0:
+            raise ValueError("select_sensors: rtol >= 0")
+        piv, diag = self._engine.select_sensors(x, k, mask)
+        piv, diag = np.asarray(piv, dtype=np.int64), np.asarray(diag, dtype=np.float32)
+        keep = (piv >= 0) & (diag > np.float32(rtol) * diag[0])
+        rank = int(k if keep.all() else np.argmin(keep))
+        piv, diag = piv[:rank], diag[:rank]
+        point, component = piv // so, piv % so
+        return SensorResult(point, component, x[point], diag, rank)
 
     # ---- training --------------------------------------------------------------------------------
     # Keras' compile(metrics=[...]): names / metric objects -> (history key, kind).  Unweighted (Keras applies sample_weight to
@@ -1250,6 +1300,10 @@ class SobolevModel(Model):
     def fit_snapshots(self, *args, **kwargs):
         raise NotImplementedError("SobolevModel.fit_snapshots: the snapshot-wise step has no derivative outputs (fit() on the expanded "
                                   "table trains the two- and three-output models)")
+
+    def select_sensors(self, *args, **kwargs):
+        """Model.select_sensors of the wrapped model: the basis phi(x) has no derivative outputs to select on"""
+        return Model.select_sensors(self, *args, **kwargs)
 
     def _run(self, x):
         if self._order == 2:      # HessianLayer(model, y_index, x_index)(x), the layer the model wraps
